@@ -7,8 +7,13 @@
 
 One step = forward + 5-term criterion + backward + fused SGD of GRFBUNet(3, 2, base_c=32) on a device-resident synthetic
 batch of 8 x 3 x 512 x 512 per GPU, bf16 activation storage / MFMA, fp32 accumulation and master weights.
-Prints ONE JSON line (rank 0) with the extra `roofline` (dominant kernel, timed with HIP events on the launch stream in an
-instrumented step outside the timed region) and `cpu_baseline` (CPU oracle on a bounded sample) objects.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the line; the `roofline`,
+`roofline_wgrad`, `families` and `cpu_baseline` objects stay null.  --full adds them: the dominant kernel, timed with HIP events on
+the launch stream in an instrumented step outside the timed region, and the CPU oracle on a bounded sample.
+
+--dump-outputs DIR writes what the timed path computed in its last step (the loss, and the state_dict the caller's model holds
+after it; CLIPSeg inference: the logits) as DIR/<name>.npy, float32 (float64 for integer buffers), 64 MB at most; the inputs
+and the initial weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import struct
@@ -39,6 +44,38 @@ def synth_batch(n, h, w, seed, device):
         t[i, max(0, cy - hh // 2):cy + hh // 2, max(0, cx - ww // 2):cx + ww // 2] = 1
     t[torch.rand(n, h, w, generator=g) < 0.01] = 255     # 1 % ignore pixels
     return x.to(device), t.to(device)
+
+
+DUMP_BUDGET_BYTES = 64_000_000                         # --dump-outputs in all, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy: floating tensors as float32 (float64 stays float64), integer ones as float64.  Over the
+    64 MB budget every array is cut down to the same fraction of its elements, a fixed seeded sample of its flattened values."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        t = t.double() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float()
+        host[name] = t
+    total = sum(t.numel() * t.element_size() for t in host.values())
+    frac = min(1.0, (DUMP_BUDGET_BYTES - 256 * len(host)) / total) if total else 1.0       # 256: room for one .npy header
+    for name, t in host.items():
+        if frac < 1.0:
+            k = max(1, int(t.numel() * frac))
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+    print(f"[bench] {len(host)} output arrays written to {path}" + (f" (seeded sample of {frac:.3f} of each)" if frac < 1.0 else ""),
+          file=sys.stderr)
+
+
+def _state_arrays(model, loss):
+    """what a caller of the training step holds after it: the loss it returned and the model's parameters and buffers"""
+    out = {"loss": loss.detach().reshape(1)}
+    out.update({"state." + k: v for k, v in model.state_dict().items()})
+    return out
 
 
 class _Span:
@@ -321,19 +358,26 @@ def clipseg_bench(args, dev, rank, world):
         def step():
             loss = T.bce_with_logits(m(x, cond)[0], target)
             opt.zero_grad(); loss.backward(); opt.step()
+            return loss
     else:
         m.eval()
 
         def step():
-            m(x, prompts)
+            return m(x, prompts)[0]
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        res = step()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        if train:
+            dump_outputs(args.dump_outputs, dict({"loss": res.detach().reshape(1)},
+                                                 **{"param." + k: p for k, p in m.named_parameters() if p.requires_grad}))
+        else:
+            dump_outputs(args.dump_outputs, {"logits": res})
     if rank == 0:
         what = ("decoder training step (frozen ViT-B/16 forward + decoder fwd/bwd + BCE + AdamW)" if train
                 else "forward (text encoder uncached)")
@@ -467,6 +511,8 @@ def ablation_bench(args, dev, rank, world):
         loss = step()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, _state_arrays(model, loss))
     if rank == 0:
         k10 = rows[1]
         print(json.dumps({
@@ -488,11 +534,17 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the instrumented eager step (roofline, roofline_wgrad, families) "
+                         "and the CPU-oracle baseline (cpu_baseline; at N > 1 carried from the checked-in N = 1 line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss and model state; CLIPSeg inference: logits) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU-oracle baseline")
     ap.add_argument("--workload", default="egm_unet_train", choices=["egm_unet_train", "clipseg_infer", "clipseg_train", "ablation_1024"],
                     help="egm_unet_train = the headline metric (BASELINE.json configs[1]); clipseg_infer = configs[3] (ViT-B/16 image+text "
                          "encode + decoder on 352x352), reported as a secondary line")
-    ap.add_argument("--instrument", action="store_true", help="N > 1: also run the instrumented eager step (roofline / families objects) on every rank")
+    ap.add_argument("--instrument", action="store_true", help="N > 1: also run the instrumented eager step (roofline / families objects) on every rank "
+                                                                "(at N = 1, --full runs it)")
     ap.add_argument("--eager", action="store_true", help="issue every kernel from Python instead of replaying the captured hipGraph")
     ap.add_argument("--dp-single-graph", action="store_true",
                     help="N > 1: one captured graph (forward + backward) followed by the exchange and the SGD launch, instead of the three-graph "
@@ -599,14 +651,16 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     final_loss = float(loss.detach())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, _state_arrays(model, loss))
 
     roofline = roofline_wgrad = families = None
     cpu = None
-    # Instrumented eager step outside the timed region: every C-ABI call bracketed by HIP events on the launch stream.  At N > 1 it is
-    # off unless --instrument (EVERY rank would have to run it, its hook-driven gradient exchange included, after the measurement);
-    # EGM_BENCH_NO_INSTRUMENT=1 switches it off at N = 1 too -- the rocprofv3 --pmc passes use that, so that their per-kernel
-    # averages cover the graph replays only (tools/pmc_traffic.py).
-    instrument = (world == 1 or args.instrument) and not os.environ.get("EGM_BENCH_NO_INSTRUMENT")
+    # Instrumented eager step outside the timed region: every C-ABI call bracketed by HIP events on the launch stream.  Only with
+    # --full at N = 1; at N > 1 it is off unless --instrument (EVERY rank would have to run it, its hook-driven gradient exchange
+    # included, after the measurement); EGM_BENCH_NO_INSTRUMENT=1 switches it off in any case -- the rocprofv3 --pmc passes use
+    # that, so that their per-kernel averages cover the graph replays only (tools/pmc_traffic.py).
+    instrument = ((world == 1 and args.full) or args.instrument) and not os.environ.get("EGM_BENCH_NO_INSTRUMENT")
     kt = None
     if instrument:
         # after a captured graph the reducer's autograd hooks are off: switch them back on for this eager step
@@ -675,7 +729,7 @@ def main():
               ", ".join(f"{k}={v[1]:.2f}({v[0]})" for k, v in top) + f"; total {total_ms:.2f}", file=sys.stderr)
         if os.environ.get("EGM_CONV_TABLE"):
             print("\n".join(kt.conv_table()), file=sys.stderr)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         if world == 1:
             cpu = cpu_baseline()
         else:

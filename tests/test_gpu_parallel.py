@@ -116,7 +116,7 @@ def test_bench_two_rank_code_path_rehearsal():
     env = dict(os.environ, EGM_BENCH_SINGLE_DEVICE="1", EGM_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29531", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "128",
-           "--no-cpu-baseline", "--instrument"]
+           "--no-cpu-baseline", "--full", "--instrument"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -246,7 +246,7 @@ def test_bench_starts_its_own_ranks_single_graph_variant():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(EGM_BENCH_SINGLE_DEVICE="1", EGM_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "128",
-                        "--dp-single-graph"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--dp-single-graph", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["world_size"] == 2 and line["config"]["global_batch"] == 16 and line["value"] > 0

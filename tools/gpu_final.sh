@@ -2,7 +2,7 @@
 # Evidence run on the GPU box, one script for every round:  tools/gpu_final.sh <tag> [steps ...]
 #   steps (default: all, in this order): tests bench trace pmc ablation
 #   tests     python -m pytest tests -m gpu (optionally narrowed by PYTEST_ARGS)
-#   bench     the headline line -> $out/bench.json
+#   bench     the headline line with its roofline and CPU baseline (bench.py --full) -> $out/bench.json
 #   trace     rocprofv3 --kernel-trace --stats of the bench command -> kernel_trace_summary.md, timeline.tsv, kernel_stats.csv
 #   pmc       three separate --pmc passes over GRAPH REPLAYS ONLY (EGM_BENCH_NO_INSTRUMENT=1): FETCH_SIZE, WRITE_SIZE -> pmc_traffic.json;
 #             SQ_VALU_MFMA_BUSY_CYCLES + GRBM_GUI_ACTIVE -> pmc_mfma_util.json.  The raw counter CSVs are kept (gzip) beside them.
@@ -19,7 +19,7 @@ if has tests; then
   tail -2 "$out/tests.log"
 fi
 if has bench; then
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err" || { tail -30 "$out/bench.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err" || { tail -30 "$out/bench.err"; exit 1; }
   python -c "import json,sys; d=json.loads(open('$out/bench.json').read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['bound'], d['roofline']['frac'])"
 fi
 if has trace; then
