@@ -1,5 +1,7 @@
 """Inference operators of the CLIP / CLIPSeg path over libegm_hip.so (no autograd: the CLIP backbone is frozen in the
 reference, models/clipseg.py:155-156, and only forward passes are used by predict_CLIPseg.py / eval_CLIPseg.py)."""
+import math
+
 import torch
 
 from .._lib import dtype_code, lib, ptr, stream
@@ -117,4 +119,40 @@ def attention(qkv, n_heads, mode, cls_mask=None):
         L_.call("egm_attn_mask_cls", code, ptr(P), Lp, L * Lp, ptr(m), m.shape[0], B * n_heads, L - 1, stream())
     out = torch.empty((B, L, D), dtype=dt, device=dev)
     gemm(P, Lp, qkv, D3, False, out, D, L, dh, L, dt, nb1=B, nb2=n_heads, sA=(n_heads * L * Lp, L * Lp), sB=(L * D3, dh), sC=(L * D, dh), offB=2 * D)
+    return out
+
+
+_refine_cache = {}
+REFINE_PATCH = 16
+
+
+def refine_packed(w0, w1, w2, dtype):
+    """The refined head's three weights (Conv2d [rd,rd,3,3], ConvTranspose2d [rd,rd/2,4,4], [rd/2,1,4,4]) in the operand layouts of
+    csrc/clipseg_refine.hip, in the activation dtype; cached like cast_weight (parameter storage + version + cast generation)."""
+    rd = w0.shape[0]
+    slot = tuple(id(w) for w in (w0, w1, w2))
+    key = tuple((w.data_ptr(), w._version) for w in (w0, w1, w2)) + (_cast_generation[0], dtype)
+    hit = _refine_cache.get((slot, dtype))
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    n = lib().query("egm_refine_packed_elems", rd, REFINE_PATCH)
+    out = torch.empty(n, dtype=dtype, device=w0.device)
+    src = [w.detach().float().contiguous() for w in (w0, w1, w2)]
+    lib().call("egm_refine_pack", dtype_code(dtype), ptr(src[0]), ptr(src[1]), ptr(src[2]), ptr(out), rd, REFINE_PATCH, stream())
+    _refine_cache[(slot, dtype)] = (key, out)
+    return out
+
+
+def refine_head(a, w0, b0, w1, b1, w2, b2, tok_off=1, h=None):
+    """complex_trans_conv head (models/clipseg.py:405-411) on a [B, Ltot, rd] (tok_off leading tokens skipped) -> fp32 [B, 1, 16g, 16g].
+    h: optional [B, g*g, rd] tensor in a's dtype that receives the first ReLU's output (kept by the training backward)."""
+    B, Ltot, rd = a.shape
+    g = int(math.isqrt(Ltot - tok_off))
+    if g * g != Ltot - tok_off:
+        raise RuntimeError(f"refine_head: {Ltot - tok_off} grid tokens do not form a square grid")
+    a = a.contiguous()
+    pk = refine_packed(w0, w1, w2, a.dtype)
+    out = torch.empty((B, 1, g * REFINE_PATCH, g * REFINE_PATCH), dtype=torch.float32, device=a.device)
+    lib().call("egm_refine_fwd", dtype_code(a.dtype), ptr(a), tok_off, Ltot, ptr(pk), ptr(b0.detach().float().contiguous()),
+               ptr(b1.detach().float().contiguous()), ptr(b2.detach().float().contiguous()), ptr(h), ptr(out), B, g, rd, REFINE_PATCH, stream())
     return out

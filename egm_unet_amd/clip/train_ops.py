@@ -291,6 +291,44 @@ class TransConvFn(Function):
         return da.reshape(a.shape), dw.reshape(weight.shape), db
 
 
+class RefineFn(Function):
+    """The complex_trans_conv head (models/clipseg.py:405-411): Conv2d 3x3 -> ReLU -> ConvTranspose2d 4/4 -> ReLU -> ConvTranspose2d 4/4
+    on the token grid, csrc/clipseg_refine.hip.  a [B, Ltot, rd] (token 0 = cls, its gradient row is 0), the six parameters of the
+    nn.Sequential in order -> fp32 [B, 1, 16g, 16g].  Forward: one launch (+ the cached weight pack); backward: three, z is recomputed
+    from the saved first ReLU output h."""
+
+    @staticmethod
+    def forward(ctx, a, w0, b0, w1, b1, w2, b2):
+        B, Ltot, rd = a.shape
+        g = int(math.isqrt(Ltot - 1))
+        a = a.contiguous()
+        h = torch.empty((B, g * g, rd), dtype=a.dtype, device=a.device)
+        out = O.refine_head(a, w0, b0, w1, b1, w2, b2, tok_off=1, h=h)
+        ctx.save_for_backward(a, h, w0, w1, w2, b1)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, h, w0, w1, w2, b1 = ctx.saved_tensors
+        B, Ltot, rd = a.shape
+        g, dt, dev, L = int(math.isqrt(Ltot - 1)), a.dtype, a.device, lib()
+        gout = gout.contiguous().float()
+        pk = O.refine_packed(w0, w1, w2, dt)
+        ws = torch.empty(L.query("egm_refine_bwd_workspace", B, g, rd, O.REFINE_PATCH) // 4, dtype=torch.float32, device=dev)
+        da = torch.empty_like(a)
+        f32 = dict(dtype=torch.float32, device=dev)
+        dw0, dw1, dw2 = torch.empty(w0.shape, **f32), torch.empty(w1.shape, **f32), torch.empty(w2.shape, **f32)
+        db0, db1, db2 = torch.empty(rd, **f32), torch.empty(rd // 2, **f32), torch.empty(1, **f32)
+        L.call("egm_refine_bwd", dtype_code(dt), ptr(gout), ptr(a), 1, Ltot, ptr(h), ptr(pk), ptr(b1.detach().float().contiguous()), ptr(da),
+               ptr(dw0), ptr(db0), ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), ptr(ws), B, g, rd, O.REFINE_PATCH, stream())
+        return da, dw0, db0, dw1, db1, dw2, db2
+
+
+def refine(a, seq):
+    """RefineFn over the reference's nn.Sequential(Conv2d, ReLU, ConvTranspose2d, ReLU, ConvTranspose2d)."""
+    return RefineFn.apply(a, seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias, seq[4].weight, seq[4].bias)
+
+
 class BCEWithLogitsFn(Function):
     """nn.BCEWithLogitsLoss() (mean) on fp32 logits / targets of equal shape (experiments/phrasecut.yaml: loss)."""
 

@@ -39,7 +39,7 @@ class CLIPDensePredT(nn.Module):
                  clip_weights="weights/longclip-B.pt"):
         super().__init__()
         for flag, name in ((extra_blocks, "extra_blocks"), (reduce_cond, "reduce_cond"), (fix_shift, "fix_shift"), (upsample, "upsample"),
-                           (n_tokens, "n_tokens"), (complex_trans_conv, "complex_trans_conv"), (trans_conv, "trans_conv")):
+                           (n_tokens, "n_tokens"), (trans_conv, "trans_conv")):
             if flag:
                 raise NotImplementedError(f"egm_unet_amd: CLIPDensePredT({name}=...) is not used by the reference scripts and not implemented")
         cfg = _VIT[version]
@@ -63,7 +63,20 @@ class CLIPDensePredT(nn.Module):
         self.token_shape = cfg["token_shape"]
         self.shift_vector = None
         ks = (cfg["patch"], cfg["patch"])
-        self.trans_conv = nn.ConvTranspose2d(reduce_dim, 1, ks, stride=ks)
+        self.complex_trans_conv = bool(complex_trans_conv)
+        if not complex_trans_conv:
+            self.trans_conv = nn.ConvTranspose2d(reduce_dim, 1, ks, stride=ks)
+        else:                                                       # models/clipseg.py:403-414, the rd64-uni-refined checkpoint
+            if cfg["patch"] != 16 or reduce_dim not in (64, 128):
+                raise NotImplementedError(f"egm_unet_amd: complex_trans_conv needs ViT-B/16 and reduce_dim 64 or 128 (got {version}, {reduce_dim})")
+            tp = cfg["patch"] // 4
+            self.trans_conv = nn.Sequential(
+                nn.Conv2d(reduce_dim, reduce_dim, kernel_size=3, padding=1),
+                nn.ReLU(),
+                nn.ConvTranspose2d(reduce_dim, reduce_dim // 2, kernel_size=tp, stride=tp),
+                nn.ReLU(),
+                nn.ConvTranspose2d(reduce_dim // 2, 1, kernel_size=tp, stride=tp),
+            )
         depth = len(extract_layers)
         self.reduces = nn.ModuleList([nn.Linear(768, reduce_dim) for _ in range(depth)])
         self.blocks = nn.ModuleList([nn.TransformerEncoderLayer(d_model=reduce_dim, nhead=n_heads) for _ in range(depth)])
@@ -182,7 +195,10 @@ class CLIPDensePredT(nn.Module):
                 a = T.FilmFn.apply(a, T.linear(condT, self.film_mul.weight, self.film_mul.bias),
                                    T.linear(condT, self.film_add.weight, self.film_add.bias))
             a = self._encoder_layer_train(blk, a)
-        out = T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
+        if self.complex_trans_conv:
+            out = T.refine(a, self.trans_conv)
+        else:
+            out = T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
         if return_features:
             return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts_all]
         return out,
@@ -205,6 +221,12 @@ class CLIPDensePredT(nn.Module):
                 mul, add = O.linear(condT, self.film_mul.weight, self.film_mul.bias), O.linear(condT, self.film_add.weight, self.film_add.bias)
                 L_.call("egm_film", code, ptr(a), ptr(mul), ptr(add), bs, a.shape[1], a.shape[2], stream())
             a = self._encoder_layer(blk, a)
+        if self.complex_trans_conv:
+            tc = self.trans_conv
+            out = O.refine_head(a, tc[0].weight, tc[0].bias, tc[2].weight, tc[2].bias, tc[4].weight, tc[4].bias)
+            if return_features:
+                return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts_all]
+            return out,
         Ltot, rd = a.shape[1], a.shape[2]
         g = int(math.isqrt(Ltot - 1))
         P = self.trans_conv.kernel_size[0]

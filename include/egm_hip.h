@@ -669,6 +669,25 @@ int egm_dropout(int dtype, const void* x, const void* residual, void* out, long 
 int egm_attn_mask_cls(int dtype, void* probs, int ldp, long long head_stride, const float* mask, int nmask, int nbh, int ntok,
                       egm_stream_t s);
 
+/* ---- CLIPSeg refined head, complex_trans_conv=True (models/clipseg.py:401-414; experiments/phrasecut.yaml:74 rd64-uni-refined) --------
+ * Conv2d(rd, rd, 3, pad 1) -> ReLU -> ConvTranspose2d(rd, rd/2, 4, stride 4) -> ReLU -> ConvTranspose2d(rd/2, 1, 4, stride 4) on the g x g
+ * token grid of a [B][Ltot][rd] (rows tok_off .. tok_off + g*g - 1; the leading class token is skipped), out fp32 [B][1][16g][16g].
+ * Supported: patch 16 (ViT-B/16), rd 64 or 128, 1 <= g <= 32; anything else returns EGM_ERR_UNSUPPORTED.
+ * egm_refine_pack: the fp32 parameters w0 [rd][rd][3][3], w1 [rd][rd/2][4][4], w2 [rd/2][1][4][4] -> packed, egm_refine_packed_elems(rd,
+ *   patch) elements in `dtype` (operand layouts of the forward and backward products; rerun after every optimizer step).
+ * egm_refine_fwd: ONE launch.  h (dtype [B][g*g][rd], the first ReLU's output, for the backward) may be NULL.
+ * egm_refine_bwd: three launches from dout fp32 [B][1][16g][16g], the forward's a and h: da (dtype, shape of a, rows outside the grid 0)
+ *   and the parameter gradients (fp32, parameter shapes; overwritten).  Weight gradients are per-slice slabs in the workspace
+ *   (egm_refine_bwd_workspace() bytes) summed in fixed order: bitwise reproducible. */
+long long egm_refine_packed_elems(int rd, int patch);
+long long egm_refine_bwd_workspace(int B, int g, int rd, int patch);
+int egm_refine_pack(int dtype, const float* w0, const float* w1, const float* w2, void* packed, int rd, int patch, egm_stream_t s);
+int egm_refine_fwd(int dtype, const void* a, int tok_off, int Ltot, const void* packed, const float* b0, const float* b1,
+                   const float* b2, void* h, float* out, int B, int g, int rd, int patch, egm_stream_t s);
+int egm_refine_bwd(int dtype, const float* dout, const void* a, int tok_off, int Ltot, const void* h, const void* packed,
+                   const float* b1, void* da, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
+                   void* workspace, int B, int g, int rd, int patch, egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
