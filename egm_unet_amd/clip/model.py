@@ -75,9 +75,10 @@ class VisionTransformer(nn.Module):
             self._pos_cache = {key: torch.cat([pos[:1].float(), grid]).contiguous()}
         return self._pos_cache[key]
 
-    def run(self, img, dtype, extract_layers=(), csa_all_layers=True, cls_mask=None):
+    def run(self, img, dtype, extract_layers=(), csa_all_layers=True, cls_mask=None, stop_after=None):
         """img fp32 NCHW -> (cls feature [B, output_dim], [activations [B, L, D] at extract_layers]).
-        cls_mask = (layer index | 'all', [B, tokens] fp32): see CLIPDensePredT.visual_forward."""
+        cls_mask = (layer index | 'all', [B, tokens] fp32): see CLIPDensePredT.visual_forward.
+        stop_after = block index: the blocks behind it are skipped (they do not change earlier activations) and the cls feature is None."""
         B, C, H, W = img.shape
         P = self.patch_size
         gh, gw = H // P, W // P
@@ -96,6 +97,8 @@ class VisionTransformer(nn.Module):
             x = blk.run(x, "csa" if (csa_all_layers or i == n - 1) else "full", m)
             if i in extract_layers:
                 acts.append(x)
+            if stop_after is not None and i >= stop_after:
+                return None, acts
         cls = O.layernorm(x[:, 0].contiguous(), self.ln_post)
         return O.matmul_kn(cls, self.proj), acts
 

@@ -156,3 +156,49 @@ def refine_head(a, w0, b0, w1, b1, w2, b2, tok_off=1, h=None):
     lib().call("egm_refine_fwd", dtype_code(a.dtype), ptr(a), tok_off, Ltot, ptr(pk), ptr(b0.detach().float().contiguous()),
                ptr(b1.detach().float().contiguous()), ptr(b2.detach().float().contiguous()), ptr(h), ptr(out), B, g, rd, REFINE_PATCH, stream())
     return out
+
+
+_baseline_cache = {}
+BASELINE_PATCH = 16
+
+
+def baseline_supported(rd, rd2, patch, dtype):
+    """True when csrc/clipseg_baseline.hip takes the shape (patch 16, rd / rd2 multiples of 16 up to 128) in this dtype (bf16)."""
+    return dtype == torch.bfloat16 and lib().cdll.egm_baseline_supported(rd, rd2, patch) == 1
+
+
+def baseline_packed(w_red, w1, w2, wt):
+    """CLIPDenseBaseline's four head weights (reduce [rd,768], reduce2.0 [rd2,rd], reduce2.2 [rd,rd2], trans_conv [rd,1,16,16]) in the bf16
+    operand layouts of csrc/clipseg_baseline.hip; cached like cast_weight (parameter storage + version + cast generation)."""
+    ws = (w_red, w1, w2, wt)
+    slot = tuple(id(w) for w in ws)
+    key = tuple((w.data_ptr(), w._version) for w in ws) + (_cast_generation[0],)
+    hit = _baseline_cache.get(slot)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    rd, rd2 = w_red.shape[0], w1.shape[0]
+    out = torch.empty(lib().query("egm_baseline_packed_elems", rd, rd2, BASELINE_PATCH), dtype=torch.bfloat16, device=w_red.device)
+    src = [w.detach().float().contiguous() for w in ws]
+    lib().call("egm_baseline_pack", dtype_code(torch.bfloat16), ptr(src[0]), ptr(src[1]), ptr(src[2]), ptr(src[3]), ptr(out), rd, rd2,
+               BASELINE_PATCH, stream())
+    _baseline_cache[slot] = (key, out)
+    return out
+
+
+def baseline_head(x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off=1, u=None, h=None):
+    """CLIPDenseBaseline's head (models/clipseg.py:567-583) as ONE launch: x [B, Ltot, 768] bf16 (tok_off leading tokens skipped),
+    mul / add [B, rd] bf16 (film_mul / film_add of the conditional) -> fp32 [B, 1, 16g, 16g].  u [B, g*g, rd] / h [B, g*g, rd2] (bf16,
+    both or neither) receive reduce's output and the ReLU output for the training backward."""
+    B, Ltot, _ = x.shape
+    rd, rd2 = w_red.shape[0], w1.shape[0]
+    g = int(math.isqrt(Ltot - tok_off))
+    if g * g != Ltot - tok_off:
+        raise RuntimeError(f"baseline_head: {Ltot - tok_off} grid tokens do not form a square grid")
+    x = x.contiguous()
+    pk = baseline_packed(w_red, w1, w2, wt)
+    out = torch.empty((B, 1, g * BASELINE_PATCH, g * BASELINE_PATCH), dtype=torch.float32, device=x.device)
+    f32 = [t.detach().float().contiguous() for t in (b_red, b1, b2, bt)]
+    mul, add = mul.contiguous(), add.contiguous()
+    lib().call("egm_baseline_fwd", dtype_code(x.dtype), ptr(x), tok_off, Ltot, ptr(mul), ptr(add), ptr(pk),
+               ptr(f32[0]), ptr(f32[1]), ptr(f32[2]), ptr(f32[3]), ptr(u), ptr(h), ptr(out), B, g, rd, rd2, BASELINE_PATCH, stream())
+    return out

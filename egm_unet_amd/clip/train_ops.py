@@ -329,6 +329,71 @@ def refine(a, seq):
     return RefineFn.apply(a, seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias, seq[4].weight, seq[4].bias)
 
 
+def _linear_wgrad(x2, g2):
+    """dW [N, K] fp32 = g2^T x2 for x2 [M, K], g2 [M, N] in the activation dtype: LinearFn's weight-gradient routes.  The conv route treats
+    the M rows as the pixels of a 1x1 convolution, arranged 8 high when M % 8 == 0 (the kernel's pixel tiles are 8 rows high)."""
+    (M, K), N, dt = x2.shape, g2.shape[1], x2.dtype
+    dw = torch.empty((N, K), dtype=torch.float32, device=x2.device)
+    if _WGRAD_AS_CONV and N % 8 == 0 and K % 8 == 0 and M >= 4096:
+        L = lib()
+        H = 8 if M % 8 == 0 else 1
+        ws = torch.empty(L.query("egm_conv_wgrad_workspace", 1, H, M // H, K, N, 1, 1) // 4 + 4, dtype=torch.float32, device=x2.device)
+        L.call("egm_conv_wgrad", dtype_code(dt), ptr(x2), K, ptr(g2), N, ptr(dw), ptr(ws), 1, H, M // H, K, N, K, N, 1, 1, 1, 1, 0, stream())
+        return dw
+    (gT, mp), (xT, _) = _transpose(g2, M, N), _transpose(x2, M, K)
+    if mp == M:
+        _wgrad_gemm(gT, mp, xT, mp, True, dw, N, K, M, dt)
+    else:
+        O.gemm(gT, mp, xT, mp, True, dw, K, N, K, M, dt, c_f32=True)
+    return dw
+
+
+class BaselineHeadFn(Function):
+    """CLIPDenseBaseline's head (models/clipseg.py:567-583), csrc/clipseg_baseline.hip: reduce -> FiLM -> reduce2 (Linear, ReLU, Linear)
+    -> ConvTranspose2d(rd -> 1, 16, 16) per token.  x [B, Ltot, 768] bf16 (token 0 = cls, dropped; frozen backbone: no gradient),
+    mul / add [B, rd] bf16 (film_mul / film_add outputs), the eight head parameters -> fp32 [B, 1, 16g, 16g].
+    Forward: one launch (+ the cached weight pack), saving reduce's output u and the ReLU output h.  Backward: two launches for everything
+    but reduce's own weight gradient, which takes LinearFn's weight-gradient route on du (class-token rows 0) and x."""
+
+    @staticmethod
+    def forward(ctx, x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt):
+        B, Ltot, _ = x.shape
+        g, rd, rd2 = int(math.isqrt(Ltot - 1)), w_red.shape[0], w1.shape[0]
+        x = x.contiguous()
+        u = torch.empty((B, g * g, rd), dtype=x.dtype, device=x.device)
+        h = torch.empty((B, g * g, rd2), dtype=x.dtype, device=x.device)
+        out = O.baseline_head(x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off=1, u=u, h=h)
+        ctx.save_for_backward(x, u, h, mul.contiguous(), add.contiguous(), w_red, w1, w2, wt, b2)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, u, h, mul, add, w_red, w1, w2, wt, b2 = ctx.saved_tensors
+        B, Ltot, K = x.shape
+        g, rd, rd2, dt, dev, L = int(math.isqrt(Ltot - 1)), w_red.shape[0], w1.shape[0], x.dtype, x.device, lib()
+        gout = gout.contiguous().float()
+        pk = O.baseline_packed(w_red, w1, w2, wt)
+        ws = torch.empty(L.query("egm_baseline_bwd_workspace", B, g, rd, rd2, O.BASELINE_PATCH) // 4, dtype=torch.float32, device=dev)
+        du = torch.empty((B, Ltot, rd), dtype=dt, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        dwt, dbt = torch.empty(wt.shape, **f32), torch.empty(1, **f32)
+        dw2, db2, dw1, db1 = torch.empty(w2.shape, **f32), torch.empty(rd, **f32), torch.empty(w1.shape, **f32), torch.empty(rd2, **f32)
+        dmul, dadd = torch.empty_like(mul), torch.empty_like(add)
+        L.call("egm_baseline_bwd", dtype_code(dt), ptr(gout), ptr(u), ptr(h), ptr(mul), ptr(add), ptr(pk), ptr(b2.detach().float().contiguous()),
+               ptr(du), 1, Ltot, ptr(dwt), ptr(dbt), ptr(dw2), ptr(db2), ptr(dw1), ptr(db1), ptr(dmul), ptr(dadd), ptr(ws), B, g, rd, rd2,
+               O.BASELINE_PATCH, stream())
+        du2 = du.reshape(-1, rd)
+        dw_red = _linear_wgrad(x.reshape(-1, K), du2) if ctx.needs_input_grad[3] else None
+        db_red = _colsum(du2)[:rd] if ctx.needs_input_grad[4] else None
+        return None, dmul, dadd, dw_red, db_red, dw1, db1, dw2, db2, dwt, dbt
+
+
+def baseline_head(x, mul, add, reduce, reduce2, trans_conv):
+    """BaselineHeadFn over the reference's modules: reduce (Linear), reduce2 (Sequential(Linear, ReLU, Linear)), trans_conv."""
+    return BaselineHeadFn.apply(x, mul, add, reduce.weight, reduce.bias, reduce2[0].weight, reduce2[0].bias, reduce2[2].weight,
+                                reduce2[2].bias, trans_conv.weight, trans_conv.bias)
+
+
 class BCEWithLogitsFn(Function):
     """nn.BCEWithLogitsLoss() (mean) on fp32 logits / targets of equal shape (experiments/phrasecut.yaml: loss)."""
 

@@ -32,16 +32,12 @@ def get_prompt_list(prompt):
     raise ValueError("Invalid value for prompt")
 
 
-class CLIPDensePredT(nn.Module):
-    def __init__(self, version="ViT-B/32", extract_layers=(3, 6, 9), cond_layer=0, reduce_dim=128, n_heads=4, prompt="fixed", extra_blocks=0,
-                 reduce_cond=None, fix_shift=False, learn_trans_conv_only=False, limit_to_clip_only=False, upsample=False,
-                 add_calibration=False, rev_activations=False, trans_conv=None, n_tokens=None, complex_trans_conv=False,
-                 clip_weights="weights/longclip-B.pt"):
+class CLIPDenseBase(nn.Module):
+    """What CLIPDensePredT and CLIPDenseBaseline share (models/clipseg.py:136-332): the frozen CLIP backbone, film_mul / film_add / reduce,
+    the conditionals and the encoder pass."""
+
+    def __init__(self, version, reduce_dim, prompt, clip_weights):
         super().__init__()
-        for flag, name in ((extra_blocks, "extra_blocks"), (reduce_cond, "reduce_cond"), (fix_shift, "fix_shift"), (upsample, "upsample"),
-                           (n_tokens, "n_tokens"), (trans_conv, "trans_conv")):
-            if flag:
-                raise NotImplementedError(f"egm_unet_amd: CLIPDensePredT({name}=...) is not used by the reference scripts and not implemented")
         cfg = _VIT[version]
         if os.path.isfile(clip_weights):                            # models/clipseg.py:147 (hard-coded relative path there)
             self.clip_model = build_model(torch.load(clip_weights, map_location="cpu"), load_from_clip=False)
@@ -57,33 +53,7 @@ class CLIPDensePredT(nn.Module):
         self.reduce = nn.Linear(768, reduce_dim)
         self.prompt_list = get_prompt_list(prompt)
         self.precomputed_prompts = dict()
-        self.extract_layers, self.cond_layer = extract_layers, cond_layer
-        self.limit_to_clip_only, self.process_cond, self.rev_activations = limit_to_clip_only, None, rev_activations
-        self.upsample_proj, self.add_activation1, self.version = None, True, version
-        self.token_shape = cfg["token_shape"]
-        self.shift_vector = None
-        ks = (cfg["patch"], cfg["patch"])
-        self.complex_trans_conv = bool(complex_trans_conv)
-        if not complex_trans_conv:
-            self.trans_conv = nn.ConvTranspose2d(reduce_dim, 1, ks, stride=ks)
-        else:                                                       # models/clipseg.py:403-414, the rd64-uni-refined checkpoint
-            if cfg["patch"] != 16 or reduce_dim not in (64, 128):
-                raise NotImplementedError(f"egm_unet_amd: complex_trans_conv needs ViT-B/16 and reduce_dim 64 or 128 (got {version}, {reduce_dim})")
-            tp = cfg["patch"] // 4
-            self.trans_conv = nn.Sequential(
-                nn.Conv2d(reduce_dim, reduce_dim, kernel_size=3, padding=1),
-                nn.ReLU(),
-                nn.ConvTranspose2d(reduce_dim, reduce_dim // 2, kernel_size=tp, stride=tp),
-                nn.ReLU(),
-                nn.ConvTranspose2d(reduce_dim // 2, 1, kernel_size=tp, stride=tp),
-            )
-        depth = len(extract_layers)
-        self.reduces = nn.ModuleList([nn.Linear(768, reduce_dim) for _ in range(depth)])
-        self.blocks = nn.ModuleList([nn.TransformerEncoderLayer(d_model=reduce_dim, nhead=n_heads) for _ in range(depth)])
-        self.extra_blocks = nn.ModuleList([])
-        self.n_heads = n_heads
         self.compute_dtype = torch.float32
-        self.decoder_dropout = None          # None: the encoder layers' own p (0.1, as in the reference's train mode); 0.0 disables it
 
     def set_compute_dtype(self, dtype):
         self.clip_model.set_compute_dtype(dtype)
@@ -123,9 +93,10 @@ class CLIPDensePredT(nn.Module):
         return q.float(), [a.float().permute(1, 0, 2) for a in acts], []
 
     @torch.no_grad()
-    def _visual_run(self, x_inp, extract_layers=(), mask=None):
+    def _visual_run(self, x_inp, extract_layers=(), mask=None, stop_after=None):
         """The encoder pass behind visual_forward in the compute dtype, batch-first: (q [B, 512], [activations [B, L, 768]]).  forward() takes
-        these as they are; the reference's fp32 [L, B, 768] copies (4 x 48 MB per call at B = 32) are only made where they are returned."""
+        these as they are; the reference's fp32 [L, B, 768] copies (4 x 48 MB per call at B = 32) are only made where they are returned.
+        stop_after: the last block to run (q is None then)."""
         require_gpu()
         dev = self.model.conv1.weight.device
         cls_mask = None
@@ -138,7 +109,65 @@ class CLIPDensePredT(nn.Module):
             iy = (torch.arange(g, device=dev) * seg.shape[1] // g).long()          # nearest source index = floor(dst * in / out)
             ix = (torch.arange(g, device=dev) * seg.shape[2] // g).long()
             cls_mask = (mask_layer, seg[:, iy][:, :, ix].reshape(seg.shape[0], g * g).contiguous())
-        return self.model.run(x_inp.to(dev), self.compute_dtype, extract_layers=tuple(extract_layers), cls_mask=cls_mask)
+        return self.model.run(x_inp.to(dev), self.compute_dtype, extract_layers=tuple(extract_layers), cls_mask=cls_mask, stop_after=stop_after)
+
+    def _cond_in_dtype(self, cond):
+        """The conditional vectors [B, 512] fp32 -> the compute dtype (the film linears' input)."""
+        condT = torch.empty(cond.shape, dtype=self.compute_dtype, device=cond.device)
+        lib().call("egm_cast_f32", dtype_code(self.compute_dtype), ptr(cond.float().contiguous()), ptr(condT), cond.numel(), stream())
+        return condT
+
+    def _trans_conv_eval(self, a):
+        """ConvTranspose2d(rd -> 1, P, stride P) on a [B, 1 + g*g, rd] (token 0 dropped) as a per-token GEMM + pixel shuffle -> fp32 NCHW."""
+        bs, Ltot, rd = a.shape
+        dt, dev = a.dtype, a.device
+        g = int(math.isqrt(Ltot - 1))
+        P = self.trans_conv.kernel_size[0]
+        y = torch.empty((bs * Ltot, P * P), dtype=dt, device=dev)      # per-token 64 -> 16x16 patch (ConvTranspose2d as a GEMM)
+        O.gemm(a.reshape(-1, rd), rd, O.cast_weight(self.trans_conv.weight.reshape(rd, P * P), dt), P * P, False, y, P * P, bs * Ltot, P * P, rd, dt)
+        out = torch.empty((bs, 1, g * P, g * P), dtype=torch.float32, device=dev)
+        lib().call("egm_pixel_shuffle", dtype_code(dt), ptr(y), P * P, 1, Ltot, ptr(self.trans_conv.bias.detach().float()), ptr(out), bs, g, P,
+                   stream())
+        return out
+
+
+class CLIPDensePredT(CLIPDenseBase):
+    def __init__(self, version="ViT-B/32", extract_layers=(3, 6, 9), cond_layer=0, reduce_dim=128, n_heads=4, prompt="fixed", extra_blocks=0,
+                 reduce_cond=None, fix_shift=False, learn_trans_conv_only=False, limit_to_clip_only=False, upsample=False,
+                 add_calibration=False, rev_activations=False, trans_conv=None, n_tokens=None, complex_trans_conv=False,
+                 clip_weights="weights/longclip-B.pt"):
+        for flag, name in ((extra_blocks, "extra_blocks"), (reduce_cond, "reduce_cond"), (fix_shift, "fix_shift"), (upsample, "upsample"),
+                           (n_tokens, "n_tokens"), (trans_conv, "trans_conv")):
+            if flag:
+                raise NotImplementedError(f"egm_unet_amd: CLIPDensePredT({name}=...) is not used by the reference scripts and not implemented")
+        super().__init__(version, reduce_dim, prompt, clip_weights)
+        cfg = _VIT[version]
+        self.extract_layers, self.cond_layer = extract_layers, cond_layer
+        self.limit_to_clip_only, self.process_cond, self.rev_activations = limit_to_clip_only, None, rev_activations
+        self.upsample_proj, self.add_activation1, self.version = None, True, version
+        self.token_shape = cfg["token_shape"]
+        self.shift_vector = None
+        ks = (cfg["patch"], cfg["patch"])
+        self.complex_trans_conv = bool(complex_trans_conv)
+        if not complex_trans_conv:
+            self.trans_conv = nn.ConvTranspose2d(reduce_dim, 1, ks, stride=ks)
+        else:                                                       # models/clipseg.py:403-414, the rd64-uni-refined checkpoint
+            if cfg["patch"] != 16 or reduce_dim not in (64, 128):
+                raise NotImplementedError(f"egm_unet_amd: complex_trans_conv needs ViT-B/16 and reduce_dim 64 or 128 (got {version}, {reduce_dim})")
+            tp = cfg["patch"] // 4
+            self.trans_conv = nn.Sequential(
+                nn.Conv2d(reduce_dim, reduce_dim, kernel_size=3, padding=1),
+                nn.ReLU(),
+                nn.ConvTranspose2d(reduce_dim, reduce_dim // 2, kernel_size=tp, stride=tp),
+                nn.ReLU(),
+                nn.ConvTranspose2d(reduce_dim // 2, 1, kernel_size=tp, stride=tp),
+            )
+        depth = len(extract_layers)
+        self.reduces = nn.ModuleList([nn.Linear(768, reduce_dim) for _ in range(depth)])
+        self.blocks = nn.ModuleList([nn.TransformerEncoderLayer(d_model=reduce_dim, nhead=n_heads) for _ in range(depth)])
+        self.extra_blocks = nn.ModuleList([])
+        self.n_heads = n_heads
+        self.decoder_dropout = None          # None: the encoder layers' own p (0.1, as in the reference's train mode); 0.0 disables it
 
     def _encoder_layer(self, blk, a):
         """nn.TransformerEncoderLayer defaults in eval mode: post-norm, ReLU feed-forward, no dropout."""
@@ -227,13 +256,7 @@ class CLIPDensePredT(nn.Module):
             if return_features:
                 return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts_all]
             return out,
-        Ltot, rd = a.shape[1], a.shape[2]
-        g = int(math.isqrt(Ltot - 1))
-        P = self.trans_conv.kernel_size[0]
-        y = torch.empty((bs * Ltot, P * P), dtype=dt, device=dev)      # per-token 64 -> 16x16 patch (ConvTranspose2d as a GEMM)
-        O.gemm(a.reshape(-1, rd), rd, O.cast_weight(self.trans_conv.weight.reshape(rd, P * P), dt), P * P, False, y, P * P, bs * Ltot, P * P, rd, dt)
-        out = torch.empty((bs, 1, g * P, g * P), dtype=torch.float32, device=dev)
-        L_.call("egm_pixel_shuffle", code, ptr(y), P * P, 1, Ltot, ptr(self.trans_conv.bias.detach().float()), ptr(out), bs, g, P, stream())
+        out = self._trans_conv_eval(a)
         if return_features:
             return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts_all]
         return out,
@@ -261,3 +284,79 @@ class CLIPDensePredTMasked(CLIPDensePredT):
             with torch.no_grad():
                 cond, _, _ = self.visual_forward_masked(cond_or_img_s, seg_s)
         return super().forward(img_q, cond, return_features=return_features)
+
+
+BASELINE_FUSED = os.environ.get("EGM_CLIPSEG_BL_FUSED", "1") != "0"     # False: the head runs on the composed operators (A/B, cross-check)
+
+
+class CLIPDenseBaseline(CLIPDenseBase):
+    """CLIPSeg's baseline (models/clipseg.py:529-590; experiments/phrasecut.yaml:81, coco.yaml:98-101, pascal_1shot.yaml:92-95): the layer
+    extract_layer activation -> reduce -> FiLM -> reduce2 (Linear, ReLU, Linear) -> ConvTranspose2d per token, no transformer decoder.
+    bf16 with patch 16 and reduce dims that are multiples of 16 up to 128: one fused HIP launch (csrc/clipseg_baseline.hip, training:
+    clip/train_ops.BaselineHeadFn); fp32, other shapes or BASELINE_FUSED = False: the composed operators.  Without return_features the
+    backbone stops after extract_layer (visual_q is not computed)."""
+
+    def __init__(self, version="ViT-B/32", cond_layer=0, extract_layer=9, reduce_dim=128, reduce2_dim=None, prompt="fixed", reduce_cond=None,
+                 limit_to_clip_only=False, n_tokens=None, clip_weights="weights/longclip-B.pt"):
+        for flag, name in ((reduce_cond, "reduce_cond"), (n_tokens, "n_tokens")):
+            if flag:
+                raise NotImplementedError(f"egm_unet_amd: CLIPDenseBaseline({name}=...) is not used by the reference scripts and not implemented")
+        super().__init__(version, reduce_dim, prompt, clip_weights)
+        self.extract_layer = extract_layer
+        self.limit_to_clip_only = limit_to_clip_only
+        self.shift_vector = None
+        self.token_shape = _VIT[version]["token_shape"]
+        assert reduce2_dim is not None                              # as the reference (models/clipseg.py:546)
+        self.reduce2 = nn.Sequential(nn.Linear(reduce_dim, reduce2_dim), nn.ReLU(), nn.Linear(reduce2_dim, reduce_dim))
+        ks = (_VIT[version]["patch"], _VIT[version]["patch"])
+        self.trans_conv = nn.ConvTranspose2d(reduce_dim, 1, ks, stride=ks)
+
+    def _fused(self):
+        return BASELINE_FUSED and O.baseline_supported(self.reduce.weight.shape[0], self.reduce2[0].weight.shape[0], self.trans_conv.kernel_size[0],
+                                                       self.compute_dtype)
+
+    def forward(self, inp_image, conditional=None, return_features=False):
+        """models/clipseg.py:556-590.  eval(): inference, no autograd.  train(): film_mul / film_add / reduce / reduce2 / trans_conv are
+        differentiable through the HIP operators of clip/train_ops.py; the CLIP backbone stays frozen."""
+        assert type(return_features) == bool
+        dev = self.model.positional_embedding.device
+        x_inp = inp_image.to(dev)
+        bs = x_inp.shape[0]
+        train = self.training and torch.is_grad_enabled()
+        with torch.no_grad():
+            cond = self.get_cond_vec(conditional, bs)
+            q_raw, acts = self._visual_run(x_inp, [self.extract_layer], stop_after=None if return_features else self.extract_layer)
+            condT = self._cond_in_dtype(cond)
+        act = acts[0]
+        if train:
+            out = self._head_train(act.detach(), condT)
+        else:
+            with torch.no_grad():
+                out = self._head_eval(act, condT)
+        if return_features:
+            return out, q_raw.float(), cond, [act.float().permute(1, 0, 2)]
+        return out,
+
+    def _head_eval(self, act, condT):
+        mul = O.linear(condT, self.film_mul.weight, self.film_mul.bias)
+        add = O.linear(condT, self.film_add.weight, self.film_add.bias)
+        if self._fused():
+            r2 = self.reduce2
+            return O.baseline_head(act, mul, add, self.reduce.weight, self.reduce.bias, r2[0].weight, r2[0].bias, r2[2].weight, r2[2].bias,
+                                   self.trans_conv.weight, self.trans_conv.bias)
+        a = O.linear(act, self.reduce.weight, self.reduce.bias)
+        lib().call("egm_film", dtype_code(a.dtype), ptr(a), ptr(mul), ptr(add), a.shape[0], a.shape[1], a.shape[2], stream())
+        a = O.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
+        a = O.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
+        return self._trans_conv_eval(a)
+
+    def _head_train(self, act, condT):
+        from .clip import train_ops as T
+        mul = T.linear(condT, self.film_mul.weight, self.film_mul.bias)
+        add = T.linear(condT, self.film_add.weight, self.film_add.bias)
+        if self._fused():
+            return T.baseline_head(act, mul, add, self.reduce, self.reduce2, self.trans_conv)
+        a = T.FilmFn.apply(T.linear(act, self.reduce.weight, self.reduce.bias), mul, add)
+        a = T.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
+        a = T.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
+        return T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)

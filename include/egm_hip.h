@@ -688,6 +688,30 @@ int egm_refine_bwd(int dtype, const float* dout, const void* a, int tok_off, int
                    const float* b1, void* da, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2,
                    void* workspace, int B, int g, int rd, int patch, egm_stream_t s);
 
+/* ---- CLIPSeg baseline head, CLIPDenseBaseline (models/clipseg.py:529-590) -------------------------------------------------------------
+ * Per token of the activation x [B][Ltot][768] (rows tok_off .. tok_off + g*g - 1; the class token is skipped):
+ *   u = x W_red^T + b_red;  f = mul[b] * u + add[b];  h = relu(f W1^T + b1);  a3 = h W2^T + b2;  out = ConvTranspose2d(rd -> 1, 16, 16)(a3)
+ * with W_red [rd][768], W1 [rd2][rd], W2 [rd][rd2], Wt [rd][1][16][16] (fp32 parameters), mul / add [B][rd] in `dtype`, out fp32
+ * [B][1][16g][16g].  Supported (egm_baseline_supported() == 1): patch 16, rd and rd2 multiples of 16 in 16 .. 128; dtype bf16 only.
+ * Anything else returns EGM_ERR_UNSUPPORTED.
+ * egm_baseline_pack: the four weights -> egm_baseline_packed_elems() bf16 elements (MFMA operand layouts; rerun after every optimizer step).
+ * egm_baseline_fwd: ONE launch.  u ([B][g*g][rd]) and h ([B][g*g][rd2]) in `dtype` receive the saved tensors of the backward, or are both NULL.
+ * egm_baseline_bwd: two launches from dout fp32 [B][1][16g][16g] and the forward's u, h (requires Ltot == tok_off + g*g): du (`dtype`,
+ *   [B][Ltot][rd], the gradient of u; class-token rows 0), dmul / dadd (`dtype`, [B][rd]) and the fp32 gradients of Wt, bt, W2, b2, W1, b1
+ *   (parameter shapes; overwritten).  Per-workgroup slabs in the workspace (egm_baseline_bwd_workspace() bytes) are summed in fixed
+ *   order: bitwise reproducible.  The gradient of W_red / b_red (du^T x) is left to the caller. */
+int egm_baseline_supported(int rd, int rd2, int patch);
+long long egm_baseline_packed_elems(int rd, int rd2, int patch);
+long long egm_baseline_bwd_workspace(int B, int g, int rd, int rd2, int patch);
+int egm_baseline_pack(int dtype, const float* w_red, const float* w1, const float* w2, const float* wt, void* packed, int rd, int rd2,
+                      int patch, egm_stream_t s);
+int egm_baseline_fwd(int dtype, const void* x, int tok_off, int Ltot, const void* mul, const void* add, const void* packed,
+                     const float* b_red, const float* b1, const float* b2, const float* bt, void* u, void* h, float* out, int B, int g,
+                     int rd, int rd2, int patch, egm_stream_t s);
+int egm_baseline_bwd(int dtype, const float* dout, const void* u, const void* h, const void* mul, const void* add, const void* packed,
+                     const float* b2, void* du, int tok_off, int Ltot, float* dwt, float* dbt, float* dw2, float* db2, float* dw1,
+                     float* db1, void* dmul, void* dadd, void* workspace, int B, int g, int rd, int rd2, int patch, egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
