@@ -202,3 +202,53 @@ def baseline_head(x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off=1, 
     lib().call("egm_baseline_fwd", dtype_code(x.dtype), ptr(x), tok_off, Ltot, ptr(mul), ptr(add), ptr(pk),
                ptr(f32[0]), ptr(f32[1]), ptr(f32[2]), ptr(f32[3]), ptr(u), ptr(h), ptr(out), B, g, rd, rd2, BASELINE_PATCH, stream())
     return out
+
+
+def baseline_head_multi(x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off=1, prompts_per_group=0):
+    """baseline_head for K prompts on each of B activations, ONE launch: x [B, Ltot, 768] bf16, mul / add [K, rd] bf16 -> fp32
+    [B, K, 16g, 16g] (out[b, k] = baseline_head(x[b:b+1], mul[k:k+1], add[k:k+1])[0, 0], bit for bit).  reduce runs once per token
+    tile and prompt group; prompts_per_group <= 0 lets the library choose the groups."""
+    B, Ltot, _ = x.shape
+    K = mul.shape[0]
+    g = int(math.isqrt(Ltot - tok_off))
+    if g * g != Ltot - tok_off:
+        raise RuntimeError(f"baseline_head_multi: {Ltot - tok_off} grid tokens do not form a square grid")
+    x = x.contiguous()
+    pk = baseline_packed(w_red, w1, w2, wt)
+    out = torch.empty((B, K, g * BASELINE_PATCH, g * BASELINE_PATCH), dtype=torch.float32, device=x.device)
+    f32 = [t.detach().float().contiguous() for t in (b_red, b1, b2, bt)]
+    mul, add = mul.contiguous(), add.contiguous()
+    lib().call("egm_baseline_fwd_multi", dtype_code(x.dtype), ptr(x), tok_off, Ltot, ptr(mul), ptr(add), ptr(pk), ptr(f32[0]), ptr(f32[1]),
+               ptr(f32[2]), ptr(f32[3]), ptr(out), B, K, g, w_red.shape[0], w1.shape[0], BASELINE_PATCH, int(prompts_per_group), stream())
+    return out
+
+
+def film_fanout(r, mul, add):
+    """FiLM at the decoder's cond_layer for K prompts: r [B, L, D], mul / add [K, D] (r's dtype) -> [B*K, L, D] with
+    out[b*K + k] = mul[k] * r[b] + add[k] (sequence order b-major)."""
+    B, L, D = r.shape
+    K = mul.shape[0]
+    r, mul, add = r.contiguous(), mul.contiguous(), add.contiguous()
+    out = torch.empty((B * K, L, D), dtype=r.dtype, device=r.device)
+    lib().call("egm_film_fanout", dtype_code(r.dtype), ptr(r), ptr(mul), ptr(add), ptr(out), B, K, L, D, stream())
+    return out
+
+
+def bcast_add_(a, r):
+    """a [B*K, L, D] += r [B, L, D] broadcast over the K prompts of each image (in place; returns a)."""
+    B, L, D = r.shape
+    K = a.shape[0] // B
+    if a.shape != (B * K, L, D) or not a.is_contiguous():
+        raise RuntimeError(f"bcast_add_: a {tuple(a.shape)} is not a contiguous [B*K, L, D] for r {tuple(r.shape)}")
+    r = r.contiguous()
+    lib().call("egm_bcast_add", dtype_code(a.dtype), ptr(a), ptr(r), B, K, L, D, stream())
+    return a
+
+
+def sigmoid_affine_(x, scale, offset):
+    """x fp32 [N, C, H, W] <- offset + scale[c] * sigmoid(x) in place (scale fp32 [C] on x's device); returns x."""
+    N, C, H, W = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous() or scale.shape != (C,):
+        raise RuntimeError("sigmoid_affine_: x must be contiguous fp32 [N, C, H, W] and scale [C]")
+    lib().call("egm_sigmoid_affine", ptr(x), ptr(scale.float().contiguous()), float(offset), N, C, H * W, stream())
+    return x

@@ -111,6 +111,49 @@ class CLIPDenseBase(nn.Module):
             cls_mask = (mask_layer, seg[:, iy][:, :, ix].reshape(seg.shape[0], g * g).contiguous())
         return self.model.run(x_inp.to(dev), self.compute_dtype, extract_layers=tuple(extract_layers), cls_mask=cls_mask, stop_after=stop_after)
 
+    # ---- several prompts on one backbone pass (the reference runs the image once per prompt: predict_CLIPseg.py:495, eval_CLIPseg.py:879,
+    # CLIPSegMultiLabel)
+    def forward_multi(self, inp_image, conditionals):
+        """inp_image [B, 3, H, W], conditionals: K prompts (a list / tuple of K strings, one string, a [K, 512] tensor, or a [K, 3, h, w]
+        image tensor that goes through visual_forward) -> fp32 logits [B, K, H', W'] with out[b, k] = self(inp_image[b:b+1], prompt k)[0][0, 0].
+        The backbone runs once per image (plus once per image conditional) and stops after the last layer the decoder reads; only the
+        decoder runs per (image, prompt).  Inference only."""
+        if self.training and torch.is_grad_enabled():
+            raise NotImplementedError("egm_unet_amd: forward_multi is inference only (call .eval() or run under torch.no_grad())")
+        with torch.no_grad():
+            dev = self.model.positional_embedding.device
+            x_inp = inp_image.to(dev)
+            if x_inp.ndim != 4:
+                raise ValueError(f"forward_multi: inp_image must be [B, 3, H, W], got {tuple(x_inp.shape)}")
+            cond = self._multi_cond(conditionals)
+            condT = self._cond_in_dtype(cond)
+            out = self._decode_multi(x_inp, condT)
+            B, K = x_inp.shape[0], cond.shape[0]
+            return out.view(B, K, out.shape[-2], out.shape[-1])
+
+    def _multi_cond(self, conditionals):
+        """The K conditional vectors [K, 512] fp32 of forward_multi (get_cond_vec's forms, K in place of the batch size)."""
+        width = self.film_mul.in_features
+        if isinstance(conditionals, str):
+            return self.compute_conditional(conditionals).reshape(1, -1)
+        if isinstance(conditionals, (list, tuple)):
+            if len(conditionals) == 0:
+                raise ValueError("forward_multi: no conditionals given")
+            if not all(isinstance(c, str) for c in conditionals):
+                raise ValueError("forward_multi: a list of conditionals must hold strings only")
+            return self.compute_conditional(list(conditionals))
+        if isinstance(conditionals, torch.Tensor):
+            if conditionals.shape[0] == 0:
+                raise ValueError("forward_multi: no conditionals given")
+            if conditionals.ndim == 2:
+                if conditionals.shape[1] != width:
+                    raise ValueError(f"forward_multi: conditional vectors must be [K, {width}], got {tuple(conditionals.shape)}")
+                return conditionals.to(self.model.positional_embedding.device).float()
+            if conditionals.ndim == 4:
+                return self.visual_forward(conditionals)[0]
+            raise ValueError(f"forward_multi: a conditional tensor must be [K, {width}] or [K, 3, h, w], got {tuple(conditionals.shape)}")
+        raise ValueError("forward_multi: invalid conditionals")
+
     def _cond_in_dtype(self, cond):
         """The conditional vectors [B, 512] fp32 -> the compute dtype (the film linears' input)."""
         condT = torch.empty(cond.shape, dtype=self.compute_dtype, device=cond.device)
@@ -261,6 +304,35 @@ class CLIPDensePredT(CLIPDenseBase):
             return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts_all]
         return out,
 
+    def _decode_multi(self, x_inp, condT):
+        """forward_multi's decoder: layers before cond_layer on the B sequences; at cond_layer reduce (+ the running a) on B*L rows, then
+        one fan-out kernel writes a[b*K + k] = mul[k] * r[b] + add[k]; behind it reduce_i(act_i) stays a GEMM over B*L rows whose result
+        is broadcast-added into the B*K sequences.  Encoder layers and heads then run on B*K sequences -> fp32 [B*K, 1, H', W']."""
+        B, K = x_inp.shape[0], condT.shape[0]
+        _, acts_all = self._visual_run(x_inp, extract_layers=[0] + list(self.extract_layers), stop_after=max(self.extract_layers))
+        acts = acts_all[1:]
+        acts = acts[::-1] if not self.rev_activations else acts
+        a, fanned = None, False
+        for i, (act, blk, red) in enumerate(zip(acts, self.blocks, self.reduces)):
+            if not fanned:
+                a = O.linear(act, red.weight, red.bias, residual=a)
+                if i == self.cond_layer:
+                    mul = O.linear(condT, self.film_mul.weight, self.film_mul.bias)
+                    add = O.linear(condT, self.film_add.weight, self.film_add.bias)
+                    a = O.film_fanout(a, mul, add)
+                    fanned = True
+            else:
+                O.bcast_add_(a, O.linear(act, red.weight, red.bias))
+            a = self._encoder_layer(blk, a)
+        if not fanned:                                               # cond_layer behind the last layer: no FiLM, every prompt alike
+            rd = a.shape[-1]
+            one = torch.ones((K, rd), dtype=a.dtype, device=a.device)
+            a = O.film_fanout(a, one, torch.zeros_like(one))
+        if self.complex_trans_conv:
+            tc = self.trans_conv
+            return O.refine_head(a, tc[0].weight, tc[0].bias, tc[2].weight, tc[2].bias, tc[4].weight, tc[4].bias)
+        return self._trans_conv_eval(a)
+
 
 class CLIPDensePredTMasked(CLIPDensePredT):
     """CLIPSeg conditioned on a support image + its segmentation (models/clipseg.py:500-525): the conditional vector is the CLIP
@@ -350,6 +422,22 @@ class CLIPDenseBaseline(CLIPDenseBase):
         a = O.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
         return self._trans_conv_eval(a)
 
+    def _decode_multi(self, x_inp, condT):
+        """forward_multi's head: the backbone once (stopping after extract_layer), then the fused multi-prompt launch (reduce once per
+        token tile) or, composed, reduce on B*L rows + the FiLM fan-out + reduce2 / trans_conv on B*K sequences."""
+        _, acts = self._visual_run(x_inp, [self.extract_layer], stop_after=self.extract_layer)
+        act = acts[0]
+        mul = O.linear(condT, self.film_mul.weight, self.film_mul.bias)
+        add = O.linear(condT, self.film_add.weight, self.film_add.bias)
+        if self._fused():
+            r2 = self.reduce2
+            return O.baseline_head_multi(act, mul, add, self.reduce.weight, self.reduce.bias, r2[0].weight, r2[0].bias, r2[2].weight,
+                                         r2[2].bias, self.trans_conv.weight, self.trans_conv.bias)
+        a = O.film_fanout(O.linear(act, self.reduce.weight, self.reduce.bias), mul, add)
+        a = O.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
+        a = O.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
+        return self._trans_conv_eval(a)
+
     def _head_train(self, act, condT):
         from .clip import train_ops as T
         mul = T.linear(condT, self.film_mul.weight, self.film_mul.bias)
@@ -360,3 +448,44 @@ class CLIPDenseBaseline(CLIPDenseBase):
         a = T.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
         a = T.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
         return T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
+
+
+# 'background' + datasets/pascal_classes.json in id order (the reference's third_party.JoEm VOC list, which its tree does not ship)
+PASCAL_CLASSES = ("background", "aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable", "dog",
+                  "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor")
+
+
+class CLIPSegMultiLabel(nn.Module):
+    """models/clipseg.py:592-625: the 21 PASCAL classes as bare-name prompts on one image batch -> [B, 21, 352, 352] with
+    out[:, c] = -10 + fac_c * sigmoid(logits_c), fac = 3 for background, 1 otherwise.  One forward_multi call (the backbone runs once
+    per image, not once per class), then one in-place sigmoid / scale / offset kernel.
+    model: a CLIPDenseBase instance, or the path of a decoder state dict loaded with strict=False into
+    CLIPDensePredT(version='ViT-B/16', reduce_dim=64) (what the reference's load_model does for its checkpoints, predict_CLIPseg.py:413-415)."""
+
+    SIZE = 352                                                      # the reference's output buffer (models/clipseg.py:611)
+
+    def __init__(self, model):
+        super().__init__()
+        self.pascal_classes = PASCAL_CLASSES
+        if isinstance(model, CLIPDenseBase):
+            self.clipseg = model
+        elif isinstance(model, (str, os.PathLike)):
+            self.clipseg = CLIPDensePredT(version="ViT-B/16", reduce_dim=64)
+            self.clipseg.load_state_dict(torch.load(model, map_location="cpu"), strict=False)
+        else:
+            raise TypeError(f"CLIPSegMultiLabel: model must be a CLIPDenseBase or a state-dict path, got {type(model).__name__}")
+        self.clipseg.eval()
+        self._fac = {}
+
+    def forward(self, x):
+        P = self.clipseg.model.patch_size
+        H, W = x.shape[-2] // P * P, x.shape[-1] // P * P
+        if (H, W) != (self.SIZE, self.SIZE):
+            raise ValueError(f"CLIPSegMultiLabel: the logits are {H} x {W}; the reference's output is fixed at {self.SIZE} x {self.SIZE} "
+                             f"(input {x.shape[-2]} x {x.shape[-1]})")
+        out = self.clipseg.forward_multi(x, list(self.pascal_classes))                   # [B, 21, 352, 352] fp32
+        fac = self._fac.get(out.device)
+        if fac is None:
+            fac = torch.tensor([3.0 if c == "background" else 1.0 for c in self.pascal_classes], device=out.device)
+            self._fac[out.device] = fac
+        return O.sigmoid_affine_(out, fac, -10.0)

@@ -204,6 +204,111 @@ __global__ __launch_bounds__(NT) void baseline_fwd_kernel(const bf16_t* __restri
     }
 }
 
+// ---- forward, K prompts on the same activation (CLIPDenseBase.forward_multi) ------------------------------------------------------
+// u = x W_red^T + b_red (the 768-deep product, the head's largest) is computed ONCE per token tile and kept in registers; the prompts
+// k0 .. k1 - 1 of this workgroup's group (blockIdx.y) then each run FiLM -> W1 -> ReLU -> W2 -> Wt from the LDS-resident weights and
+// store out[b*K + k].  Per prompt the instruction sequence and rounding points are those of baseline_fwd_kernel with mul[k] / add[k], so
+// every prompt's mask equals egm_baseline_fwd's bit for bit.  The prompt groups exist for small B: a grid of token tiles alone is ~8
+// workgroups at B = 1, so u is recomputed per group to fill the GPU.
+template <int NP>
+__global__ __launch_bounds__(NT) void baseline_fwd_multi_kernel(const bf16_t* __restrict__ x, int tok_off, int Ltot, const bf16_t* __restrict__ mul,
+                                                                const bf16_t* __restrict__ add, const bf16_t* __restrict__ pk,
+                                                                const float* __restrict__ b_red, const float* __restrict__ b1,
+                                                                const float* __restrict__ b2, const float* __restrict__ bt, float* __restrict__ out,
+                                                                int g, int rd, int rd2, long long nwt, long long ntpi, int K, int kpg) {
+    constexpr int MT = NP / 16, KS = NP / 32;
+    __shared__ __align__(16) bf16_t s_wr[64 * NP];
+    __shared__ __align__(16) bf16_t s_res[2 * NP * NP + PP * NP];
+    const int tid = threadIdx.x, lane = tid & 63, q = lane >> 4, col = lane & 15;
+    const long long wt = (long long)blockIdx.x * WT + (tid >> 6);
+    const bool has = wt < nwt;
+    const int b = has ? (int)(wt / ntpi) : 0;
+    const int t = has ? (int)(wt % ntpi) * TT + col : 0;
+    const bool tv = has && t < g * g;
+    bf16x8_t xf[24];
+    {
+        const bf16_t* xr = x + ((long long)b * Ltot + tok_off + (tv ? t : 0)) * DX + 16 * q;
+#pragma unroll
+        for (int c = 0; c < 12; ++c)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) xf[2 * c + s] = tv ? frag(xr + 64 * c + 8 * s) : zero8();
+    }
+    stage(s_res, pk + off_w1f(NP), (2 * NP * NP + PP * NP) / 8);
+    f32x4_t acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < 12; ++c) {
+        stage(s_wr, pk + off_wr(NP) + 64LL * NP * c, 64 * NP / 8);
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m] = mfma(frag(s_wr + ((m * 2 + s) * 64 + lane) * 8), xf[2 * c + s], acc[m]);
+        __syncthreads();
+    }
+    f32x4_t u[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int r0 = 16 * m + 4 * q;
+        for (int r = 0; r < 4; ++r) u[m][r] = r0 + r < rd ? rnd(acc[m][r] + b_red[r0 + r]) : 0.f;
+    }
+    const float bias = bt[0];
+    const int G16 = 16 * g, ty = t / g, tx = t % g;
+    const int k0 = blockIdx.y * kpg, k1 = k0 + kpg < K ? k0 + kpg : K;
+    for (int k = k0; k < k1; ++k) {
+        // compiler-only fence: keeps the LDS weight fragments from being hoisted out of the prompt loop (they would not fit in registers)
+        asm volatile("" ::: "memory");
+        const bf16_t* mk = mul + (long long)k * rd;
+        const bf16_t* ak = add + (long long)k * rd;
+        bf16x8_t fb[KS];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const int r0 = 16 * m + 4 * q;
+            for (int r = 0; r < 4; ++r) acc[m][r] = r0 + r < rd ? fmaf(to_f32(mk[r0 + r]), u[m][r], to_f32(ak[r0 + r])) : 0.f;
+        }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) fb[s] = pack2(acc[2 * s], acc[2 * s + 1]);
+        // h = relu(W1 f + b1)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const int r0 = 16 * m + 4 * q;
+            for (int r = 0; r < 4; ++r) acc[m][r] = r0 + r < rd2 ? b1[r0 + r] : 0.f;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) acc[m] = mfma(frag(s_res + ((m * KS + s) * 64 + lane) * 8), fb[s], acc[m]);
+            for (int r = 0; r < 4; ++r) acc[m][r] = rnd(fmaxf(acc[m][r], 0.f));
+        }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) fb[s] = pack2(acc[2 * s], acc[2 * s + 1]);
+        // a3 = W2 h + b2
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const int r0 = 16 * m + 4 * q;
+            for (int r = 0; r < 4; ++r) acc[m][r] = r0 + r < rd ? b2[r0 + r] : 0.f;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) acc[m] = mfma(frag(s_res + NP * NP + ((m * KS + s) * 64 + lane) * 8), fb[s], acc[m]);
+        }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) fb[s] = pack2(acc[2 * s], acc[2 * s + 1]);
+        // y = Wt^T a3 + bt -> out[b*K + k]
+        float* ok = out + ((long long)b * K + k) * G16 * G16;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            f32x4_t y[4];
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {
+                y[cc] = (f32x4_t){bias, bias, bias, bias};
+#pragma unroll
+                for (int s = 0; s < KS; ++s) y[cc] = mfma(frag(s_res + 2 * NP * NP + (((4 * a + cc) * KS + s) * 64 + lane) * 8), fb[s], y[cc]);
+            }
+            if (tv) {
+                float* o = ok + (16LL * ty + 4 * a + q) * G16 + 16 * tx;
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc) *reinterpret_cast<f32x4_t*>(o + 4 * cc) = y[cc];
+            }
+        }
+    }
+}
+
 // ---- backward 1: per-token data gradients + per-workgroup slabs ---------------------------------------------------------------
 template <int NP>
 __global__ __launch_bounds__(NT) void baseline_bwd_kernel(const float* __restrict__ dout, const bf16_t* __restrict__ u_in,
@@ -506,6 +611,30 @@ extern "C" int egm_baseline_fwd(int dtype, const void* x, int tok_off, int Ltot,
                                                Ltot, (const bf16_t*)mul, (const bf16_t*)add, (const bf16_t*)packed, b_red, b1, b2, bt,
                                                (bf16_t*)u, (bf16_t*)h, out, g, rd, rd2, tl.nwt, tl.ntpi));
     EGM_CHECK_LAUNCH("baseline_fwd");
+    return EGM_OK;
+}
+
+extern "C" int egm_baseline_fwd_multi(int dtype, const void* x, int tok_off, int Ltot, const void* mul, const void* add, const void* packed,
+                                      const float* b_red, const float* b1, const float* b2, const float* bt, float* out, int B, int K, int g,
+                                      int rd, int rd2, int patch, int prompts_per_group, egm_stream_t s) {
+    const int rc = check(dtype, rd, rd2, patch);
+    if (rc != EGM_OK) return rc;
+    EGM_REQUIRE(x && mul && add && packed && b_red && b1 && b2 && bt && out && B > 0 && K > 0 && g > 0 && tok_off >= 0 &&
+                Ltot >= tok_off + g * g, "baseline_fwd_multi: bad args");
+    const Tiles tl = tiles_for(B, g);
+    int kpg = prompts_per_group;
+    if (kpg <= 0) {                        // automatic: enough prompt groups that the grid covers the 256 CUs once
+        long long ng = 256 / tl.nwg;
+        ng = ng < 1 ? 1 : (ng > K ? K : ng);
+        kpg = egm_cdiv(K, ng);
+    }
+    if (kpg > K) kpg = K;
+    const int ngroups = egm_cdiv(K, kpg);
+    EGM_REQUIRE(ngroups < 65536, "baseline_fwd_multi: %d prompt groups", ngroups);
+    EGM_NP(np_for(rd, rd2), hipLaunchKernelGGL((baseline_fwd_multi_kernel<NP>), dim3(tl.nwg, ngroups), dim3(NT), 0, (hipStream_t)s,
+                                               (const bf16_t*)x, tok_off, Ltot, (const bf16_t*)mul, (const bf16_t*)add, (const bf16_t*)packed,
+                                               b_red, b1, b2, bt, out, g, rd, rd2, tl.nwt, tl.ntpi, K, kpg));
+    EGM_CHECK_LAUNCH("baseline_fwd_multi");
     return EGM_OK;
 }
 

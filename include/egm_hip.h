@@ -711,6 +711,25 @@ int egm_baseline_fwd(int dtype, const void* x, int tok_off, int Ltot, const void
 int egm_baseline_bwd(int dtype, const float* dout, const void* u, const void* h, const void* mul, const void* add, const void* packed,
                      const float* b2, void* du, int tok_off, int Ltot, float* dwt, float* dbt, float* dw2, float* db2, float* dw1,
                      float* db1, void* dmul, void* dadd, void* workspace, int B, int g, int rd, int rd2, int patch, egm_stream_t s);
+/* egm_baseline_fwd_multi: the same head for K prompts on each of B activations, ONE launch (CLIPDenseBase.forward_multi).  mul / add are
+ * [K][rd]; out is fp32 [B*K][1][16g][16g] with sequence b*K + k (= [B][K][16g][16g]).  Per token tile u = x W_red^T + b_red is computed
+ * once per prompt group and every prompt of the group runs FiLM .. Wt on it; each prompt's output equals egm_baseline_fwd's with that
+ * prompt's mul / add bit for bit.  prompts_per_group <= 0: chosen so that the grid covers the device (B = 1: one prompt per group).
+ * Same support and dtype rules as egm_baseline_fwd. */
+int egm_baseline_fwd_multi(int dtype, const void* x, int tok_off, int Ltot, const void* mul, const void* add, const void* packed,
+                           const float* b_red, const float* b1, const float* b2, const float* bt, float* out, int B, int K, int g, int rd,
+                           int rd2, int patch, int prompts_per_group, egm_stream_t s);
+
+/* ---- CLIPSeg multi-prompt decoder (CLIPDenseBase.forward_multi, CLIPSegMultiLabel; csrc/clipseg_multi.hip) ----------------------------
+ * B images, K prompts; decoder sequences are b-major (s = b*K + k), rows [L][D] per sequence, D a multiple of 4, 16-byte aligned buffers.
+ * egm_film_fanout: out[b*K + k][t][:] = mul[k][:] * r[b][t][:] + add[k][:]  (the FiLM at cond_layer, B -> B*K sequences; same rounding
+ *   as egm_film).  r [B][L][D], mul / add [K][D], out [B*K][L][D], all in `dtype`.
+ * egm_bcast_add: a[b*K + k][t][:] += r[b][t][:]  (reduce_i(act_i) of the layers behind cond_layer, a GEMM over B*L rows only).
+ * egm_sigmoid_affine: x[n][c][:] = offset + scale[c] * sigmoid(x[n][c][:]) in place; x fp32 [N][C][HW] (HW a multiple of 4), scale fp32 [C]
+ *   (CLIPSegMultiLabel: offset -10, scale 3 for background, else 1). */
+int egm_film_fanout(int dtype, const void* r, const void* mul, const void* add, void* out, int B, int K, int L, int D, egm_stream_t s);
+int egm_bcast_add(int dtype, void* a, const void* r, int B, int K, int L, int D, egm_stream_t s);
+int egm_sigmoid_affine(float* x, const float* scale, float offset, int N, int C, long long HW, egm_stream_t s);
 
 #ifdef __cplusplus
 }
