@@ -22,6 +22,13 @@ __device__ __forceinline__ float act_fwd(float v, int act) {
     if (act == EGM_ACT_SILU) return FAST ? v * logistic<FAST>(v) : v / (1.f + expf(-v));
     return v;
 }
+// The activation in a convolution's epilogue (egm_conv_fwd_act: BatchNorm folded into the weights and bias).  ACT is a template
+// argument of the kernels that call it: their ACT = NONE instantiations (the training path) compile exactly as without it.
+template <int ACT, bool FAST>
+__device__ __forceinline__ float conv_epi_act(float v) {
+    if constexpr (ACT == EGM_ACT_NONE) return v;
+    else return act_fwd<FAST>(v, ACT);
+}
 // derivative of act at pre-activation v
 template <bool FAST = false>
 __device__ __forceinline__ float act_grad(float v, int act) {

@@ -17,6 +17,7 @@
 //     image [pixel][half] is conflict-free for this fragment shape: every group holds eight pixel columns of one half and the other
 //     eight of the other half.
 #include "common.h"
+#include "bn_elem.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -32,7 +33,9 @@ struct C7Params {
     int ldx, ldy, N, H, W, bias_n, tiles_y, tiles_x;
 };
 
-__global__ __launch_bounds__(256, 2) void conv7x7_c16_kernel(C7Params p) {
+// The kernel body; ACT = the activation of the epilogue (egm_conv_fwd_act), NONE for egm_conv_fwd.
+template <int ACT>
+__device__ __forceinline__ void conv7x7_c16_body(const C7Params& p) {
     __shared__ __attribute__((aligned(16))) uint4 patch[C7_SLOTS];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int px = lane & 15, q = lane >> 4;
@@ -104,13 +107,19 @@ __global__ __launch_bounds__(256, 2) void conv7x7_c16_kernel(C7Params p) {
             const int oy = y0 + m;
             if (oy < p.H) {
                 uint2 o;
-                o.x = (uint32_t)f32_to_bf16(acc[m][0] + bs[0]) | ((uint32_t)f32_to_bf16(acc[m][1] + bs[1]) << 16);
-                o.y = (uint32_t)f32_to_bf16(acc[m][2] + bs[2]) | ((uint32_t)f32_to_bf16(acc[m][3] + bs[3]) << 16);
+                o.x = (uint32_t)f32_to_bf16(conv_epi_act<ACT, true>(acc[m][0] + bs[0])) |
+                      ((uint32_t)f32_to_bf16(conv_epi_act<ACT, true>(acc[m][1] + bs[1])) << 16);
+                o.y = (uint32_t)f32_to_bf16(conv_epi_act<ACT, true>(acc[m][2] + bs[2])) |
+                      ((uint32_t)f32_to_bf16(conv_epi_act<ACT, true>(acc[m][3] + bs[3])) << 16);
                 *reinterpret_cast<uint2*>(p.y + ((long long)(n * p.H + oy) * p.W + ox) * p.ldy + 4 * q) = o;
             }
         }
     }
 }
+__global__ __launch_bounds__(256, 2) void conv7x7_c16_kernel(C7Params p) { conv7x7_c16_body<EGM_ACT_NONE>(p); }
+// the same with an activation in the epilogue (egm_conv_fwd_act)
+template <int ACT>
+__global__ __launch_bounds__(256, 2) void conv7x7_c16_act_kernel(C7Params p) { conv7x7_c16_body<ACT>(p); }
 
 // ---- weight gradient of the same layer: dW[r*7+s][co][ci] = sum_{n,y,x} dy[n,y,x,co] * x[n, y+r-3, x+s-3, ci] ------------------------
 // On the generic wave-specialised kernel this shape pads both channel counts to 32 (a quarter of every MFMA is real work) and walks
@@ -354,7 +363,9 @@ struct CDParams {
     int ldx, ldy, N, H, W, dil, bias_n, tiles_y, tiles_x;
 };
 
-__global__ __launch_bounds__(256) void conv3x3d_c16_kernel(CDParams p) {
+// The kernel body; ACT = the activation of the epilogue (egm_conv_fwd_act), NONE for egm_conv_fwd.
+template <int ACT>
+__device__ __forceinline__ void conv3x3d_c16_body(const CDParams& p) {
     __shared__ __attribute__((aligned(16))) uint4 imgd[WD_XSLOTS_MAX];
     __shared__ float sred[4 * 2 * 16];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -418,8 +429,10 @@ __global__ __launch_bounds__(256) void conv3x3d_c16_kernel(CDParams p) {
             const int oy = y0 + yy, ox = x0 + 32 * wv + 16 * nb + px;
             if (oy < p.H && ox < p.W) {
                 uint2 o;
-                o.x = (uint32_t)f32_to_bf16(acc[yy][nb][0] + bs[0]) | ((uint32_t)f32_to_bf16(acc[yy][nb][1] + bs[1]) << 16);
-                o.y = (uint32_t)f32_to_bf16(acc[yy][nb][2] + bs[2]) | ((uint32_t)f32_to_bf16(acc[yy][nb][3] + bs[3]) << 16);
+                o.x = (uint32_t)f32_to_bf16(conv_epi_act<ACT, true>(acc[yy][nb][0] + bs[0])) |
+                      ((uint32_t)f32_to_bf16(conv_epi_act<ACT, true>(acc[yy][nb][1] + bs[1])) << 16);
+                o.y = (uint32_t)f32_to_bf16(conv_epi_act<ACT, true>(acc[yy][nb][2] + bs[2])) |
+                      ((uint32_t)f32_to_bf16(conv_epi_act<ACT, true>(acc[yy][nb][3] + bs[3])) << 16);
                 *reinterpret_cast<uint2*>(p.y + ((long long)(n * p.H + oy) * p.W + ox) * p.ldy + 4 * q) = o;
                 const float v0 = __uint_as_float(o.x << 16), v1 = __uint_as_float(o.x & 0xffff0000u);
                 const float v2 = __uint_as_float(o.y << 16), v3 = __uint_as_float(o.y & 0xffff0000u);
@@ -444,6 +457,10 @@ __global__ __launch_bounds__(256) void conv3x3d_c16_kernel(CDParams p) {
         }
     }
 }
+__global__ __launch_bounds__(256) void conv3x3d_c16_kernel(CDParams p) { conv3x3d_c16_body<EGM_ACT_NONE>(p); }
+// the same with an activation in the epilogue (egm_conv_fwd_act; no statistics)
+template <int ACT>
+__global__ __launch_bounds__(256) void conv3x3d_c16_act_kernel(CDParams p) { conv3x3d_c16_body<ACT>(p); }
 
 }  // namespace
 
@@ -463,12 +480,18 @@ int egm_conv_c7_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, 
 }
 
 int egm_conv_c7_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, int N, int H, int W,
-                       egm_stream_t s) {
+                       egm_stream_t s, int act) {
     C7Params p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)wf; p.bias = bias; p.y = (bf16_t*)y;
     p.ldx = ldx; p.ldy = ldy; p.N = N; p.H = H; p.W = W; p.bias_n = bias ? bias_n : 0;
     p.tiles_y = egm_cdiv(H, C7_R); p.tiles_x = egm_cdiv(W, C7_TW);
-    hipLaunchKernelGGL(conv7x7_c16_kernel, dim3(N * p.tiles_y * p.tiles_x), dim3(256), 0, (hipStream_t)s, p);
+    const dim3 grid(N * p.tiles_y * p.tiles_x);
+    switch (act) {
+        case EGM_ACT_RELU: hipLaunchKernelGGL(conv7x7_c16_act_kernel<EGM_ACT_RELU>, grid, dim3(256), 0, (hipStream_t)s, p); break;
+        case EGM_ACT_SIGMOID: hipLaunchKernelGGL(conv7x7_c16_act_kernel<EGM_ACT_SIGMOID>, grid, dim3(256), 0, (hipStream_t)s, p); break;
+        case EGM_ACT_SILU: hipLaunchKernelGGL(conv7x7_c16_act_kernel<EGM_ACT_SILU>, grid, dim3(256), 0, (hipStream_t)s, p); break;
+        default: hipLaunchKernelGGL(conv7x7_c16_kernel, grid, dim3(256), 0, (hipStream_t)s, p);
+    }
     EGM_CHECK_LAUNCH("conv7x7_c16");
     return EGM_OK;
 }
@@ -516,12 +539,19 @@ int egm_conv_c16d_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH
 }
 
 int egm_conv_c16d_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, float* stats, int N, int H,
-                         int W, int dil, egm_stream_t s) {
+                         int W, int dil, egm_stream_t s, int act) {
     CDParams p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)wf; p.bias = bias; p.y = (bf16_t*)y; p.stats = stats;
     p.ldx = ldx; p.ldy = ldy; p.N = N; p.H = H; p.W = W; p.dil = dil; p.bias_n = bias ? bias_n : 0;
     p.tiles_y = egm_cdiv(H, WD_RB); p.tiles_x = egm_cdiv(W, WD_TW);
-    hipLaunchKernelGGL(conv3x3d_c16_kernel, dim3(N * p.tiles_y * p.tiles_x), dim3(256), 0, (hipStream_t)s, p);
+    const dim3 grid(N * p.tiles_y * p.tiles_x);
+    EGM_REQUIRE(act == EGM_ACT_NONE || stats == nullptr, "conv3x3d_c16: no statistics with an activation");
+    switch (act) {
+        case EGM_ACT_RELU: hipLaunchKernelGGL(conv3x3d_c16_act_kernel<EGM_ACT_RELU>, grid, dim3(256), 0, (hipStream_t)s, p); break;
+        case EGM_ACT_SIGMOID: hipLaunchKernelGGL(conv3x3d_c16_act_kernel<EGM_ACT_SIGMOID>, grid, dim3(256), 0, (hipStream_t)s, p); break;
+        case EGM_ACT_SILU: hipLaunchKernelGGL(conv3x3d_c16_act_kernel<EGM_ACT_SILU>, grid, dim3(256), 0, (hipStream_t)s, p); break;
+        default: hipLaunchKernelGGL(conv3x3d_c16_kernel, grid, dim3(256), 0, (hipStream_t)s, p);
+    }
     EGM_CHECK_LAUNCH("conv3x3d_c16");
     return EGM_OK;
 }

@@ -14,6 +14,7 @@
 #include <type_traits>
 #include "common.h"
 #include "group.h"
+#include "bn_elem.h"
 #include <string.h>
 #include <stdlib.h>
 
@@ -31,7 +32,7 @@ struct DirectParams {
 __device__ __forceinline__ bf16x8_t as_frag(uint4 v) { return __builtin_bit_cast(bf16x8_t, v); }
 
 // K1: the 1x1 instantiation (no tap groups: its register count, and with it the occupancy the streaming layers live on, stays low)
-template <int NT, bool K1>
+template <int NT, bool K1, int ACT>
 __device__ __forceinline__ void conv_direct_body(const DirectParams& p, const int b) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int OROW = NT * 64 + 16, NV = NT * 4;
@@ -173,6 +174,10 @@ __device__ __forceinline__ void conv_direct_body(const DirectParams& p, const in
                         acc[nt][gq * 4 + j] += co < p.bias_n ? p.bias[co] : 0.f;
                     }
                 }
+                if constexpr (ACT != EGM_ACT_NONE) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[nt][gq * 4 + j] = conv_epi_act<ACT, true>(acc[nt][gq * 4 + j]);
+                }
                 uint2 pk;
                 pk.x = (uint32_t)f32_to_bf16(acc[nt][gq * 4 + 0]) | ((uint32_t)f32_to_bf16(acc[nt][gq * 4 + 1]) << 16);
                 pk.y = (uint32_t)f32_to_bf16(acc[nt][gq * 4 + 2]) | ((uint32_t)f32_to_bf16(acc[nt][gq * 4 + 3]) << 16);
@@ -230,7 +235,7 @@ __device__ __forceinline__ void conv_direct_body(const DirectParams& p, const in
 
 template <int NT, bool K1>
 __global__ __launch_bounds__(256) void conv_direct_kernel(DirectParams p) {
-    conv_direct_body<NT, K1>(p, blockIdx.x);
+    conv_direct_body<NT, K1, EGM_ACT_NONE>(p, blockIdx.x);
 }
 // merged launch of up to EGM_GROUP_MAX independent convolutions (group.h): member i owns blocks [blk0[i], blk0[i+1])
 struct DirectMulti { DirectParams p[EGM_GROUP_MAX]; int blk0[EGM_GROUP_MAX + 1]; int n; };
@@ -238,21 +243,40 @@ template <int NT, bool K1>
 __global__ __launch_bounds__(256) void conv_direct_multi_kernel(DirectMulti m) {
     int i = 0;
     while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
-    conv_direct_body<NT, K1>(m.p[i], (int)blockIdx.x - m.blk0[i]);
+    conv_direct_body<NT, K1, EGM_ACT_NONE>(m.p[i], (int)blockIdx.x - m.blk0[i]);
+}
+// the same with an activation in the epilogue (egm_conv_fwd_act)
+template <int NT, bool K1, int ACT>
+__global__ __launch_bounds__(256) void conv_direct_act_kernel(DirectParams p) {
+    conv_direct_body<NT, K1, ACT>(p, blockIdx.x);
+}
+template <int NT, bool K1, int ACT>
+__global__ __launch_bounds__(256) void conv_direct_act_multi_kernel(DirectMulti m) {
+    int i = 0;
+    while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
+    conv_direct_body<NT, K1, ACT>(m.p[i], (int)blockIdx.x - m.blk0[i]);
+}
+template <int NT, bool K1, int ACT> constexpr auto direct_kernel() {
+    if constexpr (ACT == EGM_ACT_NONE) return &conv_direct_kernel<NT, K1>;
+    else return &conv_direct_act_kernel<NT, K1, ACT>;
+}
+template <int NT, bool K1, int ACT> constexpr auto direct_multi_kernel() {
+    if constexpr (ACT == EGM_ACT_NONE) return &conv_direct_multi_kernel<NT, K1>;
+    else return &conv_direct_act_multi_kernel<NT, K1, ACT>;
 }
 
-template <int NT, bool K1>
+template <int NT, bool K1, int ACT>
 int launch_direct_group(const EgmGroupRec* recs, int n, hipStream_t st) {
     if (n == 1) {
         DirectParams first;
         memcpy(&first, recs[0].params, sizeof(DirectParams));
-        hipLaunchKernelGGL((conv_direct_kernel<NT, K1>), dim3(recs[0].grid), dim3(256), recs[0].smem, st, first);
+        hipLaunchKernelGGL((direct_kernel<NT, K1, ACT>()), dim3(recs[0].grid), dim3(256), recs[0].smem, st, first);
         EGM_CHECK_LAUNCH("conv_direct");
         return EGM_OK;
     }
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct_multi_kernel<NT, K1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(direct_multi_kernel<NT, K1, ACT>()), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            160 * 1024);
         if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_direct_multi: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done = true;
@@ -266,15 +290,15 @@ int launch_direct_group(const EgmGroupRec* recs, int n, hipStream_t st) {
         if (recs[i].smem > smem) smem = recs[i].smem;
     }
     for (int i = n; i < EGM_GROUP_MAX; ++i) { m.p[i] = m.p[0]; m.blk0[i + 1] = m.blk0[n]; }
-    hipLaunchKernelGGL((conv_direct_multi_kernel<NT, K1>), dim3(m.blk0[n]), dim3(256), smem, st, m);
+    hipLaunchKernelGGL((direct_multi_kernel<NT, K1, ACT>()), dim3(m.blk0[n]), dim3(256), smem, st, m);
     EGM_CHECK_LAUNCH("conv_direct_multi");
     return EGM_OK;
 }
-template <int NT, bool K1>
+template <int NT, bool K1, int ACT>
 int launch_direct_k(const DirectParams& p, size_t smem, hipStream_t st) {
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct_kernel<NT, K1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(direct_kernel<NT, K1, ACT>()), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            160 * 1024);
         if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_direct: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done = true;
@@ -284,19 +308,28 @@ int launch_direct_k(const DirectParams& p, size_t smem, hipStream_t st) {
     if (egm_group_recording()) {                                       // launched by egm_group_end(), merged with its siblings
         static_assert(sizeof(DirectParams) <= sizeof(EgmGroupRec::params), "group record too small");
         EgmGroupRec r;
-        r.launch = &launch_direct_group<NT, K1>;
+        r.launch = &launch_direct_group<NT, K1, ACT>;
         memcpy(r.params, &p, sizeof(DirectParams));
         r.G = p.G; r.grid = grid; r.smem = smem;
         egm_group_push(r);
         return EGM_OK;
     }
-    hipLaunchKernelGGL((conv_direct_kernel<NT, K1>), dim3(grid), dim3(256), smem, st, p);
+    hipLaunchKernelGGL((direct_kernel<NT, K1, ACT>()), dim3(grid), dim3(256), smem, st, p);
     EGM_CHECK_LAUNCH("conv_direct");
     return EGM_OK;
 }
-template <int NT>
+template <int NT, int ACT>
 int launch_direct(const DirectParams& p, size_t smem, hipStream_t st) {
-    return p.KH == 1 ? launch_direct_k<NT, true>(p, smem, st) : launch_direct_k<NT, false>(p, smem, st);
+    return p.KH == 1 ? launch_direct_k<NT, true, ACT>(p, smem, st) : launch_direct_k<NT, false, ACT>(p, smem, st);
+}
+template <int NT>
+int launch_direct_act(const DirectParams& p, size_t smem, hipStream_t st, int act) {
+    switch (act) {
+        case EGM_ACT_RELU: return launch_direct<NT, EGM_ACT_RELU>(p, smem, st);
+        case EGM_ACT_SIGMOID: return launch_direct<NT, EGM_ACT_SIGMOID>(p, smem, st);
+        case EGM_ACT_SILU: return launch_direct<NT, EGM_ACT_SILU>(p, smem, st);
+        default: return launch_direct<NT, EGM_ACT_NONE>(p, smem, st);
+    }
 }
 
 }  // namespace
@@ -337,11 +370,11 @@ int egm_conv_direct_plan(int dtype, int N, int H, int W, int Cin, int Cout, int 
 
 int egm_conv_direct_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy,
                            float* stats, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int NT, int nct, int G, size_t smem,
-                           egm_stream_t s) {
+                           egm_stream_t s, int act) {
     DirectParams p;
     p.x = x; p.w = wf; p.bias = bias; p.y = y; p.stats = stats;
     p.ldx = ldx; p.ldy = ldy; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.dil = (KH == 1) ? 1 : dil;
     p.bias_n = bias ? bias_n : 0;
     p.nblk = (int)(((long long)N * H * W + 31) / 32); p.nct = nct; p.G = G; p.wrow = ((Cin + 15) / 16) * 32 + 16;
-    return NT == 2 ? launch_direct<2>(p, smem, (hipStream_t)s) : launch_direct<1>(p, smem, (hipStream_t)s);
+    return NT == 2 ? launch_direct_act<2>(p, smem, (hipStream_t)s, act) : launch_direct_act<1>(p, smem, (hipStream_t)s, act);
 }

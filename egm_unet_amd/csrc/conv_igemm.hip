@@ -24,6 +24,7 @@
 // f32 : v_mfma_f32_32x32x2_f32   (exact fp32 FMA chain; the parity path)
 #include "common.h"
 #include "group.h"
+#include "bn_elem.h"
 #include <string.h>
 #include <stdio.h>
 
@@ -36,7 +37,7 @@ int egm_conv_direct_plan(int dtype, int N, int H, int W, int Cin, int Cout, int 
                          size_t* smem_out);
 int egm_conv_direct_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy,
                            float* stats, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int NT, int nct, int G, size_t smem,
-                           egm_stream_t s);
+                           egm_stream_t s, int act = EGM_ACT_NONE);
 
 // conv3x3_tile.hip: 8-wave LDS-DMA 3x3 kernel (the throughput path of the 3x3 stacks)
 int egm_conv_tile_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int* cfg_out, int* nct_out, int* G_out);
@@ -45,16 +46,17 @@ const char* egm_conv_tile_name(int cfg);
 int egm_conv_wreg_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int* G_out);
 const char* egm_conv_wreg_name(int Cin);
 int egm_conv_wreg_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, float* stats, int N, int H,
-                         int W, int Cin, int Cout, int G, egm_stream_t s);
+                         int W, int Cin, int Cout, int G, egm_stream_t s, int act = EGM_ACT_NONE);
 int egm_conv_tile_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, float* stats, int N, int H,
-                         int W, int Cin, int Cout, int cfg, int nct, int G, egm_stream_t s, void* y2 = nullptr, int ldy2 = 0, int csplit = 0);
+                         int W, int Cin, int Cout, int cfg, int nct, int G, egm_stream_t s, void* y2 = nullptr, int ldy2 = 0, int csplit = 0,
+                         int act = EGM_ACT_NONE);
 // conv7x7_c16.hip: weights-in-registers 7x7 kernel for 16 -> 16 channels (FusionConv's merged multi-scale conv at the 64-channel level)
 int egm_conv_c7_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil);
 int egm_conv_c7_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, int N, int H, int W,
-                       egm_stream_t s);
+                       egm_stream_t s, int act = EGM_ACT_NONE);
 int egm_conv_c16d_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil);
 int egm_conv_c16d_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, float* stats, int N, int H,
-                         int W, int dil, egm_stream_t s);
+                         int W, int dil, egm_stream_t s, int act = EGM_ACT_NONE);
 
 namespace {
 
@@ -111,147 +113,13 @@ struct ConvParams {
 
 template <typename T, int NT>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using M = Mma<T>;
-    constexpr int VEC = 16 / sizeof(T);               // elements per 16-byte vector
-    constexpr int NVPP = KC / VEC;                    // vectors per LDS row
-    constexpr int PS = M::kPixStride;
-
-    // ---- block -> (pixel tile, cout tile), XCD-aware
-    const int b = blockIdx.x, q = b >> 3;
-    const int ct = q % p.nct;
-    const int pt = (q / p.nct) * 8 + (b & 7);
-    if (pt >= p.npt) return;
-    const int tpi = p.tiles_y * p.tiles_x;
-    const int n = pt / tpi, trem = pt - n * tpi;
-    const int oy0 = (trem / p.tiles_x) * TH, ox0 = (trem % p.tiles_x) * TW;
-    const int co0 = ct * NT * 32;
-
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r31 = lane & 31, h = lane >> 5;
-    const T* __restrict__ xg = reinterpret_cast<const T*>(p.x);
-    const T* __restrict__ wg = reinterpret_cast<const T*>(p.w);
-
-    const bool halo = (p.dil == 1);
-    const int ngroups = halo ? 1 : p.KH * p.KW;
-    const int wh = halo ? p.KH : 1, ww = halo ? p.KW : 1;
-    const int PH = TH + wh - 1, PW = TW + ww - 1;
-    unsigned char* patch = smem;
-    unsigned char* wts = smem + p.patch_bytes;
-    const int rows_per_stage = halo ? p.wrows_per_stage : 1;
-
-    f32x16_t acc[2][NT];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][t][i] = 0.f;
-
-    for (int g = 0; g < ngroups; ++g) {
-        int offy, offx, tapbase;
-        if (halo) { offy = -(p.KH / 2); offx = -(p.KW / 2); tapbase = 0; }
-        else {
-            offy = (g / p.KW - p.KH / 2) * p.dil; offx = (g % p.KW - p.KW / 2) * p.dil; tapbase = g;
-            // shifted tile entirely outside the image -> contributes only zeros (block-uniform test)
-            if (oy0 + offy >= p.H || oy0 + offy + TH <= 0 || ox0 + offx >= p.W || ox0 + offx + TW <= 0) continue;
-        }
-        for (int c0 = 0; c0 < p.Cin; c0 += KC) {
-            const int kc = min(KC, p.Cin - c0);
-            const int nks = (kc + M::kStep - 1) / M::kStep;
-            __syncthreads();                                   // everyone done reading the previous patch/weights
-            // ---- stage the input patch (zero-filled outside the image / beyond Cin)
-            for (int i = tid; i < PH * PW * NVPP; i += 256) {
-                const int pix = i / NVPP, v = i - pix * NVPP;
-                const int py = pix / PW, px = pix - py * PW;
-                const int iy = oy0 + offy + py, ix = ox0 + offx + px, c = c0 + v * VEC;
-                const bool ok = (iy >= 0) && (iy < p.H) && (ix >= 0) && (ix < p.W) && (c < p.Cin);
-                const long long pixoff = (long long)(n * p.H + iy) * p.W + ix;
-                const T* src = xg + pixoff * p.ldx + c;
-                M::stage16(patch + pix * PS + v * 16, src, ok);
-            }
-            for (int wr0 = 0; wr0 < wh; wr0 += rows_per_stage) {
-                const int nrows = min(rows_per_stage, wh - wr0);
-                const int ntaps = nrows * ww;
-                if (wr0 > 0) __syncthreads();                  // previous weight stage consumed
-                // ---- stage weights of taps [wr0*ww, wr0*ww+ntaps) x NT*32 couts x KC
-                for (int i = tid; i < ntaps * NT * 32 * NVPP; i += 256) {
-                    const int row = i / NVPP, v = i - row * NVPP;
-                    const int t = row / (NT * 32), j = row - t * (NT * 32);
-                    const int co = co0 + j, c = c0 + v * VEC;
-                    const int tap = tapbase + wr0 * ww + t;
-                    const bool ok = (co < p.Cout) && (c < p.Cin);
-                    const T* src = wg + egm_w_off(p.wl, tap, co, c, p.Cout, p.Cin);
-                    M::stage16(wts + row * PS + v * 16, src, ok);
-                }
-                __syncthreads();
-                // ---- MFMA over the staged taps
-                for (int t = 0; t < ntaps; ++t) {
-                    const int wr = wr0 + t / ww, ws = t - (t / ww) * ww;
-                    const unsigned char* a0 = patch + ((2 * wv + 0 + wr) * PW + r31 + ws) * PS;
-                    const unsigned char* a1 = patch + ((2 * wv + 1 + wr) * PW + r31 + ws) * PS;
-                    const unsigned char* b0 = wts + (t * NT * 32 + r31) * PS;
-                    for (int ks = 0; ks < nks; ++ks) {
-                        const typename M::Frag fa0 = M::load(a0, ks, h), fa1 = M::load(a1, ks, h);
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            const typename M::Frag fb = M::load(b0 + nt * 32 * PS, ks, h);
-                            acc[0][nt] = M::mma(fa0, fb, acc[0][nt]);
-                            acc[1][nt] = M::mma(fa1, fb, acc[1][nt]);
-                        }
-                    }
-                }
-            }
-        }
-    }
-
-    // ---- epilogue: C/D layout of 32x32 MFMA: col (cout) = lane&31, row (pixel) = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-    T* __restrict__ yg = reinterpret_cast<T*>(p.y);
-    float ssum[NT], ssq[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) { ssum[nt] = 0.f; ssq[nt] = 0.f; }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int co = co0 + nt * 32 + r31;
-        const bool cok = co < p.Cout;
-        const float bv = (p.bias != nullptr && co < p.bias_n) ? p.bias[co] : 0.f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int oy = oy0 + 2 * wv + m;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int ox = ox0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (cok && oy < p.H && ox < p.W) {
-                    const T o = from_f32<T>(acc[m][nt][i] + bv);
-                    yg[((long long)(n * p.H + oy) * p.W + ox) * p.ldy + co] = o;
-                    const float f = to_f32(o);
-                    ssum[nt] += f; ssq[nt] += f * f;
-                }
-            }
-        }
-    }
-    if (p.stats != nullptr) {
-        __syncthreads();                                       // LDS is free again
-        float* red = reinterpret_cast<float*>(smem);           // [4 waves][2][NT*32]
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const float s = ssum[nt] + __shfl_xor(ssum[nt], 32, 64);
-            const float qq = ssq[nt] + __shfl_xor(ssq[nt], 32, 64);
-            if (h == 0) {
-                red[(wv * 2 + 0) * NT * 32 + nt * 32 + r31] = s;
-                red[(wv * 2 + 1) * NT * 32 + nt * 32 + r31] = qq;
-            }
-        }
-        __syncthreads();
-        if (tid < 2 * NT * 32) {
-            const int which = tid / (NT * 32), j = tid - which * NT * 32;
-            const int co = co0 + j;
-            if (co < p.Cout) {
-                float v = 0.f;
-                for (int w4 = 0; w4 < 4; ++w4) v += red[(w4 * 2 + which) * NT * 32 + j];
-                p.stats[((long long)pt * 2 + which) * p.Cout + co] = v;
-            }
-        }
-    }
+    constexpr int ACT = EGM_ACT_NONE;
+#include "conv_igemm_body.h"
+}
+// the same with an activation in the epilogue (egm_conv_fwd_act)
+template <typename T, int NT, int ACT>
+__global__ __launch_bounds__(256) void conv_igemm_act_kernel(ConvParams p) {
+#include "conv_igemm_body.h"
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -281,7 +149,7 @@ template <int WH, int WW, int R> struct PipeGeom {
 
 // The kernel body; `b` = the workgroup's index within THIS convolution (blockIdx.x, or blockIdx.x minus the member's first block in a
 // merged launch, group.h).
-template <int NT, int WH, int WW, int R>
+template <int NT, int WH, int WW, int R, int ACT>
 __device__ __forceinline__ void conv_igemm_pipe_body(const ConvParams& p, const int G, const int b) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using Gm = PipeGeom<WH, WW, R>;
@@ -534,6 +402,10 @@ __device__ __forceinline__ void conv_igemm_pipe_body(const ConvParams& p, const 
                                 acc[m][nt][gq * 4 + j] += co < p.bias_n ? p.bias[co] : 0.f;
                             }
                         }
+                        if constexpr (ACT != EGM_ACT_NONE) {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) acc[m][nt][gq * 4 + j] = conv_epi_act<ACT, true>(acc[m][nt][gq * 4 + j]);
+                        }
                         uint2 pk;
                         pk.x = (uint32_t)f32_to_bf16(acc[m][nt][gq * 4 + 0]) | ((uint32_t)f32_to_bf16(acc[m][nt][gq * 4 + 1]) << 16);
                         pk.y = (uint32_t)f32_to_bf16(acc[m][nt][gq * 4 + 2]) | ((uint32_t)f32_to_bf16(acc[m][nt][gq * 4 + 3]) << 16);
@@ -605,7 +477,7 @@ __device__ __forceinline__ void conv_igemm_pipe_body(const ConvParams& p, const 
 
 template <int NT, int WH, int WW, int R>
 __global__ __launch_bounds__(256, (R * NT >= 8) ? 1 : 2) void conv_igemm_pipe_kernel(ConvParams p, int G) {
-    conv_igemm_pipe_body<NT, WH, WW, R>(p, G, blockIdx.x);
+    conv_igemm_pipe_body<NT, WH, WW, R, EGM_ACT_NONE>(p, G, blockIdx.x);
 }
 // merged launch of up to EGM_GROUP_MAX independent convolutions of one instantiation (group.h): member i owns blocks [blk0[i], blk0[i+1])
 struct PipeMulti { ConvParams p[EGM_GROUP_MAX]; int G[EGM_GROUP_MAX]; int blk0[EGM_GROUP_MAX + 1]; int n; };
@@ -613,7 +485,27 @@ template <int NT, int WH, int WW, int R>
 __global__ __launch_bounds__(256, (R * NT >= 8) ? 1 : 2) void conv_igemm_pipe_multi_kernel(PipeMulti m) {
     int i = 0;
     while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
-    conv_igemm_pipe_body<NT, WH, WW, R>(m.p[i], m.G[i], (int)blockIdx.x - m.blk0[i]);
+    conv_igemm_pipe_body<NT, WH, WW, R, EGM_ACT_NONE>(m.p[i], m.G[i], (int)blockIdx.x - m.blk0[i]);
+}
+// the same with an activation in the epilogue (egm_conv_fwd_act)
+template <int NT, int WH, int WW, int R, int ACT>
+__global__ __launch_bounds__(256, (R * NT >= 8) ? 1 : 2) void conv_igemm_pipe_act_kernel(ConvParams p, int G) {
+    conv_igemm_pipe_body<NT, WH, WW, R, ACT>(p, G, blockIdx.x);
+}
+template <int NT, int WH, int WW, int R, int ACT>
+__global__ __launch_bounds__(256, (R * NT >= 8) ? 1 : 2) void conv_igemm_pipe_act_multi_kernel(PipeMulti m) {
+    int i = 0;
+    while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
+    conv_igemm_pipe_body<NT, WH, WW, R, ACT>(m.p[i], m.G[i], (int)blockIdx.x - m.blk0[i]);
+}
+// kernel of an instantiation: the training kernels for ACT = NONE, the *_act_* ones otherwise
+template <int NT, int WH, int WW, int R, int ACT> constexpr auto pipe_kernel() {
+    if constexpr (ACT == EGM_ACT_NONE) return &conv_igemm_pipe_kernel<NT, WH, WW, R>;
+    else return &conv_igemm_pipe_act_kernel<NT, WH, WW, R, ACT>;
+}
+template <int NT, int WH, int WW, int R, int ACT> constexpr auto pipe_multi_kernel() {
+    if constexpr (ACT == EGM_ACT_NONE) return &conv_igemm_pipe_multi_kernel<NT, WH, WW, R>;
+    else return &conv_igemm_pipe_act_multi_kernel<NT, WH, WW, R, ACT>;
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -669,17 +561,18 @@ __global__ __launch_bounds__(256) void conv_pack_multi_kernel(const PackEntry* _
     }
 }
 
-template <typename T, int NT>
+template <typename T, int NT, int ACT = EGM_ACT_NONE>
 int launch_conv(const ConvParams& p, size_t smem, hipStream_t st) {
+    constexpr auto kern = [] { if constexpr (ACT == EGM_ACT_NONE) return &conv_igemm_kernel<T, NT>; else return &conv_igemm_act_kernel<T, NT, ACT>; }();
     static bool attr_done = false;      // >64 KiB dynamic LDS needs an opt-in; done once per instantiation
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<T, NT>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_igemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done = true;
     }
     const int grid = ((p.npt + 7) / 8) * 8 * p.nct;
-    hipLaunchKernelGGL((conv_igemm_kernel<T, NT>), dim3(grid), dim3(256), smem, st, p);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, p);
     EGM_CHECK_LAUNCH("conv_igemm");
     return EGM_OK;
 }
@@ -707,18 +600,18 @@ template <int WH, int WW, int R> size_t pipe_base_bytes(int NT) {
     return (size_t)((Gm::PH * Gm::PW * 80 + 15) / 16 * 16) + (size_t)Gm::NTAPS * NT * 32 * 80 + 64 * 16;
 }
 
-template <int NT, int WH, int WW, int R>
+template <int NT, int WH, int WW, int R, int ACT = EGM_ACT_NONE>
 int launch_pipe_group(const EgmGroupRec* recs, int n, hipStream_t st) {
     ConvParams first;
     memcpy(&first, recs[0].params, sizeof(ConvParams));
     if (n == 1) {
-        hipLaunchKernelGGL((conv_igemm_pipe_kernel<NT, WH, WW, R>), dim3(recs[0].grid), dim3(256), recs[0].smem, st, first, recs[0].G);
+        hipLaunchKernelGGL((pipe_kernel<NT, WH, WW, R, ACT>()), dim3(recs[0].grid), dim3(256), recs[0].smem, st, first, recs[0].G);
         EGM_CHECK_LAUNCH("conv_igemm_pipe");
         return EGM_OK;
     }
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_pipe_multi_kernel<NT, WH, WW, R>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pipe_multi_kernel<NT, WH, WW, R, ACT>()),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_igemm_pipe_multi: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done = true;
@@ -733,16 +626,16 @@ int launch_pipe_group(const EgmGroupRec* recs, int n, hipStream_t st) {
         if (recs[i].smem > smem) smem = recs[i].smem;
     }
     for (int i = n; i < EGM_GROUP_MAX; ++i) { m.p[i] = m.p[0]; m.G[i] = 0; m.blk0[i + 1] = m.blk0[n]; }
-    hipLaunchKernelGGL((conv_igemm_pipe_multi_kernel<NT, WH, WW, R>), dim3(m.blk0[n]), dim3(256), smem, st, m);
+    hipLaunchKernelGGL((pipe_multi_kernel<NT, WH, WW, R, ACT>()), dim3(m.blk0[n]), dim3(256), smem, st, m);
     EGM_CHECK_LAUNCH("conv_igemm_pipe_multi");
     return EGM_OK;
 }
-template <int NT, int WH, int WW, int R>
+template <int NT, int WH, int WW, int R, int ACT = EGM_ACT_NONE>
 int launch_pipe(ConvParams& p, int G, hipStream_t st) {
     using Gm = PipeGeom<WH, WW, R>;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_pipe_kernel<NT, WH, WW, R>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pipe_kernel<NT, WH, WW, R, ACT>()),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_igemm_pipe: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done = true;
@@ -756,15 +649,34 @@ int launch_pipe(ConvParams& p, int G, hipStream_t st) {
     if (egm_group_recording()) {                                       // launched by egm_group_end(), merged with its siblings
         static_assert(sizeof(ConvParams) <= sizeof(EgmGroupRec::params), "group record too small");
         EgmGroupRec r;
-        r.launch = &launch_pipe_group<NT, WH, WW, R>;
+        r.launch = &launch_pipe_group<NT, WH, WW, R, ACT>;
         memcpy(r.params, &p, sizeof(ConvParams));
         r.G = G; r.grid = grid; r.smem = smem;
         egm_group_push(r);
         return EGM_OK;
     }
-    hipLaunchKernelGGL((conv_igemm_pipe_kernel<NT, WH, WW, R>), dim3(grid), dim3(256), smem, st, p, G);
+    hipLaunchKernelGGL((pipe_kernel<NT, WH, WW, R, ACT>()), dim3(grid), dim3(256), smem, st, p, G);
     EGM_CHECK_LAUNCH("conv_igemm_pipe");
     return EGM_OK;
+}
+// runtime activation -> instantiation (egm_conv_fwd_act)
+template <int NT, int WH, int WW, int R>
+int launch_pipe_act(ConvParams& p, int G, hipStream_t st, int act) {
+    switch (act) {
+        case EGM_ACT_RELU: return launch_pipe<NT, WH, WW, R, EGM_ACT_RELU>(p, G, st);
+        case EGM_ACT_SIGMOID: return launch_pipe<NT, WH, WW, R, EGM_ACT_SIGMOID>(p, G, st);
+        case EGM_ACT_SILU: return launch_pipe<NT, WH, WW, R, EGM_ACT_SILU>(p, G, st);
+        default: return launch_pipe<NT, WH, WW, R>(p, G, st);
+    }
+}
+template <typename T, int NT>
+int launch_conv_act(const ConvParams& p, size_t smem, hipStream_t st, int act) {
+    switch (act) {
+        case EGM_ACT_RELU: return launch_conv<T, NT, EGM_ACT_RELU>(p, smem, st);
+        case EGM_ACT_SIGMOID: return launch_conv<T, NT, EGM_ACT_SIGMOID>(p, smem, st);
+        case EGM_ACT_SILU: return launch_conv<T, NT, EGM_ACT_SILU>(p, smem, st);
+        default: return launch_conv<T, NT>(p, smem, st);
+    }
 }
 
 // One place decides kernel, tile shape and grouping, so the stats-tile count the caller allocates always matches the launch.
@@ -878,8 +790,9 @@ extern "C" int egm_conv_fwd_split(int dtype, const void* x, int ldx, const void*
     return egm_conv_tile_launch(x, ldx, wf, nullptr, 0, y, ldy, nullptr, N, H, W, Cin, Cout, c.tile_cfg, c.nct, c.G, s, y2, ldy2, csplit);
 }
 
-extern "C" int egm_conv_fwd(int dtype, const void* x, int ldx, const void* wf, const void* bias, int bias_n, void* y, int ldy, float* stats,
-                            int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, egm_stream_t s) {
+// egm_conv_fwd (act = NONE) and egm_conv_fwd_act (stats == NULL): one plan, the activation picks the instantiation of the planned kernel
+static int conv_fwd_impl(int dtype, const void* x, int ldx, const void* wf, const void* bias, int bias_n, void* y, int ldy, float* stats,
+                         int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int act, egm_stream_t s) {
     EGM_REQUIRE(x && wf && y, "conv_fwd: null pointer");
     EGM_REQUIRE(!bias || (bias_n > 0 && bias_n <= Cout), "conv_fwd: bad bias_n %d", bias_n);
     EGM_REQUIRE(N > 0 && H > 0 && W > 0, "conv_fwd: bad shape N=%d H=%d W=%d", N, H, W);
@@ -895,24 +808,26 @@ extern "C" int egm_conv_fwd(int dtype, const void* x, int ldx, const void* wf, c
     p.ldx = ldx; p.ldy = ldy; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.dil = dil; p.bias_n = bias ? bias_n : 0;
     p.wl = egm_w_layout(dtype, KH, KW, Cin, Cout);
     const ConvPlan c = conv_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil);
-    if (c.c16d) return egm_conv_c16d_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, dil, s);
-    if (c.c7 && stats == nullptr) return egm_conv_c7_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, N, H, W, s);
-    if (c.wreg) return egm_conv_wreg_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, c.G, s);
-    if (c.tile) return egm_conv_tile_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, c.tile_cfg, c.nct, c.G, s);
+    if (c.c16d) return egm_conv_c16d_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, dil, s, act);
+    if (c.c7 && stats == nullptr) return egm_conv_c7_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, N, H, W, s, act);
+    if (c.wreg) return egm_conv_wreg_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, c.G, s, act);
+    if (c.tile)
+        return egm_conv_tile_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, c.tile_cfg, c.nct, c.G, s,
+                                    nullptr, 0, 0, act);
     if (c.direct)
         return egm_conv_direct_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, KH, KW, dil, c.NT,
-                                      c.nct, c.G, c.smem, s);
+                                      c.nct, c.G, c.smem, s, act);
     p.tiles_y = c.tiles_y; p.tiles_x = c.tiles_x; p.npt = c.npt; p.nct = c.nct;
     const int NT = c.NT;
     if (c.pipe) {
         hipStream_t st = (hipStream_t)s;
         if (KH == 3 && dil == 1) {
-            if (c.R == 4) return launch_pipe<1, 3, 3, 4>(p, c.G, st);                      // tall tiles: Cout <= 32 only (conv_plan)
-            if (c.R == 1) return launch_pipe<1, 3, 3, 1>(p, c.G, st);
-            return NT == 2 ? launch_pipe<2, 3, 3, 2>(p, c.G, st) : launch_pipe<1, 3, 3, 2>(p, c.G, st);
+            if (c.R == 4) return launch_pipe_act<1, 3, 3, 4>(p, c.G, st, act);             // tall tiles: Cout <= 32 only (conv_plan)
+            if (c.R == 1) return launch_pipe_act<1, 3, 3, 1>(p, c.G, st, act);
+            return NT == 2 ? launch_pipe_act<2, 3, 3, 2>(p, c.G, st, act) : launch_pipe_act<1, 3, 3, 2>(p, c.G, st, act);
         }
-        if (KH == 7) return NT == 2 ? launch_pipe<2, 1, 7, 2>(p, c.G, st) : launch_pipe<1, 1, 7, 2>(p, c.G, st);
-        return NT == 2 ? launch_pipe<2, 1, 1, 2>(p, c.G, st) : launch_pipe<1, 1, 1, 2>(p, c.G, st);
+        if (KH == 7) return NT == 2 ? launch_pipe_act<2, 1, 7, 2>(p, c.G, st, act) : launch_pipe_act<1, 1, 7, 2>(p, c.G, st, act);
+        return NT == 2 ? launch_pipe_act<2, 1, 1, 2>(p, c.G, st, act) : launch_pipe_act<1, 1, 1, 2>(p, c.G, st, act);
     }
     const int ps = (dtype == EGM_BF16) ? Mma<bf16_t>::kPixStride : Mma<float>::kPixStride;
     const bool halo = (dil == 1);
@@ -928,7 +843,18 @@ extern "C" int egm_conv_fwd(int dtype, const void* x, int ldx, const void* wf, c
     if (smem < red_bytes) smem = red_bytes;
     EGM_REQUIRE(smem <= 160 * 1024, "conv_fwd: LDS budget exceeded (%zu)", smem);
     hipStream_t st = (hipStream_t)s;
-    if (dtype == EGM_BF16) return NT == 2 ? launch_conv<bf16_t, 2>(p, smem, st) : launch_conv<bf16_t, 1>(p, smem, st);
-    if (dtype == EGM_F32) return NT == 2 ? launch_conv<float, 2>(p, smem, st) : launch_conv<float, 1>(p, smem, st);
+    if (dtype == EGM_BF16) return NT == 2 ? launch_conv_act<bf16_t, 2>(p, smem, st, act) : launch_conv_act<bf16_t, 1>(p, smem, st, act);
+    if (dtype == EGM_F32) return NT == 2 ? launch_conv_act<float, 2>(p, smem, st, act) : launch_conv_act<float, 1>(p, smem, st, act);
     EGM_FAIL(EGM_ERR_ARG, "conv_fwd: unknown dtype %d", dtype);
+}
+
+extern "C" int egm_conv_fwd(int dtype, const void* x, int ldx, const void* wf, const void* bias, int bias_n, void* y, int ldy, float* stats,
+                            int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, egm_stream_t s) {
+    return conv_fwd_impl(dtype, x, ldx, wf, bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, KH, KW, dil, EGM_ACT_NONE, s);
+}
+
+extern "C" int egm_conv_fwd_act(int dtype, const void* x, int ldx, const void* wf, const void* bias, int bias_n, void* y, int ldy, int N,
+                                int H, int W, int Cin, int Cout, int KH, int KW, int dil, int act, egm_stream_t s) {
+    EGM_REQUIRE(act >= EGM_ACT_NONE && act <= EGM_ACT_SILU, "conv_fwd_act: unknown activation %d", act);
+    return conv_fwd_impl(dtype, x, ldx, wf, bias, bias_n, y, ldy, nullptr, N, H, W, Cin, Cout, KH, KW, dil, act, s);
 }

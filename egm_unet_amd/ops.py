@@ -6,6 +6,7 @@ wider buffer).  torch is used for memory (torch.empty / views), streams and auto
 import ctypes
 import os
 import struct
+import threading
 import weakref
 
 import torch
@@ -1115,6 +1116,8 @@ class _ConvBNPool(Function):
 def conv_bn_lazy(x, conv, bn, act, dil=1, groups=1):
     """conv -> BatchNorm -> activation as an ops.Lazy: for a consumer whose first pass materialises the tensor itself (ops.mca_layer:
     BatchNorm apply + the three-axis statistics in one pass)."""
+    if _fold_packs() is not None:
+        return _fold_conv(x, conv, act, dil)            # folded: the layer's statistics pass reads the finished tensor
     if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
         bn.num_batches_tracked.add_(1)
     training = bn.training or bn.running_mean is None
@@ -1128,6 +1131,9 @@ def conv_bn_act_pool(x, conv, bn, act, dil=1, groups=1, out=None):
     """conv -> BatchNorm -> activation -> (result, maxpool2(result)): the skip-connection tensor (into the destination view `out` when
     given) and its pooled copy from one BatchNorm apply pass, one autograd node (see _ConvBNPool).  H and W must be even; callers fall
     back to conv_bn_act + fork_maxpool2 otherwise (pool_fusable)."""
+    if _fold_packs() is not None:
+        z = _fold_conv(x, conv, act, dil, out)
+        return z, maxpool2(z)
     if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
         bn.num_batches_tracked.add_(1)                  # bookkeeping counter (int64), as nn.BatchNorm2d does
     training = bn.training or bn.running_mean is None
@@ -1332,6 +1338,9 @@ class _MultiConvBN(Function):
 def multi_conv_bn_act(items):
     """items: K <= 4 tuples (x, conv, bn, act, dil, groups, out) of INDEPENDENT layers (x: NHWC tensor or Lazy) -> list of K outputs.
     With the BatchNorm passes shared between the layers (_MultiConvBN); falls back to K conv_bn_act calls when disabled or K == 1."""
+    if _fold_packs() is not None:
+        with conv_group():                                # folded: the K convolutions are all there is, one launch per instantiation
+            return [_fold_conv(x, conv, act, dil, out) for x, conv, bn, act, dil, groups, out in items]
     if not _FUSE_BN_MULTI or len(items) == 1 or len(items) > BN_MULTI_MAX:
         return [conv_bn_act(x, conv, bn, act, dil=dil, groups=groups, out=out) for x, conv, bn, act, dil, groups, out in items]
     meta, flat = [], []
@@ -1433,6 +1442,8 @@ def conv_bn_ew(x, conv, bn, act, p, mode, alpha=1.0, out=None):
     """F(p, act(BN(conv(x)))) with F = EW_GATE: p*(1+z) or EW_SAR: relu(alpha*p + z); 1x1 convs (the two users in EdgeEnhancedGRFB)."""
     if conv.weight.shape[2] != 1 or conv.weight.shape[3] != 1 or conv.groups != 1:
         raise RuntimeError("conv_bn_ew: 1x1 ungrouped convolutions only")
+    if _fold_packs() is not None:
+        return _fold_conv_ew(x, conv, act, p, mode, alpha, out)
     if pw_applicable(x, [conv]):
         return pw_conv_bn([(x, [(conv, bn, act, mode, p, alpha, out)])])[0]
     if not _FUSE_BN_EW:
@@ -1633,7 +1644,7 @@ def pw_sites(sites=None):
 
 def pw_applicable(x, convs, site="ew"):
     """True when the 1x1 convs `convs` (nn.Conv2d holders) reading the NHWC tensor / Lazy x can take the moment form."""
-    if not _FUSE_PW or site not in _PW_SITES:
+    if not _FUSE_PW or site not in _PW_SITES or _fold_packs() is not None:
         return False
     for c in convs:
         if tuple(c.weight.shape[2:]) != (1, 1) or c.groups != 1 or pad8(c.weight.shape[1]) != x.shape[3]:
@@ -1679,6 +1690,9 @@ def conv_bn_act(x, conv, bn, act, dil=1, groups=1, out=None, lazy=False):
     """conv -> BatchNorm -> activation (statistics from the conv epilogue).  x: NHWC tensor (a Lazy is materialised first).
     lazy="force" returns the result as a Lazy for a consumer that applies the BatchNorm in a pass of its own (MCALayer statistics, the
     classifier inside the apply pass); otherwise the result is materialised, into the destination view `out` when given."""
+    if _fold_packs() is not None:
+        z = _fold_conv(x, conv, act, dil, out)
+        return Lazy(z, _fold_identity(z.shape[3]), ACT_NONE) if out is None and lazy == "force" else z
     if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
         bn.num_batches_tracked.add_(1)                  # bookkeeping counter (int64), as nn.BatchNorm2d does
     training = bn.training or bn.running_mean is None
@@ -1690,6 +1704,84 @@ def conv_bn_act(x, conv, bn, act, dil=1, groups=1, out=None, lazy=False):
     if out is None and lazy == "force":                 # the consumer materialises the tensor in a pass of its own
         return z
     return z.materialize(out)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# folded inference (egm_unet_amd/infer.py): BatchNorm folded into the conv in front of it, the activation in the conv epilogue
+# ----------------------------------------------------------------------------------------------------------
+_fold_state = threading.local()
+
+
+class folded_inference:
+    """`with folded_inference(packs):` -- on THIS thread the conv -> BatchNorm entry points (conv_bn_act, conv_bn_lazy, conv_bn_act_pool,
+    conv_bn_ew, multi_conv_bn_act) run the eval-mode forward with every BatchNorm folded into its convolution.  packs: {conv holder:
+    (wf, bias)} from egm_conv_fold_pack_multi, plus "identity": fp32 [4, >= C] rows 1 | 0 | 0 | 1 (written before any capture).
+    No pass exists only to apply a BatchNorm: passes that fuse it with element-wise work (the EdgeAware gate, the GRFB residual tail,
+    the skip pool, the classifier) keep their launch with identity coefficients or become the plain element-wise kernel.  Entered by
+    infer.Predictor only; off, nothing changes."""
+
+    def __init__(self, packs):
+        self.packs, self.prev = packs, None
+
+    def __enter__(self):
+        self.prev = getattr(_fold_state, "packs", None)
+        _fold_state.packs = self.packs
+        return self
+
+    def __exit__(self, *a):
+        _fold_state.packs = self.prev
+        return False
+
+
+def _fold_packs():
+    return getattr(_fold_state, "packs", None)
+
+
+def _fold_identity(C):
+    ident = _fold_state.packs["identity"]
+    if ident.shape[1] < C:
+        raise RuntimeError(f"folded_inference: identity coefficients cover {ident.shape[1]} channels, {C} needed")
+    return ident[:, :C]
+
+
+def _fold_conv(x, conv, act, dil=1, out=None):
+    """act(conv(x) * s + b') with the folded pack of `conv` (egm_conv_fwd_act), into the destination view `out` when given"""
+    hit = _fold_state.packs.get(conv)
+    if hit is None:
+        raise RuntimeError("folded_inference: no folded pack for this convolution (not followed by a BatchNorm in the model)")
+    wf, bias = hit
+    x, ldx = _nhwc(materialize(x))
+    N, H, W, CinP = x.shape
+    Cout, Cin_g, KH, KW = conv.weight.shape
+    if pad8(Cin_g * conv.groups) != CinP:
+        raise RuntimeError(f"conv_bn: input has {CinP} channels, weight expects {Cin_g * conv.groups}")
+    CoutP = pad8(Cout)
+    z, ldz = _slot_or_new(None if out is None else [out], (N, H, W, CoutP), x.dtype, x.device)
+    lib().call("egm_conv_fwd_act", dtype_code(x.dtype), ptr(x), ldx, ptr(wf), ptr(bias), CoutP, ptr(z), ldz, N, H, W, CinP, CoutP, KH, KW,
+               1 if KH == 1 and KW == 1 else dil, act, stream())
+    return z
+
+
+def _fold_conv_ew(x, conv, act, p, mode, alpha, out):
+    """conv_bn_ew folded: the element-wise pass stays (it is real work), with identity BatchNorm coefficients"""
+    y = _fold_conv(x, conv, ACT_NONE)
+    p, ldp = _nhwc(materialize(p))
+    if tuple(p.shape) != tuple(y.shape):
+        raise RuntimeError(f"conv_bn_ew: element-wise operand {tuple(p.shape)} does not match the conv output {tuple(y.shape)}")
+    CoutP = y.shape[3]
+    o, ldo = _slot_or_new(None if out is None else [out], tuple(y.shape), y.dtype, y.device)
+    coef = _fold_identity(CoutP)
+    lib().call("egm_bn_ew_fwd", dtype_code(y.dtype), mode, ptr(y), CoutP, ptr(coef[0]), ptr(coef[1]), act, ptr(p), ldp, float(alpha), ptr(o),
+               ldo, _npix(y), CoutP, stream())
+    return o
+
+
+def claim_prepack(st):
+    """Point the packed-weight cache at the buffers of the prepack state `st` (a prepack_model state dict that is current), so the
+    convolutions without a BatchNorm take exactly these buffers -- the ones a captured graph keeps reading."""
+    for m, (wf, wd) in zip(st["convs"], st["bufs"]):
+        w = m.weight
+        _pack_cache[id(w)] = ((w.data_ptr(), w._version, _weight_generation[0], st["dtype"], m.groups, tuple(w.shape)), wf, wd, weakref.ref(w))
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -102,6 +102,22 @@ int egm_conv_kernel_name(int dtype, int N, int H, int W, int Cin, int Cout, int 
 int egm_conv_fwd(int dtype, const void* x, int ldx, const void* wf, const void* bias_f32, int bias_n, void* y, int ldy,
                  float* stats, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, egm_stream_t s);
 int egm_conv_stats_tiles(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil);
+/* egm_conv_fwd without statistics, with act (enum egm_act) applied in the epilogue after the bias, before the one rounding to `dtype`:
+ * y = act(conv(x, wf) + bias).  The eval-mode conv -> BatchNorm -> activation of egm_unet_amd/infer.py, with wf / bias from
+ * egm_conv_fold_pack_multi.  Same plan, kernel family, launch groups and ldy (concat slots) as egm_conv_fwd; act = NONE is
+ * egm_conv_fwd with stats = NULL. */
+int egm_conv_fwd_act(int dtype, const void* x, int ldx, const void* wf, const void* bias_f32, int bias_n, void* y, int ldy, int N, int H,
+                     int W, int Cin, int Cout, int KH, int KW, int dil, int act, egm_stream_t s);
+/* BatchNorm folded into the conv in front of it, every conv -> BatchNorm pair of a model in one launch (csrc/infer.hip).  table_dev:
+ * device array of 104-byte entries {const float* w, *b, *gamma, *beta, *running_mean, *running_var; void* wf; float* bias; float eps;
+ * int Cout, Cin, CoutP, CinP, KH, KW, groups, chunk0, pad;}; b, gamma, beta may be NULL (0, 1, 0).  With s = gamma / sqrt(running_var
+ * + eps): wf = egm_conv_pack's forward pack of w*s (fp32 product, one rounding to `dtype`), bias [CoutP] fp32 = (b - running_mean)*s
+ * + beta, padded channels 0.  Chunks of egm_conv_fold_chunk() elements per workgroup; chunk0 / total_chunks as for egm_conv_pack_multi. */
+int egm_conv_fold_chunk(void);
+int egm_conv_fold_pack_multi(int dtype, const void* table_dev, int n, long long total_chunks, egm_stream_t s);
+/* out[n][h][w] = lut[argmax_c logits[n][c][h][w]] (lut NULL: the index itself); logits fp32 NCHW, C <= 256, ties to the lowest index as
+ * torch.argmax (predict.py's mask and its color_map). */
+int egm_argmax_u8(const float* logits, const unsigned char* lut, unsigned char* out, int N, int C, int H, int W, egm_stream_t s);
 /* Weight gradient: dw_oihw_f32 [CoutR][CinR/groups][KH][KW] (+)= sum_pixels dy (x) x.
  * Cin/Cout are padded counts of the activation buffers, CinR/CoutR the real (unpadded) ones.
  * workspace: egm_conv_wgrad_workspace() bytes.  accumulate != 0 adds to dw. */
