@@ -8,6 +8,7 @@ import os
 import struct
 import threading
 import weakref
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function, Variable
@@ -42,6 +43,19 @@ def _f32(n, device, zero=False):
     return (torch.zeros if zero else torch.empty)(n, dtype=torch.float32, device=device)
 
 
+class _Switch:
+    """An A/B switch of this module (a bool; a set of names for pw_sites).  `.on` is what the code here reads; calling the object is the
+    public get / set.  The environment variable is read once, where the switch is defined (import time)."""
+
+    def __init__(self, env, default, doc=None, parse=lambda v: v != "0"):
+        self.on, self.__doc__ = parse(os.environ.get(env, default)), doc
+
+    def __call__(self, enabled=None):
+        if enabled is not None:
+            self.on = type(self.on)(enabled)
+        return type(self.on)(self.on)               # (a set is handed out as a copy)
+
+
 _zero_pools = {}
 
 
@@ -66,6 +80,30 @@ def _bn_conv_bias_grad(Cout, dy, training, device):
     """Gradient of a conv bias in front of a BatchNorm: identically zero when the BatchNorm normalises with batch statistics (the mean
     subtraction removes the bias), sum(dy) over the pixels when it is frozen (eval mode with grad enabled)."""
     return _zero_grad_vec(Cout, device) if training else _channel_sum(dy)[0, :Cout]
+
+
+def _slot_or_new(out_slot, shape, dtype, device):
+    """Output placement: `out_slot` is None or a one-element list holding a kernel-addressable NHWC view (a channel slice of a wider
+    buffer, e.g. of a concat destination) the result is written into -- the concat copy and its extra tensor write disappear.  The
+    list keeps the tensor out of autograd's sight: it is returned as a fresh output, not as an input passed through."""
+    if out_slot is None:
+        t = torch.empty(shape, dtype=dtype, device=device)
+        return t, shape[3]
+    t = out_slot[0]
+    v, ld = _nhwc(t)
+    if v.data_ptr() != t.data_ptr() or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+        raise RuntimeError(f"egm_unet_amd: output slot {tuple(t.shape)}/{t.dtype} does not fit result {tuple(shape)}/{dtype}")
+    return t, ld
+
+
+def cat_slots(N, H, W, channels, dtype, device):
+    """A concat destination [N, H, W, sum(channels)] and its channel-slice views, for producers that write in place."""
+    buf = torch.empty((N, H, W, sum(channels)), dtype=dtype, device=device)
+    views, off = [], 0
+    for c in channels:
+        views.append(buf[..., off:off + c])
+        off += c
+    return buf, views
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -370,25 +408,20 @@ def flush_ready_wgrads():
 # backward ends (egm_bias_grad_multi) instead of a pair per layer inside it.  Same hand-over protocol as the deferred weight gradients:
 # backward() returns an unfilled [Cout] tensor that autograd adopts as bias.grad (no reference kept here, so it is not copied), the
 # queue entry keeps dy alive and finds the tensor again through a weak reference or bias.grad's address.
-_DEFER_BGRAD = os.environ.get("EGM_DEFER_BGRAD", "1") != "0"
 _pending_bgrad = []
 _bgrad_table = DeviceTable()
 _bgrad_table_partial = DeviceTable()
 _BSUM_ENTRY = struct.Struct("<3Qq6i")       # egm_bsum_entry
 
 
-def defer_bgrads(enabled=None):
-    """Get / set whether conv bias gradients are left to the one multi-tensor pass at the end of backward."""
-    global _DEFER_BGRAD
-    if enabled is not None:
-        _DEFER_BGRAD = bool(enabled)
-    return _DEFER_BGRAD
+defer_bgrads = _Switch("EGM_DEFER_BGRAD", "1",
+                       """Get / set whether conv bias gradients are left to the one multi-tensor pass at the end of backward.""")
 
 
 def _bias_grad(gy, Cout, bias=None, defer=False):
     """db[c] = sum over pixels of gy[..., c] (gy NHWC, channels padded) -> fp32 [Cout].  defer: the conv's weight gradient is being
     deferred in this backward (so this is the only use of the layer in it) -- the bias gradient then joins the end-of-backward pass."""
-    if (defer and _DEFER_BGRAD and bias is not None and bias.is_leaf and bias.grad is None and not bias._backward_hooks
+    if (defer and defer_bgrads.on and bias is not None and bias.is_leaf and bias.grad is None and not bias._backward_hooks
             and not torch.is_grad_enabled()):
         gy, ldg = _nhwc(gy)
         gb = torch.empty(Cout, dtype=torch.float32, device=gy.device)
@@ -451,6 +484,7 @@ def _channel_sum(t):
 
 _DEFER_WGRAD = os.environ.get("EGM_DEFER_WGRAD", "1") != "0"
 
+
 class Lazy:
     """A logical activation z = act(scale*y + shift) that has NOT been written to memory: `y` is the raw conv output (the autograd
     stand-in: its gradient is, by convention, dL/dz), `coef` the fp32 [4, C] rows scale | shift | mean | rstd of the BatchNorm.
@@ -504,15 +538,8 @@ def _unlazy(x):
     return x, None, ACT_NONE
 
 
-_GROUP_CONVS = os.environ.get("EGM_GROUP_CONVS", "1") != "0"
-
-
-def group_convs(enabled=None):
-    """Get / set whether conv_group() merges launches (tests compare both ways)."""
-    global _GROUP_CONVS
-    if enabled is not None:
-        _GROUP_CONVS = bool(enabled)
-    return _GROUP_CONVS
+group_convs = _Switch("EGM_GROUP_CONVS", "1",
+                      """Get / set whether conv_group() merges launches (tests compare both ways).""")
 
 
 class conv_group:
@@ -524,7 +551,7 @@ class conv_group:
     serial = 0                                # number of the outermost block that is open / was opened last
 
     def __enter__(self):
-        self.on = _GROUP_CONVS
+        self.on = group_convs.on
         conv_group.depth += 1
         if conv_group.depth == 1:
             conv_group.serial += 1
@@ -587,23 +614,18 @@ def _queue_wgrad(ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, gw):
 
 
 # ---- 1x1 convolutions: data gradient + weight-gradient slabs in ONE pass over dy and x (csrc/pw_bn.hip, egm_conv1x1_bwd) -----------
-_FUSE_C1 = os.environ.get("EGM_CONV1X1_BWD", "1") != "0"
 _C1_DESC = struct.Struct("<5Qq6i")
 _C1_MAXC = int(os.environ.get("EGM_CONV1X1_BWD_MAXC", "64"))
 
 
-def fuse_c1(enabled=None):
-    """Get / set whether the backward of a 1x1 conv runs as one fused launch (dx + weight-gradient slabs) where that applies."""
-    global _FUSE_C1
-    if enabled is not None:
-        _FUSE_C1 = bool(enabled)
-    return _FUSE_C1
+fuse_c1 = _Switch("EGM_CONV1X1_BWD", "1",
+                  """Get / set whether the backward of a 1x1 conv runs as one fused launch (dx + weight-gradient slabs) where that applies.""")
 
 
 def _c1_shape_ok(x, gy, weight, dil, groups):
     # measured (profiles/r04_*): <= 64 channels on both sides 32-43 us against 60 us for the pair at 8 x 256^2 x 64; at 128 channels the
     # fused kernel needs one workgroup per CU and two column blocks and LOSES (73 us against 43 us), so those keep the pair
-    return (_FUSE_C1 and weight.shape[2] == 1 and weight.shape[3] == 1 and groups == 1 and x.shape[3] <= _C1_MAXC and gy.shape[3] <= _C1_MAXC
+    return (fuse_c1.on and weight.shape[2] == 1 and weight.shape[3] == 1 and groups == 1 and x.shape[3] <= _C1_MAXC and gy.shape[3] <= _C1_MAXC
             and bool(lib().cdll.egm_conv1x1_bwd_supported(dtype_code(x.dtype), x.shape[3], gy.shape[3])))
 
 
@@ -636,12 +658,13 @@ def _conv1x1_bwd(items):
     return res
 
 
-def _conv_grads(x, ldx, dy, weight, wd, dil, groups, Cin, Cout, need_gx, need_gw, x_split=0):
+def _conv_grads(x, ldx, dy, weight, wd, dil, groups, Cin, Cout, need_gx, need_gw, x_split=0, c1=True):
     """(data gradient, weight gradient) of a conv from a materialised dy [N, H, W, CoutP] (contiguous): one fused launch for a 1x1 conv
-    whose weight gradient is deferrable, the weight-gradient slab kernel followed by the data-gradient conv otherwise."""
+    whose weight gradient is deferrable (c1=False: never, the caller's launch sequence is the pair), the weight-gradient slab kernel
+    followed by the data-gradient conv otherwise."""
     N, H, W, CinP = x.shape
     CoutP = dy.shape[3]
-    if need_gw and not x_split and _c1_shape_ok(x, dy, weight, dil, groups):
+    if c1 and need_gw and not x_split and _c1_shape_ok(x, dy, weight, dil, groups):
         return _conv1x1_bwd([(x, ldx, dy, CoutP, weight, wd, need_gx, _wgrad_deferrable(weight))])[0]
     gx = gw = None
     if need_gw:
@@ -651,16 +674,12 @@ def _conv_grads(x, ldx, dy, weight, wd, dil, groups, Cin, Cout, need_gx, need_gw
     return gx, gw
 
 
-_MERGE_WGRAD = os.environ.get("EGM_MERGE_WGRAD", "1") != "0"
 _pending_slab_launch = []                 # deferred slab-kernel launches (argument tuples holding their tensors)
 
 
-def merge_wgrads(enabled=None):
-    """Get / set whether the slab kernels of deferred weight gradients are launched together when backward ends (merged launches)."""
-    global _MERGE_WGRAD
-    if enabled is not None:
-        _MERGE_WGRAD = bool(enabled)
-    return _MERGE_WGRAD
+merge_wgrads = _Switch("EGM_MERGE_WGRAD", "1",
+                       """Get / set whether the slab kernels of deferred weight gradients are launched together when backward ends (merged
+                       launches).""")
 
 
 _WGRAD_DESC = struct.Struct("<3Q14i")       # egm_conv_wgrad_desc
@@ -707,7 +726,7 @@ def _conv_wgrad(x, ldx, gy, ldg, weight, dil, groups, Cin, Cout, defer=None):
     ws = torch.empty(nbytes // 4 + 4, dtype=torch.float32, device=x.device)
     if defer is None:                     # (a caller that asked already -- _wgrad_deferrable consumes the use note -- passes the answer)
         defer = _wgrad_deferrable(weight)
-    if defer and _MERGE_WGRAD:
+    if defer and merge_wgrads.on:
         _wgrad_run_begin()
         # nothing reads the slabs before the end-of-backward reduction: the launch itself waits for it too and shares launches with the
         # other deferred ones (_flush_wgrads); x and gy stay alive in the queue entry
@@ -726,16 +745,12 @@ def _conv_wgrad(x, ldx, gy, ldg, weight, dil, groups, Cin, Cout, defer=None):
 # tensor of the right shape and registers what the BatchNorm backward needs under the stand-in's address; _ConvBN.backward picks it up.
 # Only used where the model code knows the tensor between the two nodes has exactly one consumer (so autograd hands the stand-in through
 # unchanged); an entry nobody consumed by the end of the backward pass is an error, not a silent garbage gradient.
-_FUSE_DZ = os.environ.get("EGM_FUSE_DZ", "1") != "0"
 _DEFERRED_DZ = {}
 
 
-def fuse_dz(enabled=None):
-    """Get / set whether BatchNorm backward computes dz on the fly from the classifier / MCALayer behind it (tests compare both ways)."""
-    global _FUSE_DZ
-    if enabled is not None:
-        _FUSE_DZ = bool(enabled)
-    return _FUSE_DZ
+fuse_dz = _Switch("EGM_FUSE_DZ", "1",
+                  """Get / set whether BatchNorm backward computes dz on the fly from the classifier / MCALayer behind it (tests compare both
+                  ways).""")
 
 
 def _check_deferred_dz():
@@ -764,7 +779,7 @@ def _defer_dz(standin, payload):
 
 
 def _dz_fusable(C):
-    return _FUSE_DZ and C % 8 == 0 and C <= 1024 and 256 % (C // 8) == 0
+    return fuse_dz.on and C % 8 == 0 and C <= 1024 and 256 % (C // 8) == 0
 
 
 class _Conv2d(Function):
@@ -807,13 +822,13 @@ class _Conv2d(Function):
         defer = _wgrad_deferrable(weight) if need_gw else False     # (consumes the weight's use note: asked once per backward)
         if has_bias and ctx.needs_input_grad[2]:
             gb = _zero_grad_vec(Cout, x.device) if ctx.bias_grad_zero else _bias_grad(gy, Cout, ctx.bias, defer)
-        if need_gw and not (need_gx and ctx.defer_dgrad and _FUSE_DZ) and _c1_shape_ok(x, gy, weight, dil, groups):
+        if need_gw and not (need_gx and ctx.defer_dgrad and fuse_dz.on) and _c1_shape_ok(x, gy, weight, dil, groups):
             # 1x1: data gradient + weight-gradient slabs from ONE pass over gy and x
             gx, gw = _conv1x1_bwd([(x, ldx, gy, ldg, weight, wd, need_gx, defer)])[0]
             return gx, gw, gb, None, None, None, None, None
         if need_gx:
             gx = torch.empty((N, H, W, CinP), dtype=x.dtype, device=x.device)
-            if ctx.defer_dgrad and _FUSE_DZ:
+            if ctx.defer_dgrad and fuse_dz.on:
                 # never written: the BatchNorm backward in front computes dz = gy * W per vector itself (egm_bn_cls_bwd_*)
                 _defer_dz(gx, ("cls", gy, ldg, weight.detach(), Cout, Cin))
             else:
@@ -836,7 +851,7 @@ def _conv_dgrad(dy, wd, N, H, W, CoutP, CinP, KH, KW, dil, x_split):
     concat's backward."""
     L, dt, st = lib(), dtype_code(dy.dtype), stream()
     gx = torch.empty((N, H, W, CinP), dtype=dy.dtype, device=dy.device)
-    if x_split and _FUSE_DZ and L.cdll.egm_conv_split_ok(dt, N, H, W, CoutP, CinP, KH, KW, dil, x_split):
+    if x_split and fuse_dz.on and L.cdll.egm_conv_split_ok(dt, N, H, W, CoutP, CinP, KH, KW, dil, x_split):
         ga = torch.empty((N, H, W, x_split), dtype=dy.dtype, device=dy.device)
         gb = torch.empty((N, H, W, CinP - x_split), dtype=dy.dtype, device=dy.device)
         L.call("egm_conv_fwd_split", dt, ptr(dy), CoutP, ptr(wd), ptr(ga), x_split, ptr(gb), CinP - x_split, x_split, N, H, W, CoutP, CinP,
@@ -847,15 +862,8 @@ def _conv_dgrad(dy, wd, N, H, W, CoutP, CinP, KH, KW, dil, x_split):
     return gx
 
 
-_FUSE_CLS = os.environ.get("EGM_FUSE_CLS", "1") != "0"
-
-
-def fuse_cls(enabled=None):
-    """Get / set whether the 1x1 classifier runs inside the BatchNorm apply pass of the layer in front (tests compare both ways)."""
-    global _FUSE_CLS
-    if enabled is not None:
-        _FUSE_CLS = bool(enabled)
-    return _FUSE_CLS
+fuse_cls = _Switch("EGM_FUSE_CLS", "1",
+                   """Get / set whether the 1x1 classifier runs inside the BatchNorm apply pass of the layer in front (tests compare both ways).""")
 
 
 class _BnActCls(Function):
@@ -898,7 +906,7 @@ class _BnActCls(Function):
             gb = _bias_grad(dl, nc, ctx.bias, defer)
         if ctx.needs_input_grad[0]:
             gy = torch.empty((N, H, W, C), dtype=z.dtype, device=dev)
-            if _FUSE_DZ and _dz_fusable(C):
+            if fuse_dz.on and _dz_fusable(C):
                 _defer_dz(gy, ("cls", dl, 8, weight.detach(), nc, Cin))     # never written: see _defer_dz
             else:
                 _, wd = _packed_weights(weight, 1, z.dtype)
@@ -909,13 +917,81 @@ class _BnActCls(Function):
 def bn_act_cls_ok(x, weight):
     """True when ops.bn_act_cls applies: x an ops.Lazy, a 1x1 classifier to <= 8 classes, channel count a power of two <= 512."""
     C = x.shape[3] if isinstance(x, Lazy) else 0
-    return (_FUSE_CLS and isinstance(x, Lazy) and weight.dim() == 4 and weight.shape[2] == 1 and weight.shape[3] == 1 and weight.shape[0] <= 8
+    return (fuse_cls.on and isinstance(x, Lazy) and weight.dim() == 4 and weight.shape[2] == 1 and weight.shape[3] == 1 and weight.shape[0] <= 8
             and pad8(weight.shape[1]) == C and C % 8 == 0 and C // 8 <= 64 and (C // 8) & (C // 8 - 1) == 0 and weight.is_contiguous())
 
 
 def bn_act_cls(x, weight, bias):
     """Lazy x -> fp32 NCHW logits of the 1x1 classifier (weight, bias); x's only consumer."""
     return _BnActCls.apply(x.y, x.coef, x.act, weight, bias)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# conv -> BatchNorm (+ activation): the steps every such node shares
+# ----------------------------------------------------------------------------------------------------------
+def _bn_step(bn):
+    """The per-forward bookkeeping of an nn.BatchNorm2d used as the parameter / buffer holder: bumps num_batches_tracked (an int64
+    counter, as nn.BatchNorm2d does; not where a graphed step keeps it) -> (training, momentum) for the kernels."""
+    if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
+        bn.num_batches_tracked.add_(1)
+    return bn.training or bn.running_mean is None, 0.1 if bn.momentum is None else bn.momentum
+
+
+def _rows(coef):
+    return ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3])
+
+
+def _bn_coef(stats, npix, gamma, beta, running_mean, running_var, eps, momentum, training, CP, C, dev):
+    """-> coef, fp32 [4, CP] rows scale | shift | save_mean | save_rstd (see Lazy): from the per-tile batch statistics `stats` when
+    training (the running statistics are updated on the way), from the running statistics otherwise."""
+    L, coef = lib(), _f32((4, CP), dev)
+    if training:
+        L.call("egm_bn_finalize", ptr(stats), stats.shape[0], npix, ptr(gamma.detach()), ptr(beta.detach()), eps, momentum,
+               ptr(running_mean), ptr(running_var), *_rows(coef), CP, C, stream())
+    else:
+        L.call("egm_bn_eval_coeffs", ptr(gamma.detach()), ptr(beta.detach()), ptr(running_mean), ptr(running_var), eps, *_rows(coef), CP, C,
+               stream())
+    return coef
+
+
+def _bn_bwd_buffers(y, nb=None):
+    """The temporaries of a BatchNorm backward over the conv output y -> (nb, part, sums, cf4, dy): `nb` blocks write their partial sums
+    to `part`; sums = fp32 [2, CP] rows sum(dz) | sum(dz * xhat), which are dbeta | dgamma; cf4 the per-channel coefficients of dy."""
+    CP, dev = y.shape[3], y.device
+    if nb is None:
+        nb = lib().query("egm_channel_partials_blocks", _npix(y), CP)
+    return nb, _f32(nb * 2 * CP, dev), _f32((2, CP), dev), _f32((4, CP), dev), torch.empty(tuple(y.shape), dtype=y.dtype, device=dev)
+
+
+def _bn_backward(family, lead, geo, y, coef, act, training, nb=None):
+    """What a conv -> BatchNorm node does in backward before the conv's own gradients: partial sums over (dz, y) -> egm_bn_bwd_coefs ->
+    dy in one apply pass.  -> (dy, sums).  The kernel family says where dz comes from: `family` is the entry-point prefix, `lead` its
+    leading arguments (the dtype and the tensors dz is read or computed from), `geo` its trailing geometry arguments:
+        egm_bn_act   dz is a tensor                                           (dt, dz, lddz)                      (npix, CP)
+        egm_bn_pool  dz = gskip + scatter(gpool), see _ConvBNPool             (dt, gskip, ldg, gpool, ldp)        (N, H, W, CP)
+        egm_bn_cls   dz = dlogits * W, see _defer_dz "cls"                    (dt, dl, lddl, w, nc, ldw)          (npix, CP)
+        egm_bn_mca   dz from the MCALayer's gates, see _defer_dz "mca"        (dt, dxo, ld, gates, mcoef, ns)     geometry + (CP,)
+    nb: the number of partial-sum blocks where the family has a decomposition of its own (egm_bn_pool_bwd_blocks)."""
+    L, st = lib(), stream()
+    y, ldy = _nhwc(y)
+    CP, npix = y.shape[3], _npix(y)
+    nb, part, sums, cf4, dy = _bn_bwd_buffers(y, nb)
+    rows, train = _rows(coef), 1 if training else 0
+    L.call(family + "_bwd_reduce", *lead, ptr(y), ldy, *rows, act, ptr(part), *geo, st)
+    L.call("egm_bn_bwd_coefs", ptr(part), nb, npix, *rows, train, ptr(sums), ptr(cf4), CP, st)
+    L.call(family + "_bwd_apply", *lead, ptr(y), ldy, *rows, act, train, ptr(sums), ptr(dy), CP, *geo, st)
+    return dy, sums
+
+
+def _conv_bn_grads(need, x, ldx, dy, weight, wd, sums, dil, groups, has_bias, Cin, Cout, training, x_split=0, c1=True, conv_grads=None):
+    """The tail of a conv -> BatchNorm backward: (gx, gw, gb, ggamma, gbeta) from the conv's gradient dy and the BatchNorm's `sums`.
+    need: needs_input_grad of (x, weight, bias, gamma, beta).  conv_grads: (gx, gw) where the caller has launched them already
+    (_MultiConvBN groups the launches of its members); c1 as in _conv_grads."""
+    if conv_grads is None:
+        conv_grads = _conv_grads(x, ldx, dy, weight, wd, dil, groups, Cin, Cout, need[0], need[1], x_split, c1)
+    gx, gw = conv_grads
+    gb = _bn_conv_bias_grad(Cout, dy, training, dy.device) if (has_bias and need[2]) else None
+    return gx, gw, gb, sums[1, :Cout] if need[3] else None, sums[0, :Cout] if need[4] else None
 
 
 class _ConvBN(Function):
@@ -934,15 +1010,7 @@ class _ConvBN(Function):
         ctx.x_split = int(x_split) if (x_split and 0 < x_split < x.shape[3] and x_split % 8 == 0) else 0
         Cout, Cin_g = weight.shape[0], weight.shape[1]
         y, stats, wd = _conv_forward(x, ldx, weight, bias, dil, groups, training)
-        CoutP, npix, dev = y.shape[3], _npix(y), y.device
-        L, st = lib(), stream()
-        coef = _f32((4, CoutP), dev)                    # scale, shift, save_mean, save_rstd
-        if training:
-            L.call("egm_bn_finalize", ptr(stats), stats.shape[0], npix, ptr(gamma.detach()), ptr(beta.detach()), eps, momentum,
-                   ptr(running_mean), ptr(running_var), ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), CoutP, Cout, st)
-        else:
-            L.call("egm_bn_eval_coeffs", ptr(gamma.detach()), ptr(beta.detach()), ptr(running_mean), ptr(running_var), eps,
-                   ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), CoutP, Cout, st)
+        coef = _bn_coef(stats, _npix(y), gamma, beta, running_mean, running_var, eps, momentum, training, y.shape[3], Cout, y.device)
         if ctx.needs_input_grad[1]:
             _note_conv_use(weight)
         ctx.save_for_backward(x, weight, wd, y, coef)
@@ -960,73 +1028,33 @@ class _ConvBN(Function):
         pend = _DEFERRED_DZ.pop(gz.data_ptr(), None) if _DEFERRED_DZ else None      # gz is a stand-in: dz comes from its producer's inputs
         gz, ldg = _nhwc(gz)
         x, ldx = _nhwc(x)
-        y, ldy = _nhwc(y)
-        N, H, W, CinP = x.shape
-        CoutP, npix, dev = y.shape[3], _npix(y), y.device
-        L, dt, st = lib(), dtype_code(x.dtype), stream()
-        scale, shift, mean, rstd = coef[0], coef[1], coef[2], coef[3]
-        nb = L.query("egm_channel_partials_blocks", npix, CoutP)
-        part = _f32(nb * 2 * CoutP, dev)
-        sums, cf4 = _f32((2, CoutP), dev), _f32((4, CoutP), dev)
-        train = 1 if training else 0
-        need_gx, need_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dy = torch.empty((N, H, W, CoutP), dtype=x.dtype, device=dev)
-        if pend is not None:
-            kind = pend[1][0]
-            if kind == "cls":
-                _, dl, lddl, wcls, nc, ldw = pend[1]
-                head = ("egm_bn_cls", (dt, ptr(dl), lddl, ptr(wcls), nc, ldw), (npix, CoutP))
-            else:
-                _, dxo, ldd, gates, mcoef, ns, geo = pend[1]
-                head = ("egm_bn_mca", (dt, ptr(dxo), ldd, ptr(gates), ptr(mcoef), ns), geo + (CoutP,))
-            L.call(head[0] + "_bwd_reduce", *head[1], ptr(y), ldy, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), act, ptr(part), *head[2], st)
-            L.call("egm_bn_bwd_coefs", ptr(part), nb, npix, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), train, ptr(sums), ptr(cf4), CoutP, st)
-            L.call(head[0] + "_bwd_apply", *head[1], ptr(y), ldy, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), act, train, ptr(sums),
-                   ptr(dy), CoutP, *head[2], st)
+        CoutP, npix, dt = y.shape[3], _npix(y), dtype_code(x.dtype)
+        if pend is None:
+            family = ("egm_bn_act", (dt, ptr(gz), ldg), (npix, CoutP))
+        elif pend[1][0] == "cls":
+            _, dl, lddl, wcls, nc, ldw = pend[1]
+            family = ("egm_bn_cls", (dt, ptr(dl), lddl, ptr(wcls), nc, ldw), (npix, CoutP))
         else:
-            L.call("egm_bn_act_bwd_reduce", dt, ptr(gz), ldg, ptr(y), ldy, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), act, ptr(part),
-                   npix, CoutP, st)
-            L.call("egm_bn_bwd_coefs", ptr(part), nb, npix, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), train, ptr(sums),
-                   ptr(cf4), CoutP, st)
-            L.call("egm_bn_act_bwd_apply", dt, ptr(gz), ldg, ptr(y), ldy, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), act,
-                   train, ptr(sums), ptr(dy), CoutP, npix, CoutP, st)
-        gx, gw = _conv_grads(x, ldx, dy, weight, wd, dil, groups, Cin, Cout, need_gx, need_gw, ctx.x_split)
-        gb = _bn_conv_bias_grad(Cout, dy, training, dev) if (has_bias and ctx.needs_input_grad[2]) else None
-        ggamma = sums[1, :Cout] if ctx.needs_input_grad[3] else None
-        gbeta = sums[0, :Cout] if ctx.needs_input_grad[4] else None
-        return gx, gw, gb, ggamma, gbeta, None, None, None, None, None, None, None, None, None
+            _, dxo, ldd, gates, mcoef, ns, geo = pend[1]
+            family = ("egm_bn_mca", (dt, ptr(dxo), ldd, ptr(gates), ptr(mcoef), ns), geo + (CoutP,))
+        dy, sums = _bn_backward(*family, y, coef, act, training)
+        return _conv_bn_grads(ctx.needs_input_grad, x, ldx, dy, weight, wd, sums, dil, groups, has_bias, Cin, Cout, training,
+                              ctx.x_split) + (None,) * 9
 
 
-# environment switch for A/B runs: the max pool at a skip connection fused into its producer / consumer (csrc/pool_fused.hip)
-_FUSE_POOL = os.environ.get("EGM_FUSE_POOL", "1") != "0"
+fuse_mca_bwd = _Switch("EGM_FUSE_MCA_BWD", "1",
+                       """Get / set whether the MCALayer backward computes du and dxo in one tiled launch (bf16; egm_mca_bwd_dudxo).""")
 
 
-_FUSE_MCA_BN = os.environ.get("EGM_FUSE_MCA_BN", "1") != "0"
-_FUSE_MCA_BWD = os.environ.get("EGM_FUSE_MCA_BWD", "1") != "0"
+fuse_mca_bn = _Switch("EGM_FUSE_MCA_BN", "1",
+                      """Get / set whether the BatchNorm+ReLU in front of an MCALayer is applied by the layer's statistics pass
+                      (egm_mca_reduce_bn).""")
 
 
-def fuse_mca_bwd(enabled=None):
-    """Get / set whether the MCALayer backward computes du and dxo in one tiled launch (bf16; egm_mca_bwd_dudxo)."""
-    global _FUSE_MCA_BWD
-    if enabled is not None:
-        _FUSE_MCA_BWD = bool(enabled)
-    return _FUSE_MCA_BWD
-
-
-def fuse_mca_bn(enabled=None):
-    """Get / set whether the BatchNorm+ReLU in front of an MCALayer is applied by the layer's statistics pass (egm_mca_reduce_bn)."""
-    global _FUSE_MCA_BN
-    if enabled is not None:
-        _FUSE_MCA_BN = bool(enabled)
-    return _FUSE_MCA_BN
-
-
-def fuse_pool(enabled=None):
-    """Get / set whether the skip-connection max pool is fused into the kernels on either side of it (tests compare both ways)."""
-    global _FUSE_POOL
-    if enabled is not None:
-        _FUSE_POOL = bool(enabled)
-    return _FUSE_POOL
+# the max pool at a skip connection fused into its producer / consumer (csrc/pool_fused.hip)
+fuse_pool = _Switch("EGM_FUSE_POOL", "1",
+                    """Get / set whether the skip-connection max pool is fused into the kernels on either side of it (tests compare both
+                    ways).""")
 
 
 class _ConvBNPool(Function):
@@ -1041,15 +1069,8 @@ class _ConvBNPool(Function):
         Cout, Cin_g = weight.shape[0], weight.shape[1]
         y, stats, wd = _conv_forward(x, ldx, weight, bias, dil, groups, training)
         N, H, W, CoutP = y.shape
-        npix, dev = _npix(y), y.device
-        L, dt, st = lib(), dtype_code(y.dtype), stream()
-        coef = _f32((4, CoutP), dev)                    # scale, shift, save_mean, save_rstd
-        if training:
-            L.call("egm_bn_finalize", ptr(stats), stats.shape[0], npix, ptr(gamma.detach()), ptr(beta.detach()), eps, momentum,
-                   ptr(running_mean), ptr(running_var), ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), CoutP, Cout, st)
-        else:
-            L.call("egm_bn_eval_coeffs", ptr(gamma.detach()), ptr(beta.detach()), ptr(running_mean), ptr(running_var), eps,
-                   ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), CoutP, Cout, st)
+        L, dt, st, dev = lib(), dtype_code(y.dtype), stream(), y.device
+        coef = _bn_coef(stats, _npix(y), gamma, beta, running_mean, running_var, eps, momentum, training, CoutP, Cout, dev)
         z, ldz = _slot_or_new(out_slot, (N, H, W, CoutP), y.dtype, dev)
         pooled = torch.empty((N, H // 2, W // 2, CoutP), dtype=y.dtype, device=dev)
         L.call("egm_bn_act_fwd_pool", dt, ptr(y), CoutP, ptr(coef[0]), ptr(coef[1]), act, ptr(z), ldz, ptr(pooled), CoutP, N, H, W, CoutP, st)
@@ -1067,50 +1088,26 @@ class _ConvBNPool(Function):
         x, weight, wd, y, coef, z = ctx.saved_tensors
         dil, groups, has_bias, Cin, Cout, act, training = ctx.meta
         x, ldx = _nhwc(x)
-        N, H, W, CinP = x.shape
-        CoutP, npix, dev = y.shape[3], _npix(y), y.device
-        KH, KW = weight.shape[2], weight.shape[3]
-        L, dt, st = lib(), dtype_code(x.dtype), stream()
-        scale, shift, mean, rstd = coef[0], coef[1], coef[2], coef[3]
-        sums, cf4 = _f32((2, CoutP), dev), _f32((4, CoutP), dev)
-        dy = torch.empty((N, H, W, CoutP), dtype=x.dtype, device=dev)
-        train = 1 if training else 0
+        N, H, W, CoutP = y.shape
+        L, dt = lib(), dtype_code(x.dtype)
         if gz is not None and gpool is not None:
             gz, ldg = _nhwc(gz)
             gpool, ldp = _nhwc(gpool)
+            family = ("egm_bn_pool", (dt, ptr(gz), ldg, ptr(gpool), ldp), (N, H, W, CoutP))
             nb = L.query("egm_bn_pool_bwd_blocks", N, H, W, CoutP)
-            part = _f32(nb * 2 * CoutP, dev)
-            L.call("egm_bn_pool_bwd_reduce", dt, ptr(gz), ldg, ptr(gpool), ldp, ptr(y), CoutP, ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
-                   act, ptr(part), N, H, W, CoutP, st)
-            L.call("egm_bn_bwd_coefs", ptr(part), nb, npix, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), train, ptr(sums), ptr(cf4), CoutP, st)
-            L.call("egm_bn_pool_bwd_apply", dt, ptr(gz), ldg, ptr(gpool), ldp, ptr(y), CoutP, ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
-                   act, train, ptr(sums), ptr(dy), CoutP, N, H, W, CoutP, st)
         else:
             # only one of the two consumers produced a gradient: the separate kernels
             if gz is None:
                 zk, ldzk = _nhwc(z)
                 gpool, ldp = _nhwc(gpool)
-                gz = torch.empty((N, H, W, CoutP), dtype=x.dtype, device=dev)
-                L.call("egm_maxpool2_bwd", dt, ptr(zk), ldzk, ptr(gpool), ldp, ptr(gz), CoutP, N, H, W, CoutP, st)
+                gz = torch.empty((N, H, W, CoutP), dtype=x.dtype, device=y.device)
+                L.call("egm_maxpool2_bwd", dt, ptr(zk), ldzk, ptr(gpool), ldp, ptr(gz), CoutP, N, H, W, CoutP, stream())
             gz, ldg = _nhwc(gz)
-            nb = L.query("egm_channel_partials_blocks", npix, CoutP)
-            part = _f32(nb * 2 * CoutP, dev)
-            L.call("egm_bn_act_bwd_reduce", dt, ptr(gz), ldg, ptr(y), CoutP, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), act, ptr(part),
-                   npix, CoutP, st)
-            L.call("egm_bn_bwd_coefs", ptr(part), nb, npix, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), train, ptr(sums), ptr(cf4), CoutP, st)
-            L.call("egm_bn_act_bwd_apply", dt, ptr(gz), ldg, ptr(y), CoutP, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), act, train,
-                   ptr(sums), ptr(dy), CoutP, npix, CoutP, st)
-        gx = gw = gb = None
-        if ctx.needs_input_grad[1]:
-            gw = _conv_wgrad(x, ldx, dy, CoutP, weight, dil, groups, Cin, Cout)
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty((N, H, W, CinP), dtype=x.dtype, device=dev)
-            L.call("egm_conv_fwd", dt, ptr(dy), CoutP, ptr(wd), None, 0, ptr(gx), CinP, None, N, H, W, CoutP, CinP, KH, KW, dil, st)
-        if has_bias and ctx.needs_input_grad[2]:
-            gb = _bn_conv_bias_grad(Cout, dy, training, dev)
-        ggamma = sums[1, :Cout] if ctx.needs_input_grad[3] else None
-        gbeta = sums[0, :Cout] if ctx.needs_input_grad[4] else None
-        return gx, gw, gb, ggamma, gbeta, None, None, None, None, None, None, None, None, None
+            family, nb = ("egm_bn_act", (dt, ptr(gz), ldg), (_npix(y), CoutP)), None
+        dy, sums = _bn_backward(*family, y, coef, act, training, nb)
+        # c1=False: this node issues the weight-gradient kernel and the data-gradient conv for a 1x1 conv too, never the fused launch
+        return _conv_bn_grads(ctx.needs_input_grad, x, ldx, dy, weight, wd, sums, dil, groups, has_bias, Cin, Cout, training,
+                              c1=False) + (None,) * 9
 
 
 def conv_bn_lazy(x, conv, bn, act, dil=1, groups=1):
@@ -1118,10 +1115,7 @@ def conv_bn_lazy(x, conv, bn, act, dil=1, groups=1):
     BatchNorm apply + the three-axis statistics in one pass)."""
     if _fold_packs() is not None:
         return _fold_conv(x, conv, act, dil)            # folded: the layer's statistics pass reads the finished tensor
-    if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
-        bn.num_batches_tracked.add_(1)
-    training = bn.training or bn.running_mean is None
-    momentum = 0.1 if bn.momentum is None else bn.momentum
+    training, momentum = _bn_step(bn)
     y, coef = _ConvBN.apply(materialize(x), conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, act,
                             training, dil, groups)
     return Lazy(y, coef, act)
@@ -1134,10 +1128,7 @@ def conv_bn_act_pool(x, conv, bn, act, dil=1, groups=1, out=None):
     if _fold_packs() is not None:
         z = _fold_conv(x, conv, act, dil, out)
         return z, maxpool2(z)
-    if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
-        bn.num_batches_tracked.add_(1)                  # bookkeeping counter (int64), as nn.BatchNorm2d does
-    training = bn.training or bn.running_mean is None
-    momentum = 0.1 if bn.momentum is None else bn.momentum
+    training, momentum = _bn_step(bn)
     x = materialize(x)
     return _ConvBNPool.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, act,
                              training, dil, groups, None if out is None else [out])
@@ -1145,7 +1136,7 @@ def conv_bn_act_pool(x, conv, bn, act, dil=1, groups=1, out=None):
 
 def pool_fusable(x):
     """True when the fused skip-connection pool applies to the NHWC tensor / Lazy x (switch on, even H and W, <= 1024 channels)."""
-    return _FUSE_POOL and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0 and x.shape[1] >= 2 and x.shape[2] >= 2 and x.shape[3] <= 1024
+    return fuse_pool.on and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0 and x.shape[1] >= 2 and x.shape[2] >= 2 and x.shape[3] <= 1024
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -1158,20 +1149,13 @@ class _BnAct(Function):
         N, H, W, CP = y.shape
         C, npix, dev = gamma.shape[0], _npix(y), y.device
         L, dt, st = lib(), dtype_code(y.dtype), stream()
-        coef = _f32((4, CP), dev)                       # scale, shift, save_mean, save_rstd
-        scale, shift, mean, rstd = coef[0], coef[1], coef[2], coef[3]
-        if training:
-            if stats is None:
-                nb = L.query("egm_channel_partials_blocks", npix, CP)
-                stats = _f32((nb, 2, CP), dev)
-                L.call("egm_channel_sums", dt, ptr(y), ldy, npix, CP, ptr(stats), st)
-            L.call("egm_bn_finalize", ptr(stats), stats.shape[0], npix, ptr(gamma.detach()), ptr(beta.detach()), eps, momentum,
-                   ptr(running_mean), ptr(running_var), ptr(scale), ptr(shift), ptr(mean), ptr(rstd), CP, C, st)
-        else:
-            L.call("egm_bn_eval_coeffs", ptr(gamma.detach()), ptr(beta.detach()), ptr(running_mean), ptr(running_var), eps,
-                   ptr(scale), ptr(shift), ptr(mean), ptr(rstd), CP, C, st)
+        if training and stats is None:
+            nb = L.query("egm_channel_partials_blocks", npix, CP)
+            stats = _f32((nb, 2, CP), dev)
+            L.call("egm_channel_sums", dt, ptr(y), ldy, npix, CP, ptr(stats), st)
+        coef = _bn_coef(stats, npix, gamma, beta, running_mean, running_var, eps, momentum, training, CP, C, dev)
         z, ldz = _slot_or_new(out_slot, (N, H, W, CP), y.dtype, dev)
-        L.call("egm_bn_act_fwd", dt, ptr(y), ldy, ptr(scale), ptr(shift), act, ptr(z), ldz, npix, CP, st)
+        L.call("egm_bn_act_fwd", dt, ptr(y), ldy, ptr(coef[0]), ptr(coef[1]), act, ptr(z), ldz, npix, CP, st)
         ctx.save_for_backward(y, coef)
         ctx.meta = (act, training, C)
         return z
@@ -1185,18 +1169,18 @@ class _BnAct(Function):
         N, H, W, CP = y.shape
         npix, dev = _npix(y), y.device
         L, dt, st = lib(), dtype_code(y.dtype), stream()
-        scale, shift, mean, rstd = coef[0], coef[1], coef[2], coef[3]
+        # the egm_bn_act family without _bn_backward: no conv behind it, so the sums need no egm_bn_bwd_coefs (egm_reduce_tiles), and
+        # the apply pass runs only when the input wants a gradient
+        rows = _rows(coef)
         nb = L.query("egm_channel_partials_blocks", npix, CP)
         part = _f32(nb * 2 * CP, dev)
         sums = _f32((2, CP), dev)
-        L.call("egm_bn_act_bwd_reduce", dt, ptr(gz), ldg, ptr(y), ldy, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), act,
-               ptr(part), npix, CP, st)
+        L.call("egm_bn_act_bwd_reduce", dt, ptr(gz), ldg, ptr(y), ldy, *rows, act, ptr(part), npix, CP, st)
         L.call("egm_reduce_tiles", ptr(part), nb, CP, ptr(sums), st)
         gy = None
         if ctx.needs_input_grad[0]:
             gy = torch.empty((N, H, W, CP), dtype=y.dtype, device=dev)
-            L.call("egm_bn_act_bwd_apply", dt, ptr(gz), ldg, ptr(y), ldy, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), act,
-                   1 if training else 0, ptr(sums), ptr(gy), CP, npix, CP, st)
+            L.call("egm_bn_act_bwd_apply", dt, ptr(gz), ldg, ptr(y), ldy, *rows, act, 1 if training else 0, ptr(sums), ptr(gy), CP, npix, CP, st)
         ggamma = sums[1, :C] if ctx.needs_input_grad[2] else None
         gbeta = sums[0, :C] if ctx.needs_input_grad[3] else None
         return gy, None, ggamma, gbeta, None, None, None, None, None, None, None
@@ -1207,7 +1191,7 @@ class _BnAct(Function):
 # ----------------------------------------------------------------------------------------------------------
 BN_MULTI_MAX = 4
 _BN_FINALIZE, _BN_FWD, _BN_BWD_REDUCE, _BN_BWD_COEFS, _BN_BWD_APPLY = range(5)    # enum egm_bn_multi_pass
-_FUSE_BN_MULTI = os.environ.get("EGM_BN_MULTI", "1") != "0"
+fuse_bn_multi = _Switch("EGM_BN_MULTI", "1")
 
 
 def _bn_desc(y=None, z=None, dz=None, dy=None, coef=None, stats=None, gamma=None, beta=None, rm=None, rv=None, partials=None, sums=None,
@@ -1216,6 +1200,10 @@ def _bn_desc(y=None, z=None, dz=None, dy=None, coef=None, stats=None, gamma=None
     dp = lambda t: 0 if t is None else t.data_ptr()
     return struct.pack("<13Qq10i2f", dp(y), dp(z), dp(dz), dp(dy), dp(coef), dp(stats), dp(gamma), dp(beta), dp(rm), dp(rv), dp(partials),
                        dp(sums), dp(cf4), npix, ldy, ldz, lddz, lddy, ntiles, nblocks, C, C_real, act, train, eps, momentum)
+
+
+# one member of a _MultiConvBN node in backward; need: needs_input_grad of its (x, weight, bias, gamma, beta)
+_Member = namedtuple("_Member", "x ldx weight wd dy sums need alive")
 
 
 class _MultiConvBN(Function):
@@ -1244,14 +1232,13 @@ class _MultiConvBN(Function):
             Cout, Cin_g = weight.shape[0], weight.shape[1]
             x, ldx, y, stats, wd = convs[k]
             CoutP, npix, dev = y.shape[3], _npix(y), y.device
-            coef = _f32((4, CoutP), dev)
-            if training:
+            if training:                                      # one finalize launch for all members (below) instead of _bn_coef's
+                coef = _f32((4, CoutP), dev)
                 descs_fin += _bn_desc(coef=coef, stats=stats, gamma=gamma.detach(), beta=beta.detach(), rm=rm, rv=rv, npix=npix,
                                       ntiles=stats.shape[0], C=CoutP, C_real=Cout, eps=eps, momentum=momentum)
                 keep.append(stats)
             else:
-                L.call("egm_bn_eval_coeffs", ptr(gamma.detach()), ptr(beta.detach()), ptr(rm), ptr(rv), eps, ptr(coef[0]), ptr(coef[1]),
-                       ptr(coef[2]), ptr(coef[3]), CoutP, Cout, st)
+                coef = _bn_coef(None, npix, gamma, beta, rm, rv, eps, momentum, False, CoutP, Cout, dev)
             z, ldz = _slot_or_new(out_slot, tuple(y.shape), y.dtype, dev)
             descs_fwd += _bn_desc(y=y, z=z, coef=coef, npix=npix, ldy=CoutP, ldz=ldz, C=CoutP, act=act)
             if ctx.needs_input_grad[1 + 5 * k + 1]:
@@ -1271,68 +1258,51 @@ class _MultiConvBN(Function):
         K = len(ctx.meta)
         L, st = lib(), stream()
         sv = ctx.saved_tensors
-        per, d_red, d_coef, d_app = [], b"", b"", b""
+        mem, d_red, d_coef, d_app = [], b"", b"", b""
         for k in range(K):
             x, weight, wd, y, coef = sv[5 * k:5 * k + 5]
             dil, groups, has_bias, Cin, Cout, act, training = ctx.meta[k]
             g, ldg = _nhwc(gz[k])
             x, ldx = _nhwc(x)
-            N, H, W, CinP = x.shape
-            CoutP, npix, dev = y.shape[3], _npix(y), y.device
-            nb = L.query("egm_channel_partials_blocks", npix, CoutP)
-            part, sums, cf4 = _f32(nb * 2 * CoutP, dev), _f32((2, CoutP), dev), _f32((4, CoutP), dev)
-            dy = torch.empty((N, H, W, CoutP), dtype=x.dtype, device=dev)
-            common = dict(y=y, dz=g, coef=coef, partials=part, sums=sums, cf4=cf4, npix=npix, ldy=CoutP, lddz=ldg, nblocks=nb, C=CoutP,
+            CoutP = y.shape[3]
+            nb, part, sums, cf4, dy = _bn_bwd_buffers(y)
+            common = dict(y=y, dz=g, coef=coef, partials=part, sums=sums, cf4=cf4, npix=_npix(y), ldy=CoutP, lddz=ldg, nblocks=nb, C=CoutP,
                           act=act, train=1 if training else 0)
             d_red += _bn_desc(**common)
             d_coef += _bn_desc(**common)
             d_app += _bn_desc(dy=dy, lddy=CoutP, **common)
-            # every temporary stays referenced until the launches that use it are enqueued (freed earlier, the caching allocator
-            # would hand its memory to the next layer's temporaries: the kernels are not in the stream yet)
-            per.append((x, ldx, weight, wd, g, dy, sums, N, H, W, CinP, CoutP, part, cf4))
-        dt = dtype_code(per[0][0].dtype)
+            # every temporary stays referenced (`alive`) until the launches that use it are enqueued (freed earlier, the caching
+            # allocator would hand its memory to the next layer's temporaries: the kernels are not in the stream yet)
+            mem.append(_Member(x, ldx, weight, wd, dy, sums, ctx.needs_input_grad[1 + 5 * k:6 + 5 * k], (g, part, cf4)))
+        dt = dtype_code(mem[0].x.dtype)
         L.call("egm_bn_multi", dt, _BN_BWD_REDUCE, d_red, K, st)
         L.call("egm_bn_multi", dt, _BN_BWD_COEFS, d_coef, K, st)
         L.call("egm_bn_multi", dt, _BN_BWD_APPLY, d_app, K, st)
-        grads = [None]
         gxs, gws = [None] * K, [None] * K
         # the 1x1 members (deferrable weight gradients): data gradient + weight-gradient slabs of all of them in ONE fused launch
-        fused = [k for k in range(K) if ctx.needs_input_grad[1 + 5 * k + 1] and _c1_shape_ok(per[k][0], per[k][5], per[k][2], ctx.meta[k][0], ctx.meta[k][1])]
+        fused = [k for k, m in enumerate(mem) if m.need[1] and _c1_shape_ok(m.x, m.dy, m.weight, ctx.meta[k][0], ctx.meta[k][1])]
         if fused:
-            res = _conv1x1_bwd([(per[k][0], per[k][1], per[k][5], per[k][11], per[k][2], per[k][3], ctx.needs_input_grad[1 + 5 * k],
-                                 _wgrad_deferrable(per[k][2])) for k in fused])
-            for k, (gx_k, gw_k) in zip(fused, res):
-                gxs[k], gws[k] = gx_k, gw_k
+            res = _conv1x1_bwd([(m.x, m.ldx, m.dy, m.dy.shape[3], m.weight, m.wd, m.need[0], _wgrad_deferrable(m.weight))
+                                for m in (mem[k] for k in fused)])
+            for k, r in zip(fused, res):
+                gxs[k], gws[k] = r
+        rest = [(k, m) for k, m in enumerate(mem) if k not in fused]
         with conv_group():                                    # the other data gradients: one launch per kernel instantiation
-            for k in range(K):
-                if k in fused:
-                    continue
-                x, ldx, weight, wd, g, dy, sums, N, H, W, CinP, CoutP = per[k][:12]
-                dil = ctx.meta[k][0]
-                KH, KW = weight.shape[2], weight.shape[3]
-                if ctx.needs_input_grad[1 + 5 * k]:
-                    gxs[k] = torch.empty((N, H, W, CinP), dtype=x.dtype, device=x.device)
-                    L.call("egm_conv_fwd", dt, ptr(dy), CoutP, ptr(wd), None, 0, ptr(gxs[k]), CinP, None, N, H, W, CoutP, CinP, KH, KW, dil, st)
+            for k, m in rest:
+                if m.need[0]:
+                    N, H, W, CinP = m.x.shape
+                    gxs[k] = _conv_dgrad(m.dy, m.wd, N, H, W, m.dy.shape[3], CinP, m.weight.shape[2], m.weight.shape[3], ctx.meta[k][0], 0)
         with conv_group():                                    # ... and their weight gradients (slab kernels)
-            for k in range(K):
-                if k in fused:
-                    continue
-                x, ldx, weight, wd, g, dy, sums, N, H, W, CinP, CoutP = per[k][:12]
+            for k, m in rest:
                 dil, groups, has_bias, Cin, Cout, act, training = ctx.meta[k]
-                if ctx.needs_input_grad[1 + 5 * k + 1]:
-                    gws[k] = _conv_wgrad(x, ldx, dy, CoutP, weight, dil, groups, Cin, Cout)
-        for k in range(K):
-            x, ldx, weight, wd, g, dy, sums, N, H, W, CinP, CoutP = per[k][:12]
+                if m.need[1]:
+                    gws[k] = _conv_wgrad(m.x, m.ldx, m.dy, m.dy.shape[3], m.weight, dil, groups, Cin, Cout)
+        grads = (None,)
+        for k, m in enumerate(mem):
             dil, groups, has_bias, Cin, Cout, act, training = ctx.meta[k]
-            KH, KW = weight.shape[2], weight.shape[3]
-            base = 1 + 5 * k
-            gx, gw, gb = gxs[k], gws[k], None
-            if has_bias and ctx.needs_input_grad[base + 2]:
-                gb = _bn_conv_bias_grad(Cout, dy, training, x.device)
-            ggamma = sums[1, :Cout] if ctx.needs_input_grad[base + 3] else None
-            gbeta = sums[0, :Cout] if ctx.needs_input_grad[base + 4] else None
-            grads += [gx, gw, gb, ggamma, gbeta]
-        return tuple(grads)
+            grads += _conv_bn_grads(m.need, m.x, m.ldx, m.dy, m.weight, m.wd, m.sums, dil, groups, has_bias, Cin, Cout, training,
+                                    conv_grads=(gxs[k], gws[k]))
+        return grads
 
 
 def multi_conv_bn_act(items):
@@ -1341,36 +1311,21 @@ def multi_conv_bn_act(items):
     if _fold_packs() is not None:
         with conv_group():                                # folded: the K convolutions are all there is, one launch per instantiation
             return [_fold_conv(x, conv, act, dil, out) for x, conv, bn, act, dil, groups, out in items]
-    if not _FUSE_BN_MULTI or len(items) == 1 or len(items) > BN_MULTI_MAX:
+    if not fuse_bn_multi.on or len(items) == 1 or len(items) > BN_MULTI_MAX:
         return [conv_bn_act(x, conv, bn, act, dil=dil, groups=groups, out=out) for x, conv, bn, act, dil, groups, out in items]
     meta, flat = [], []
     for x, conv, bn, act, dil, groups, out in items:
-        if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
-            bn.num_batches_tracked.add_(1)
-        training = bn.training or bn.running_mean is None
-        momentum = 0.1 if bn.momentum is None else bn.momentum
+        training, momentum = _bn_step(bn)
         meta.append((bn.running_mean, bn.running_var, bn.eps, momentum, act, training, dil, groups, None if out is None else [out]))
         flat += [materialize(x), conv.weight, conv.bias, bn.weight, bn.bias]
     return list(_MultiConvBN.apply(meta, *flat))
 
 
-def fuse_bn_multi(enabled=None):
-    global _FUSE_BN_MULTI
-    if enabled is not None:
-        _FUSE_BN_MULTI = bool(enabled)
-    return _FUSE_BN_MULTI
-
-
 EW_GATE, EW_SAR = 0, 1                     # enum egm_ew_mode
-_FUSE_BN_EW = os.environ.get("EGM_FUSE_BN_EW", "1") != "0"
 
 
-def fuse_bn_ew(enabled=None):
-    """Get / set whether BatchNorm + the element-wise op behind it run as the fused kernels of csrc/bn_fused.hip."""
-    global _FUSE_BN_EW
-    if enabled is not None:
-        _FUSE_BN_EW = bool(enabled)
-    return _FUSE_BN_EW
+fuse_bn_ew = _Switch("EGM_FUSE_BN_EW", "1",
+                     """Get / set whether BatchNorm + the element-wise op behind it run as the fused kernels of csrc/bn_fused.hip.""")
 
 
 class _ConvBNEw(Function):
@@ -1390,13 +1345,7 @@ class _ConvBNEw(Function):
         if tuple(p.shape) != tuple(y.shape):
             raise RuntimeError(f"conv_bn_ew: element-wise operand {tuple(p.shape)} does not match the conv output {tuple(y.shape)}")
         L, dt, st = lib(), dtype_code(y.dtype), stream()
-        coef = _f32((4, CoutP), dev)
-        if training:
-            L.call("egm_bn_finalize", ptr(stats), stats.shape[0], npix, ptr(gamma.detach()), ptr(beta.detach()), eps, momentum,
-                   ptr(running_mean), ptr(running_var), ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), CoutP, Cout, st)
-        else:
-            L.call("egm_bn_eval_coeffs", ptr(gamma.detach()), ptr(beta.detach()), ptr(running_mean), ptr(running_var), eps,
-                   ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), CoutP, Cout, st)
+        coef = _bn_coef(stats, npix, gamma, beta, running_mean, running_var, eps, momentum, training, CoutP, Cout, dev)
         out, ldo = _slot_or_new(out_slot, tuple(y.shape), y.dtype, dev)
         L.call("egm_bn_ew_fwd", dt, mode, ptr(y), CoutP, ptr(coef[0]), ptr(coef[1]), act, ptr(p), ldp, float(alpha), ptr(out), ldo, npix,
                CoutP, st)
@@ -1414,28 +1363,19 @@ class _ConvBNEw(Function):
         g, ldg = _nhwc(g)
         x, ldx = _nhwc(x)
         q, ldq = _nhwc(q)
-        N, H, W, CinP = x.shape
-        CoutP, npix, dev = y.shape[3], _npix(y), y.device
-        KH, KW = weight.shape[2], weight.shape[3]
+        CoutP, npix = y.shape[3], _npix(y)
         L, dt, st = lib(), dtype_code(x.dtype), stream()
-        nb = L.query("egm_channel_partials_blocks", npix, CoutP)
-        part = _f32(nb * 2 * CoutP, dev)
-        L.call("egm_bn_ew_bwd_reduce", dt, mode, ptr(g), ldg, ptr(q), ldq, ptr(y), CoutP, ptr(coef[0]), ptr(coef[1]), ptr(coef[2]),
-               ptr(coef[3]), act, alpha, ptr(part), npix, CoutP, st)
-        sums, cf4 = _f32((2, CoutP), dev), _f32((4, CoutP), dev)
-        L.call("egm_bn_bwd_coefs", ptr(part), nb, npix, ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), 1 if training else 0,
-               ptr(sums), ptr(cf4), CoutP, st)
-        dy = torch.empty((N, H, W, CoutP), dtype=x.dtype, device=dev)
-        dp = torch.empty((N, H, W, CoutP), dtype=x.dtype, device=dev)
+        # the steps of _bn_backward with the egm_bn_ew kernels, whose signatures differ: alpha, the apply pass reads cf4 and writes dp too
+        nb, part, sums, cf4, dy = _bn_bwd_buffers(y)
+        dp = torch.empty_like(dy)
+        rows = _rows(coef)
+        L.call("egm_bn_ew_bwd_reduce", dt, mode, ptr(g), ldg, ptr(q), ldq, ptr(y), CoutP, *rows, act, alpha, ptr(part), npix, CoutP, st)
+        L.call("egm_bn_bwd_coefs", ptr(part), nb, npix, *rows, 1 if training else 0, ptr(sums), ptr(cf4), CoutP, st)
         L.call("egm_bn_ew_bwd_apply", dt, mode, ptr(g), ldg, ptr(q), ldq, ptr(y), CoutP, ptr(cf4), act, alpha, ptr(dy), CoutP, ptr(dp),
                CoutP, npix, CoutP, st)
-        gb = None
-        gx, gw = _conv_grads(x, ldx, dy, weight, wd, 1, 1, Cin, Cout, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
-        if has_bias and ctx.needs_input_grad[3]:
-            gb = _bn_conv_bias_grad(Cout, dy, training, dev)
-        ggamma = sums[1, :Cout] if ctx.needs_input_grad[4] else None
-        gbeta = sums[0, :Cout] if ctx.needs_input_grad[5] else None
-        return gx, dp if ctx.needs_input_grad[1] else None, gw, gb, ggamma, gbeta, None, None, None, None, None, None, None, None, None
+        need = ctx.needs_input_grad
+        gx, gw, gb, ggamma, gbeta = _conv_bn_grads((need[0],) + need[2:6], x, ldx, dy, weight, wd, sums, 1, 1, has_bias, Cin, Cout, training)
+        return (gx, dp if need[1] else None, gw, gb, ggamma, gbeta) + (None,) * 9
 
 
 def conv_bn_ew(x, conv, bn, act, p, mode, alpha=1.0, out=None):
@@ -1446,16 +1386,13 @@ def conv_bn_ew(x, conv, bn, act, p, mode, alpha=1.0, out=None):
         return _fold_conv_ew(x, conv, act, p, mode, alpha, out)
     if pw_applicable(x, [conv]):
         return pw_conv_bn([(x, [(conv, bn, act, mode, p, alpha, out)])])[0]
-    if not _FUSE_BN_EW:
+    if not fuse_bn_ew.on:
         z = conv_bn_act(x, conv, bn, act)
         if mode == EW_GATE:
             return gate_mul(p, z) if out is None else materialize(gate_mul(p, z), out)
         r = scale_add_relu(p, alpha, z)
         return r if out is None else materialize(r, out)
-    if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
-        bn.num_batches_tracked.add_(1)
-    training = bn.training or bn.running_mean is None
-    momentum = 0.1 if bn.momentum is None else bn.momentum
+    training, momentum = _bn_step(bn)
     return _ConvBNEw.apply(materialize(x), materialize(p), conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
                            momentum, act, training, mode, alpha, None if out is None else [out])
 
@@ -1465,16 +1402,11 @@ def conv_bn_ew(x, conv, bn, act, p, mode, alpha=1.0, out=None):
 # ----------------------------------------------------------------------------------------------------------
 # Built, parity-tested (tests/test_gpu_pw.py) and measured SLOWER than the materialised chain on every site of the headline config
 # (+0.55 ms with the conv_bn_ew chains, +0.07 ms with the branch tails): opt-in.
-_FUSE_PW = os.environ.get("EGM_PW_BN", "0") != "0"
 _PW_HEAD = struct.Struct("<23Qq14i3f4x")          # egm_pw_head (include/egm_hip.h)
 
 
-def fuse_pw(enabled=None):
-    """Get / set whether 1x1 conv -> BatchNorm(+act, + GATE / SAR) chains run in the moment form (no conv output in memory)."""
-    global _FUSE_PW
-    if enabled is not None:
-        _FUSE_PW = bool(enabled)
-    return _FUSE_PW
+fuse_pw = _Switch("EGM_PW_BN", "0",
+                  """Get / set whether 1x1 conv -> BatchNorm(+act, + GATE / SAR) chains run in the moment form (no conv output in memory).""")
 
 
 def _pw_head(x=None, w=None, wd=None, bias=None, gamma=None, beta=None, rm=None, rv=None, coef=None, p=None, out=None, g=None, q=None, dp=None,
@@ -1619,10 +1551,7 @@ def pw_conv_bn(problems):
         flat.append(materialize(x))
         hm = []
         for conv, bn, act, mode, p, alpha, out in heads:
-            if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
-                bn.num_batches_tracked.add_(1)
-            training = bn.training or bn.running_mean is None
-            momentum = 0.1 if bn.momentum is None else bn.momentum
+            training, momentum = _bn_step(bn)
             hm.append((bn.running_mean, bn.running_var, bn.eps, momentum, act, 0 if mode is None else mode + 1, alpha, training,
                        None if out is None else [out]))
             flat += [conv.weight, conv.bias, bn.weight, bn.bias, None if mode is None else materialize(p)]
@@ -1630,21 +1559,18 @@ def pw_conv_bn(problems):
     return list(_PwConvBN.apply(meta, *flat))
 
 
-_PW_SITES = set(t for t in os.environ.get("EGM_PW_SITES", "ew,heads,tails").split(",") if t)
+_pw_sites = _Switch("EGM_PW_SITES", "ew,heads,tails", parse=lambda v: set(t for t in v.split(",") if t))
 
 
 def pw_sites(sites=None):
     """Get / set the places of EdgeEnhancedGRFB that use the moment form: "ew" (the conv_bn_ew chains: both EdgeAwareFeatureEnhancers and
     the shortcut), "heads" (the two 1x1 branch heads sharing the enhanced input), "tails" (the three 1x1 branch tails)."""
-    global _PW_SITES
-    if sites is not None:
-        _PW_SITES = set(sites)
-    return set(_PW_SITES)
+    return _pw_sites(sites)
 
 
 def pw_applicable(x, convs, site="ew"):
     """True when the 1x1 convs `convs` (nn.Conv2d holders) reading the NHWC tensor / Lazy x can take the moment form."""
-    if not _FUSE_PW or site not in _PW_SITES or _fold_packs() is not None:
+    if not fuse_pw.on or site not in _pw_sites.on or _fold_packs() is not None:
         return False
     for c in convs:
         if tuple(c.weight.shape[2:]) != (1, 1) or c.groups != 1 or pad8(c.weight.shape[1]) != x.shape[3]:
@@ -1652,36 +1578,9 @@ def pw_applicable(x, convs, site="ew"):
     return _pw_ok(x.dtype, x.shape[3], [pad8(c.weight.shape[0]) for c in convs])
 
 
-def _slot_or_new(out_slot, shape, dtype, device):
-    """Output placement: `out_slot` is None or a one-element list holding a kernel-addressable NHWC view (a channel slice of a wider
-    buffer, e.g. of a concat destination) the result is written into -- the concat copy and its extra tensor write disappear.  The
-    list keeps the tensor out of autograd's sight: it is returned as a fresh output, not as an input passed through."""
-    if out_slot is None:
-        t = torch.empty(shape, dtype=dtype, device=device)
-        return t, shape[3]
-    t = out_slot[0]
-    v, ld = _nhwc(t)
-    if v.data_ptr() != t.data_ptr() or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-        raise RuntimeError(f"egm_unet_amd: output slot {tuple(t.shape)}/{t.dtype} does not fit result {tuple(shape)}/{dtype}")
-    return t, ld
-
-
-def cat_slots(N, H, W, channels, dtype, device):
-    """A concat destination [N, H, W, sum(channels)] and its channel-slice views, for producers that write in place."""
-    buf = torch.empty((N, H, W, sum(channels)), dtype=dtype, device=device)
-    views, off = [], 0
-    for c in channels:
-        views.append(buf[..., off:off + c])
-        off += c
-    return buf, views
-
-
 def bn_act(y, bn, act, stats=None, out=None):
     """bn: an nn.BatchNorm2d used as the parameter/buffer holder."""
-    training = bn.training or bn.running_mean is None
-    if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
-        bn.num_batches_tracked.add_(1)                  # bookkeeping counter (int64), as nn.BatchNorm2d does
-    momentum = 0.1 if bn.momentum is None else bn.momentum
+    training, momentum = _bn_step(bn)
     return _BnAct.apply(y, stats, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, act, training,
                         None if out is None else [out])
 
@@ -1693,10 +1592,7 @@ def conv_bn_act(x, conv, bn, act, dil=1, groups=1, out=None, lazy=False):
     if _fold_packs() is not None:
         z = _fold_conv(x, conv, act, dil, out)
         return Lazy(z, _fold_identity(z.shape[3]), ACT_NONE) if out is None and lazy == "force" else z
-    if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_egm_counter_managed", False):
-        bn.num_batches_tracked.add_(1)                  # bookkeeping counter (int64), as nn.BatchNorm2d does
-    training = bn.training or bn.running_mean is None
-    momentum = 0.1 if bn.momentum is None else bn.momentum
+    training, momentum = _bn_step(bn)
     x = materialize(x)
     y, coef = _ConvBN.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, act,
                             training, dil, groups, getattr(x, "_egm_split", 0))
@@ -2812,7 +2708,7 @@ class _MCALayer(Function):
         L, dt, st, dev = lib(), dtype_code(x.dtype), stream(), x.device
         Lax = H + W + C
         dxo = torch.empty_like(xo)
-        if _FUSE_MCA_BWD and x.dtype == torch.bfloat16:
+        if fuse_mca_bwd.on and x.dtype == torch.bfloat16:
             # du and dxo in one tiled pass: the 3 x 3 neighbourhoods come from LDS, du never reaches memory
             L.call("egm_mca_bwd_dudxo", dt, ptr(codes), ptr(xo), C, ptr(g), ldg, ptr(dxo), C, N, H, W, C, st)
         else:
@@ -2828,7 +2724,7 @@ class _MCALayer(Function):
         dks = _f32((3, 8), dev)                                  # zeroed by the kernel itself
         L.call("egm_mca_gates_bwd", ptr(dG), ptr(stats), ptr(o), ptr(gates), ptr(wh), ptr(kh), ks[0], ptr(ww), ptr(kw), ks[1],
                None if ns else ptr(pc[0]), None if ns else ptr(pc[1]), ks[2], ptr(dz), ptr(coef), ptr(dwts), ptr(dks), N, H, W, C, st)
-        if ctx.defer_dx and _FUSE_DZ:
+        if ctx.defer_dx and fuse_dz.on:
             dx = dxo                                            # stand-in: the BatchNorm backward in front evaluates dx per vector itself
             _defer_dz(dxo, ("mca", dxo, C, gates, coef, ns, (N, H, W)))
         else:
