@@ -321,12 +321,18 @@ def prepack_model(model, dtype):
     st["stamp"] = stamp
 
 
-# deferred weight-gradient reductions: the slab kernels run inside backward, ONE multi-conv reduce runs when backward ends.
-# Deferral hands autograd a gradient tensor that is filled later, which is only sound when that tensor is the weight's ONLY
-# contribution in this backward (autograd would otherwise sum unfilled buffers): _conv_uses counts the conv forwards a weight has
-# taken part in since its gradients were last produced, and a weight used more than once takes the immediate path.
-_pending_wgrad = []
-_wgrad_run = [None]                       # graph-task id of the backward run whose end-of-run flush is queued
+# ----------------------------------------------------------------------------------------------------------
+# deferred work of a backward run
+# ----------------------------------------------------------------------------------------------------------
+# A backward pass postpones four kinds of work to its end, all of it held by ONE _BackwardRun record per autograd-engine run:
+#   slabs    the slab kernels of deferred weight gradients, launched together, four of one kernel instantiation to a launch
+#   wgrads   the reductions of those slabs, ONE multi-conv launch (egm_wgrad_reduce_multi)
+#   bgrads   db = sum over pixels of dy for every nn.Conv2d bias that no BatchNorm follows, ONE pair of launches (egm_bias_grad_multi)
+#   dz       data gradients that a BatchNorm backward computes itself from a stand-in tensor (csrc/bn_dz_fused.hip)
+# Deferring a weight (bias) gradient hands autograd a tensor that is filled later, which is only sound when that tensor is the
+# parameter's ONLY contribution in this backward (autograd would otherwise sum unfilled buffers): _conv_uses counts the conv forwards a
+# weight has taken part in since its gradients were last produced, and a weight used more than once takes the immediate path.  That
+# count is written in forward, so it is keyed by weight, not by run.
 _conv_uses = {}                           # id(weight) -> [weakref, weight generation, forwards awaiting their backward, peak of that]
 
 
@@ -351,123 +357,211 @@ def _sole_conv_use(weight):
     if ent[2] <= 0:
         del _conv_uses[id(weight)]
     return sole
-_wgrad_table = DeviceTable()
-_wgrad_table_partial = DeviceTable()      # mid-backward flushes (eager gradient exchange): never disturbs the bytes a captured graph re-uploads
 
 
-def _flush_wgrads(ready_only=False):
-    """Finish the deferred weight gradients with ONE multi-conv reduction.  Runs as an autograd-engine callback when backward ends;
-    ready_only=True (a gradient bucket is about to be gathered mid-backward, parallel.GradAllReducer) finishes the convs whose
-    gradient tensor autograd has already adopted and leaves the others pending."""
-    if not ready_only:
-        _wgrad_run[0] = None
-    _flush_bgrads(ready_only)
-    _launch_pending_slabs()
-    if not _pending_wgrad:
-        return
+_DEFER_WGRAD = os.environ.get("EGM_DEFER_WGRAD", "1") != "0"
+merge_wgrads = _Switch("EGM_MERGE_WGRAD", "1",
+                       """Get / set whether the slab kernels of deferred weight gradients are launched together when backward ends (merged
+                       launches).""")
+defer_bgrads = _Switch("EGM_DEFER_BGRAD", "1",
+                       """Get / set whether conv bias gradients are left to the one multi-tensor pass at the end of backward.""")
+fuse_dz = _Switch("EGM_FUSE_DZ", "1",
+                  """Get / set whether BatchNorm backward computes dz on the fly from the classifier / MCALayer behind it (tests compare both
+                  ways).""")
+
+
+def _wgrad_deferrable(weight):
+    """True when the slab reduction of this weight's gradient may be left to the ONE multi-conv launch at the end of backward: a leaf
+    parameter whose only gradient contribution this is (not when a tensor hook may replace the returned buffer, nor under create_graph:
+    both hand autograd something it copies).  Consumes the conv-use note of the weight: call once per backward of a conv."""
+    return (_DEFER_WGRAD and _sole_conv_use(weight) and weight.is_leaf and weight.grad is None
+            and not weight._backward_hooks and not torch.is_grad_enabled())
+
+
+# The tables outlive every run on purpose: a captured hipGraph re-uploads their bytes on every replay.  The *_partial twins serve the
+# mid-backward flushes (eager gradient exchange), which must never disturb the bytes a captured graph re-uploads.
+_wgrad_table, _wgrad_table_partial, _bgrad_table, _bgrad_table_partial = DeviceTable(), DeviceTable(), DeviceTable(), DeviceTable()
+_BSUM_ENTRY = struct.Struct("<3Qq6i")       # egm_bsum_entry
+_WGRAD_DESC = struct.Struct("<3Q14i")       # egm_conv_wgrad_desc
+_wgrad_names = {}
+
+
+def _wgrad_kernel_of(dt, N, H, W, CinP, CoutP, KH, KW, dil):
+    key = (dt, N, H, W, CinP, CoutP, KH, KW, dil)
+    name = _wgrad_names.get(key)
+    if name is None:
+        buf = ctypes.create_string_buffer(96)
+        lib().cdll.egm_conv_wgrad_kernel_name(dt, N, H, W, CinP, CoutP, KH, KW, dil, ctypes.cast(buf, ctypes.c_void_p), 96)
+        name = _wgrad_names[key] = buf.value
+    return name
+
+
+# queue entries (they keep the tensors their launch reads alive; `param` is the weight / bias, gref / gptr its unfilled gradient)
+_Slab = namedtuple("_Slab", "dt x ldx gy ldg ws N H W CinP CoutP Cin Cout KH KW dil groups")
+_Wgrad = namedtuple("_Wgrad", "ws param nslab taps CoutP CinP Cout Cin groups gref gptr")
+_Bgrad = namedtuple("_Bgrad", "gy ldg npix C Cout param gref gptr")
+
+
+def _handed_over(queue, ready_only, name):
+    """The hand-over protocol of the deferred weight and bias gradients.  The unfilled tensor backward() returned was handed to autograd
+    with no reference kept here, so that it is adopted as param.grad without a copy (backward()) or returned to the caller as is
+    (torch.autograd.grad()); it is still reachable through the weak reference or as the storage param.grad now shares.
+    -> the entries to fill now; `queue` keeps those for later (ready_only: autograd has not adopted the tensor yet)."""
     todo, later = [], []
-    for ent in _pending_wgrad:
-        weight, gref, gptr = ent[1], ent[9], ent[10]
-        # The gradient tensor returned from backward() was handed over to autograd with no reference kept here, so that it is
-        # adopted as weight.grad without a copy (backward()) or returned to the caller as is (torch.autograd.grad()).  It is still
-        # reachable either through the weak reference or as the storage weight.grad now shares.
-        g = gref()
-        if g is None and weight.grad is not None and weight.grad.data_ptr() == gptr:
-            g = weight.grad
-        if g is not None:
+    for ent in queue:
+        grad = ent.param.grad
+        if ent.gref() is not None or (grad is not None and grad.data_ptr() == ent.gptr):
             todo.append(ent)
         elif ready_only:
             later.append(ent)
-        elif weight.grad is not None:
+        elif grad is not None:
             # the unfilled buffer is gone but the parameter HAS a gradient: autograd copied or transformed the buffer instead of
-            # adopting it (a tensor hook returning a new tensor, a non-stealable gradient), so weight.grad holds whatever the
-            # uninitialised buffer contained.  _conv_wgrad refuses to defer in the cases it can see; anything else must not train on.
-            raise RuntimeError("deferred conv weight gradient lost its destination: weight.grad exists but is not the buffer "
-                               "backward() returned (tensor hook / gradient copy); set EGM_DEFER_WGRAD=0 for this model")
-        # else: nobody holds the gradient and the parameter has none (torch.autograd.grad() result dropped, or the weight was not
+            # adopting it (a tensor hook returning a new tensor, a non-stealable gradient), so param.grad holds whatever the
+            # uninitialised buffer contained.  The deferring code refuses in the cases it can see; anything else must not train on.
+            raise RuntimeError(f"deferred conv {name} gradient lost its destination: {name}.grad exists but is not the buffer backward() "
+                               f"returned (tensor hook / gradient copy); set EGM_DEFER_{name[0].upper()}GRAD=0 for this model")
+        # else: nobody holds the gradient and the parameter has none (torch.autograd.grad() result dropped, or the parameter was not
         # among backward(inputs=...)): it was discarded, nothing to finish
-    _pending_wgrad[:] = later
-    if not todo:
-        return
-    blob, chunks = bytearray(), 0
-    per = lib().cdll.egm_wgrad_reduce_chunk()
-    for ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, gref, gptr in todo:
-        blob += struct.pack("<QQiiiiiiiiii", ws.data_ptr(), gptr, nslab, taps, CoutP, CinP, Cout, Cin, groups, 0, chunks, 0)
-        chunks += (taps * CoutP * CinP + per - 1) // per
-    dev = todo[0][1].device
-    _wgrad_table.reserve(dev); _wgrad_table_partial.reserve(dev)      # both exist before any capture can need them
-    table = (_wgrad_table_partial if ready_only else _wgrad_table).get(bytes(blob), dev)
-    lib().call("egm_wgrad_reduce_multi", ptr(table), len(todo), chunks, stream())
+    queue[:] = later
+    return todo
+
+
+_runs = {}                                # autograd graph-task id -> weak reference to its _BackwardRun; gone when the record dies
+
+
+class _BackwardRun:
+    """The deferred work of ONE autograd-engine run.  The engine owns it: the only strong reference is the end-of-run callback
+    (`finish`) queued on the run's graph task, _runs finds it by graph-task id while the run lasts.  A backward that raises never runs
+    its callbacks, the engine drops the graph task and the record (with the tensors its entries pin) goes with it; a backward nested in
+    another one (a Function whose backward calls backward, re-entrant checkpointing) has a graph task and hence a record of its own,
+    finished when IT ends, and leaves the outer run's entries alone.
+    The DeviceTables are shared by all runs.  Outside a capture that is safe under nesting (uploads are ordered on the stream, a rewrite
+    of the pinned bytes waits for the previous upload: upload_pinned); inside a hipGraph capture every distinct content takes one buffer
+    pair of DeviceTable.POOL, so nested runs inside a capture are bounded by that pool (exhaustion raises)."""
+    __slots__ = ("id", "slabs", "wgrads", "bgrads", "dz", "__weakref__")
+
+    def __init__(self, run_id):
+        self.id, self.slabs, self.wgrads, self.bgrads, self.dz = run_id, [], [], [], {}
+
+    def finish(self):
+        _runs.pop(self.id, None)
+        if self.dz:
+            kinds = [v[1][0] for v in self.dz.values()]
+            self.dz.clear()
+            raise RuntimeError(f"egm_unet_amd: deferred BatchNorm gradients {kinds} were never consumed (the tensor between the producer and "
+                               "its BatchNorm had another consumer); call ops.fuse_dz(False)")
+        self.flush()
+
+    def flush(self, ready_only=False):
+        """ready_only=True (a gradient bucket is about to be gathered mid-backward, parallel.GradAllReducer) finishes the gradients whose
+        tensor autograd has already adopted and leaves the others pending."""
+        self.flush_bgrads(ready_only)
+        self.launch_slabs()
+        self.reduce_wgrads(ready_only)
+
+    def flush_bgrads(self, ready_only=False):
+        todo = _handed_over(self.bgrads, ready_only, "bias") if self.bgrads else None
+        if not todo:
+            return
+        L = lib()
+        by_dtype = {}
+        for e in todo:
+            by_dtype.setdefault(e.gy.dtype, []).append(e)
+        for dtype, ents in by_dtype.items():
+            dev = ents[0].gy.device
+            nblks = [L.query("egm_channel_partials_blocks", e.npix, e.C) for e in ents]
+            ws = torch.empty(sum(nb * 2 * e.C for nb, e in zip(nblks, ents)), dtype=torch.float32, device=dev)
+            blob1, blob2, b1, b2, off = bytearray(), bytearray(), 0, 0, 0
+            for nb, e in zip(nblks, ents):
+                part = ws.data_ptr() + 4 * off
+                blob1 += _BSUM_ENTRY.pack(e.gy.data_ptr(), part, e.gptr, e.npix, e.ldg, e.C, e.Cout, nb, b1, 0)
+                blob2 += _BSUM_ENTRY.pack(e.gy.data_ptr(), part, e.gptr, e.npix, e.ldg, e.C, e.Cout, nb, b2, 0)
+                b1 += nb; b2 += e.C // 8; off += nb * 2 * e.C
+            _bgrad_table.reserve(dev); _bgrad_table_partial.reserve(dev)
+            table = (_bgrad_table_partial if ready_only else _bgrad_table).get(bytes(blob1 + blob2), dev)
+            L.call("egm_bias_grad_multi", dtype_code(dtype), ptr(table), len(ents), b1, b2, stream())
+
+    def launch_slabs(self):
+        """The queued slab kernels, in queue order, those of one kernel instantiation four to a launch (egm_conv_wgrad_multi)."""
+        if not self.slabs:
+            return
+        L, st = lib(), stream()
+        todo, self.slabs = self.slabs, []
+        buckets = {}
+        for e in todo:
+            buckets.setdefault((e.dt, _wgrad_kernel_of(e.dt, e.N, e.H, e.W, e.CinP, e.CoutP, e.KH, e.KW, e.dil)), []).append(e)
+        per = 4                                                            # EGM_WGRAD_MULTI_MAX
+        for (dt, _name), ents in buckets.items():
+            for i in range(0, len(ents), per):
+                blob = b"".join(_WGRAD_DESC.pack(e.x.data_ptr(), e.gy.data_ptr(), e.ws.data_ptr(), e.ldx, e.ldg, e.N, e.H, e.W, e.CinP, e.CoutP,
+                                                 e.Cin, e.Cout, e.KH, e.KW, e.dil, e.groups, 0) for e in ents[i:i + per])
+                L.call("egm_conv_wgrad_multi", dt, blob, len(ents[i:i + per]), st)
+
+    def reduce_wgrads(self, ready_only=False):
+        """Finish the deferred weight gradients with ONE multi-conv reduction."""
+        todo = _handed_over(self.wgrads, ready_only, "weight") if self.wgrads else None
+        if not todo:
+            return
+        blob, chunks = bytearray(), 0
+        per = lib().cdll.egm_wgrad_reduce_chunk()
+        for e in todo:
+            blob += struct.pack("<QQiiiiiiiiii", e.ws.data_ptr(), e.gptr, e.nslab, e.taps, e.CoutP, e.CinP, e.Cout, e.Cin, e.groups, 0, chunks, 0)
+            chunks += (e.taps * e.CoutP * e.CinP + per - 1) // per
+        dev = todo[0].param.device
+        _wgrad_table.reserve(dev); _wgrad_table_partial.reserve(dev)      # both exist before any capture can need them
+        table = (_wgrad_table_partial if ready_only else _wgrad_table).get(bytes(blob), dev)
+        lib().call("egm_wgrad_reduce_multi", ptr(table), len(todo), chunks, stream())
+
+
+def _run(create=True):
+    """The record of the backward run this is called from (create=False: None when the run has deferred nothing so far)."""
+    run_id = torch._C._current_graph_task_id()
+    ref = _runs.get(run_id)                 # (a plain dict, half the cost of a WeakValueDictionary: backward nodes look up on every call)
+    run = None if ref is None else ref()
+    if run is None and create:
+        run = _BackwardRun(run_id)
+        _runs[run_id] = weakref.ref(run, lambda _ref: _runs.pop(run_id, None))
+        Variable._execution_engine.queue_callback(run.finish)          # the one strong reference: the run's graph task
+    return run
 
 
 def flush_ready_wgrads():
-    _flush_wgrads(ready_only=True)
+    """Mid-backward (a gradient hook): finish what the current run has deferred and autograd has already adopted."""
+    run = _run(create=False)
+    if run is not None:
+        run.flush(ready_only=True)
 
 
-# deferred bias gradients: db = sum over pixels of dy for every nn.Conv2d bias that no BatchNorm follows, as ONE pair of launches when
-# backward ends (egm_bias_grad_multi) instead of a pair per layer inside it.  Same hand-over protocol as the deferred weight gradients:
-# backward() returns an unfilled [Cout] tensor that autograd adopts as bias.grad (no reference kept here, so it is not copied), the
-# queue entry keeps dy alive and finds the tensor again through a weak reference or bias.grad's address.
-_pending_bgrad = []
-_bgrad_table = DeviceTable()
-_bgrad_table_partial = DeviceTable()
-_BSUM_ENTRY = struct.Struct("<3Qq6i")       # egm_bsum_entry
+def _queue_wgrad(ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, gw):
+    _run().wgrads.append(_Wgrad(ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, weakref.ref(gw), gw.data_ptr()))
 
 
-defer_bgrads = _Switch("EGM_DEFER_BGRAD", "1",
-                       """Get / set whether conv bias gradients are left to the one multi-tensor pass at the end of backward.""")
+# deferred dz: the producer's backward (the 1x1 classifier's data gradient; the MCALayer's last step; a conv behind a concat) does not
+# run its kernel, or writes elsewhere: it returns a STAND-IN tensor of the right shape and registers what the consumer needs under the
+# stand-in's address; _ConvBN.backward / _UpCat.backward pick it up.  Only used where the model code knows the tensor between the two
+# nodes has exactly one consumer (so autograd hands the stand-in through unchanged); an entry nobody consumed by the end of the backward
+# run is an error (_BackwardRun.finish), not a silent garbage gradient.
+def _defer_dz(standin, payload):
+    _run().dz[standin.data_ptr()] = (standin, payload)             # the stand-in stays alive: its address cannot be recycled meanwhile
+
+
+def _take_dz(g):
+    """(stand-in, payload) when the incoming gradient `g` is a stand-in registered in this run, else None.  Creates no record."""
+    run = _run(create=False)
+    return run.dz.pop(g.data_ptr(), None) if run is not None and run.dz else None
 
 
 def _bias_grad(gy, Cout, bias=None, defer=False):
     """db[c] = sum over pixels of gy[..., c] (gy NHWC, channels padded) -> fp32 [Cout].  defer: the conv's weight gradient is being
-    deferred in this backward (so this is the only use of the layer in it) -- the bias gradient then joins the end-of-backward pass."""
+    deferred in this backward (so this is the only use of the layer in it) -- the bias gradient then joins the end-of-backward pass:
+    an unfilled [Cout] tensor is returned, the queue entry keeps gy alive."""
     if (defer and defer_bgrads.on and bias is not None and bias.is_leaf and bias.grad is None and not bias._backward_hooks
             and not torch.is_grad_enabled()):
         gy, ldg = _nhwc(gy)
         gb = torch.empty(Cout, dtype=torch.float32, device=gy.device)
-        _wgrad_run_begin()
-        _pending_bgrad.append((gy, ldg, _npix(gy), gy.shape[3], Cout, bias, weakref.ref(gb), gb.data_ptr()))
+        _run().bgrads.append(_Bgrad(gy, ldg, _npix(gy), gy.shape[3], Cout, bias, weakref.ref(gb), gb.data_ptr()))
         return gb
     return _channel_sum(gy)[0, :Cout]
-
-
-def _flush_bgrads(ready_only=False):
-    if not _pending_bgrad:
-        return
-    todo, later = [], []
-    for ent in _pending_bgrad:
-        bias, gref, gptr = ent[5], ent[6], ent[7]
-        g = gref()
-        if g is None and bias.grad is not None and bias.grad.data_ptr() == gptr:
-            g = bias.grad
-        if g is not None:
-            todo.append(ent)
-        elif ready_only:
-            later.append(ent)
-        elif bias.grad is not None:
-            raise RuntimeError("deferred conv bias gradient lost its destination: bias.grad exists but is not the buffer backward() "
-                               "returned (tensor hook / gradient copy); set EGM_DEFER_BGRAD=0 for this model")
-        # else: the gradient was discarded (torch.autograd.grad() result dropped, bias not among backward(inputs=...))
-    _pending_bgrad[:] = later
-    if not todo:
-        return
-    L = lib()
-    by_dtype = {}
-    for ent in todo:
-        by_dtype.setdefault(ent[0].dtype, []).append(ent)
-    for dtype, ents in by_dtype.items():
-        dev = ents[0][0].device
-        nblks = [L.query("egm_channel_partials_blocks", npix, C) for _gy, _ld, npix, C, *_ in ents]
-        ws = torch.empty(sum(nb * 2 * ent[3] for nb, ent in zip(nblks, ents)), dtype=torch.float32, device=dev)
-        blob1, blob2, b1, b2, off = bytearray(), bytearray(), 0, 0, 0
-        for nb, (gy, ldg, npix, C, Cout, _bias, _gref, gptr) in zip(nblks, ents):
-            part = ws.data_ptr() + 4 * off
-            blob1 += _BSUM_ENTRY.pack(gy.data_ptr(), part, gptr, npix, ldg, C, Cout, nb, b1, 0)
-            blob2 += _BSUM_ENTRY.pack(gy.data_ptr(), part, gptr, npix, ldg, C, Cout, nb, b2, 0)
-            b1 += nb; b2 += C // 8; off += nb * 2 * C
-        _bgrad_table.reserve(dev); _bgrad_table_partial.reserve(dev)
-        table = (_bgrad_table_partial if ready_only else _bgrad_table).get(bytes(blob1 + blob2), dev)
-        L.call("egm_bias_grad_multi", dtype_code(dtype), ptr(table), len(ents), b1, b2, stream())
 
 
 def _channel_sum(t):
@@ -480,9 +574,6 @@ def _channel_sum(t):
     lib().call("egm_channel_sums", dtype_code(t.dtype), ptr(t), ld, npix, C, ptr(part), stream())
     lib().call("egm_reduce_tiles", ptr(part), nb, C, ptr(out), stream())
     return out
-
-
-_DEFER_WGRAD = os.environ.get("EGM_DEFER_WGRAD", "1") != "0"
 
 
 class Lazy:
@@ -590,29 +681,6 @@ def _conv_forward(x, ldx, weight, bias, dil, groups, want_stats):
     return y, stats, wd
 
 
-def _wgrad_deferrable(weight):
-    """True when the slab reduction of this weight's gradient may be left to the ONE multi-conv launch at the end of backward: a leaf
-    parameter whose only gradient contribution this is (not when a tensor hook may replace the returned buffer, nor under create_graph:
-    both hand autograd something it copies).  Consumes the conv-use note of the weight: call once per backward of a conv."""
-    return (_DEFER_WGRAD and _sole_conv_use(weight) and weight.is_leaf and weight.grad is None
-            and not weight._backward_hooks and not torch.is_grad_enabled())
-
-
-def _wgrad_run_begin():
-    run = torch._C._current_graph_task_id()
-    if run != _wgrad_run[0]:              # per engine run (an aborted backward never ran its callback: its entries are dead)
-        _pending_wgrad.clear()
-        _pending_slab_launch.clear()
-        _pending_bgrad.clear()
-        Variable._execution_engine.queue_callback(_flush_wgrads)
-        _wgrad_run[0] = run
-
-
-def _queue_wgrad(ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, gw):
-    _wgrad_run_begin()
-    _pending_wgrad.append((ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, weakref.ref(gw), gw.data_ptr()))
-
-
 # ---- 1x1 convolutions: data gradient + weight-gradient slabs in ONE pass over dy and x (csrc/pw_bn.hip, egm_conv1x1_bwd) -----------
 _C1_DESC = struct.Struct("<5Qq6i")
 _C1_MAXC = int(os.environ.get("EGM_CONV1X1_BWD_MAXC", "64"))
@@ -674,47 +742,6 @@ def _conv_grads(x, ldx, dy, weight, wd, dil, groups, Cin, Cout, need_gx, need_gw
     return gx, gw
 
 
-_pending_slab_launch = []                 # deferred slab-kernel launches (argument tuples holding their tensors)
-
-
-merge_wgrads = _Switch("EGM_MERGE_WGRAD", "1",
-                       """Get / set whether the slab kernels of deferred weight gradients are launched together when backward ends (merged
-                       launches).""")
-
-
-_WGRAD_DESC = struct.Struct("<3Q14i")       # egm_conv_wgrad_desc
-_wgrad_names = {}
-
-
-def _wgrad_kernel_of(dt, N, H, W, CinP, CoutP, KH, KW, dil):
-    key = (dt, N, H, W, CinP, CoutP, KH, KW, dil)
-    name = _wgrad_names.get(key)
-    if name is None:
-        buf = ctypes.create_string_buffer(96)
-        lib().cdll.egm_conv_wgrad_kernel_name(dt, N, H, W, CinP, CoutP, KH, KW, dil, ctypes.cast(buf, ctypes.c_void_p), 96)
-        name = _wgrad_names[key] = buf.value
-    return name
-
-
-def _launch_pending_slabs():
-    """The queued slab kernels, in queue order, those of one kernel instantiation four to a launch (egm_conv_wgrad_multi)."""
-    if not _pending_slab_launch:
-        return
-    L, st = lib(), stream()
-    todo = list(_pending_slab_launch)
-    _pending_slab_launch.clear()
-    buckets = {}
-    for ent in todo:
-        dt, x, ldx, gy, ldg, ws, N, H, W, CinP, CoutP, Cin, Cout, KH, KW, dil, groups = ent
-        buckets.setdefault((dt, _wgrad_kernel_of(dt, N, H, W, CinP, CoutP, KH, KW, dil)), []).append(ent)
-    per = 4                                                            # EGM_WGRAD_MULTI_MAX
-    for (dt, _name), ents in buckets.items():
-        for i in range(0, len(ents), per):
-            blob = b"".join(_WGRAD_DESC.pack(x.data_ptr(), gy.data_ptr(), ws.data_ptr(), ldx, ldg, N, H, W, CinP, CoutP, Cin, Cout, KH, KW, dil, groups, 0)
-                            for _dt, x, ldx, gy, ldg, ws, N, H, W, CinP, CoutP, Cin, Cout, KH, KW, dil, groups in ents[i:i + per])
-            L.call("egm_conv_wgrad_multi", dt, blob, len(ents[i:i + per]), st)
-
-
 def _conv_wgrad(x, ldx, gy, ldg, weight, dil, groups, Cin, Cout, defer=None):
     """Weight gradient of one conv; deferred slab reduction when that is safe."""
     N, H, W, CinP = x.shape
@@ -727,10 +754,9 @@ def _conv_wgrad(x, ldx, gy, ldg, weight, dil, groups, Cin, Cout, defer=None):
     if defer is None:                     # (a caller that asked already -- _wgrad_deferrable consumes the use note -- passes the answer)
         defer = _wgrad_deferrable(weight)
     if defer and merge_wgrads.on:
-        _wgrad_run_begin()
         # nothing reads the slabs before the end-of-backward reduction: the launch itself waits for it too and shares launches with the
-        # other deferred ones (_flush_wgrads); x and gy stay alive in the queue entry
-        _pending_slab_launch.append((dt, x, ldx, gy, ldg, ws, N, H, W, CinP, CoutP, Cin, Cout, KH, KW, dil, groups))
+        # other deferred ones (_BackwardRun.launch_slabs); x and gy stay alive in the queue entry
+        _run().slabs.append(_Slab(dt, x, ldx, gy, ldg, ws, N, H, W, CinP, CoutP, Cin, Cout, KH, KW, dil, groups))
     else:
         L.call("egm_conv_wgrad", dt, ptr(x), ldx, ptr(gy), ldg, None if defer else ptr(gw), ptr(ws), N, H, W, CinP, CoutP, Cin, Cout, KH, KW,
                dil, groups, 0, st)
@@ -738,44 +764,6 @@ def _conv_wgrad(x, ldx, gy, ldg, weight, dil, groups, Cin, Cout, defer=None):
         nslab = L.query("egm_conv_wgrad_slabs", dt, N, H, W, CinP, CoutP, KH, KW, dil)
         _queue_wgrad(ws, weight, nslab, KH * KW, CoutP, CinP, Cout, Cin, groups, gw)
     return gw
-
-
-# ---- deferred dz: a BatchNorm backward that computes its incoming gradient from its producer's inputs (csrc/bn_dz_fused.hip) -------
-# The producer's backward (the 1x1 classifier's data gradient; the MCALayer's last step) does not run its kernel: it returns a STAND-IN
-# tensor of the right shape and registers what the BatchNorm backward needs under the stand-in's address; _ConvBN.backward picks it up.
-# Only used where the model code knows the tensor between the two nodes has exactly one consumer (so autograd hands the stand-in through
-# unchanged); an entry nobody consumed by the end of the backward pass is an error, not a silent garbage gradient.
-_DEFERRED_DZ = {}
-
-
-fuse_dz = _Switch("EGM_FUSE_DZ", "1",
-                  """Get / set whether BatchNorm backward computes dz on the fly from the classifier / MCALayer behind it (tests compare both
-                  ways).""")
-
-
-def _check_deferred_dz():
-    _dz_run[0] = None
-    if _DEFERRED_DZ:
-        kinds = [v[1][0] for v in _DEFERRED_DZ.values()]
-        _DEFERRED_DZ.clear()
-        raise RuntimeError(f"egm_unet_amd: deferred BatchNorm gradients {kinds} were never consumed (the tensor between the producer and "
-                           "its BatchNorm had another consumer); call ops.fuse_dz(False)")
-
-
-_dz_run = [None]                          # autograd graph-task id of the backward run whose end-of-run check is queued
-
-
-def _defer_dz(standin, payload):
-    # The check is per ENGINE RUN, not per "registry was empty": the engine drops its callbacks when a backward raises (OOM, launch
-    # error, KeyboardInterrupt), so entries of an aborted run would otherwise stay for the life of the process, pin their payload
-    # tensors, and keep the check from ever being queued again.  A new graph-task id means a new run: stale entries are dropped
-    # (their stand-ins belong to a backward that no longer exists) and this run gets its own check.
-    run = torch._C._current_graph_task_id()
-    if run != _dz_run[0]:
-        _DEFERRED_DZ.clear()
-        Variable._execution_engine.queue_callback(_check_deferred_dz)
-        _dz_run[0] = run
-    _DEFERRED_DZ[standin.data_ptr()] = (standin, payload)          # the stand-in stays alive: its address cannot be recycled meanwhile
 
 
 def _dz_fusable(C):
@@ -1025,7 +1013,7 @@ class _ConvBN(Function):
             return (None,) * 14
         x, weight, wd, y, coef = ctx.saved_tensors
         dil, groups, has_bias, Cin, Cout, act, training = ctx.meta
-        pend = _DEFERRED_DZ.pop(gz.data_ptr(), None) if _DEFERRED_DZ else None      # gz is a stand-in: dz comes from its producer's inputs
+        pend = _take_dz(gz)                                  # not None: gz is a stand-in, dz comes from its producer's inputs
         gz, ldg = _nhwc(gz)
         x, ldx = _nhwc(x)
         CoutP, npix, dt = y.shape[3], _npix(y), dtype_code(x.dtype)
@@ -1777,7 +1765,7 @@ class _UpCat(Function):
     @staticmethod
     def backward(ctx, g):
         N, Hs, Ws, Cs, Hl, Wl, Cl = ctx.shape
-        pend = _DEFERRED_DZ.pop(g.data_ptr(), None) if _DEFERRED_DZ else None
+        pend = _take_dz(g)
         gskip = glow = None
         if pend is not None:                           # the conv behind the concat wrote the two halves of its gradient as dense tensors
             _, ga, gb = pend[1]

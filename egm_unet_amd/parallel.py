@@ -94,7 +94,7 @@ class GradAllReducer:
             self._launch(b)
 
     def _launch(self, b):
-        # conv weight gradients are finished by one deferred multi-conv reduction (ops._flush_wgrads, normally when backward ends):
+        # conv weight gradients are finished by one deferred multi-conv reduction (ops._BackwardRun.flush, normally when backward ends):
         # bring the ones of this bucket up to date before they are gathered
         if self.device.type == "cuda":
             from . import ops

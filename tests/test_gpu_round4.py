@@ -1,4 +1,4 @@
-"""Round-4 GPU tests: robustness of the deferred-gradient registry (ops._defer_dz) and of the gradient helpers the advisor flagged."""
+"""Round-4 GPU tests: robustness of the deferred work of a backward run (ops._BackwardRun) and of the gradient helpers the advisor flagged."""
 import pytest
 import torch
 
@@ -19,8 +19,9 @@ def _model_and_batch(dtype=torch.float32):
 
 def test_aborted_backward_does_not_poison_the_deferred_dz_registry():
     """A backward that raises between a deferring producer (the classifier's data gradient, left to up4's BatchNorm backward) and its
-    consumer leaves an entry in ops._DEFERRED_DZ and the engine never runs the end-of-run check.  The next backward must drop the
-    stale entry, queue its own check, and give the gradients of an undisturbed model."""
+    consumer never runs its end-of-run callback.  The record of that run (ops._BackwardRun: the dz entry, the queued gradients and the
+    tensors they pin) is owned by the engine's graph task and must be gone with it; the next backward gives the gradients of an
+    undisturbed model and leaves nothing behind either."""
     from egm_unet_amd import ops
     assert ops.fuse_dz()
     ref, x, gl = _model_and_batch()
@@ -33,15 +34,25 @@ def test_aborted_backward_does_not_poison_the_deferred_dz_registry():
         raise RuntimeError("boom")
     # AccumulateGrad (and its hooks) of the classifier weight runs right after the classifier's backward, before up4's BatchNorm backward
     h = m.out_conv[0].weight.register_hook(boom)
-    with pytest.raises(RuntimeError, match="boom"):
-        m(x)["out"].backward(gl)
+    deferred, orig = [], ops._defer_dz
+
+    def spy(standin, payload):
+        deferred.append(payload[0])
+        return orig(standin, payload)
+    ops._defer_dz = spy
+    try:
+        with pytest.raises(RuntimeError, match="boom"):
+            m(x)["out"].backward(gl)
+    finally:
+        ops._defer_dz = orig
     h.remove()
     torch.cuda.synchronize()
-    assert ops._DEFERRED_DZ, "the aborted run was expected to leave its deferred entry behind (otherwise this test checks nothing)"
+    assert deferred, "the aborted run was expected to register a deferred entry before it raised (otherwise this test checks nothing)"
+    assert not ops._runs, "the record of the aborted run is still alive: something besides the engine's graph task holds it"
     m.zero_grad(set_to_none=True)
     m(x)["out"].backward(gl)
     torch.cuda.synchronize()
-    assert not ops._DEFERRED_DZ and ops._dz_run[0] is None
+    assert not ops._runs
     got = {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
     assert got.keys() == want.keys()
     for k in want:
@@ -85,7 +96,7 @@ def test_merged_slab_launches_give_the_gradients_of_separate_launches(dtype):
             m, x, gl = _model_and_batch(dtype)
             m(x)["out"].backward(gl)
             torch.cuda.synchronize()
-            assert not ops._pending_slab_launch and not ops._pending_wgrad
+            assert not ops._runs                                    # no run record is left: nothing stays in any of its queues
             got[merged] = {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}
     finally:
         ops.merge_wgrads(default)
@@ -134,18 +145,18 @@ def test_deferred_bias_gradients_equal_the_per_layer_reductions(dtype):
             ops.defer_bgrads(deferred)
             m, x, gl = _model_and_batch(dtype)
             seen = []
-            orig = ops._flush_bgrads
+            orig = ops._BackwardRun.flush_bgrads
 
-            def spy(ready_only=False, _seen=seen, _orig=orig):
-                _seen.append(len(ops._pending_bgrad))
-                return _orig(ready_only)
-            ops._flush_bgrads = spy
+            def spy(run, ready_only=False, _seen=seen, _orig=orig):
+                _seen.append(len(run.bgrads))
+                return _orig(run, ready_only)
+            ops._BackwardRun.flush_bgrads = spy
             try:
                 m(x)["out"].backward(gl)
             finally:
-                ops._flush_bgrads = orig
+                ops._BackwardRun.flush_bgrads = orig
             torch.cuda.synchronize()
-            assert not ops._pending_bgrad
+            assert not ops._runs
             queued[deferred] = max(seen) if seen else 0
             got[deferred] = {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}
     finally:
@@ -154,6 +165,120 @@ def test_deferred_bias_gradients_equal_the_per_layer_reductions(dtype):
     assert got[True].keys() == got[False].keys() and len(got[True]) > 100
     for k in got[True]:
         assert torch.equal(got[True][k], got[False][k]), k
+
+
+def _seeded(module, seed):
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, p in module.named_parameters():
+            v = torch.randn(p.shape, generator=g) * 0.1
+            p.copy_(v + 1.0 if p.dim() == 1 and name.endswith("weight") else v)    # BatchNorm scales around 1
+    return module.to(DEV).train()
+
+
+class _BiasedConv(torch.nn.Conv2d):
+    """ops.conv2d with a bias and no BatchNorm behind it."""
+
+    def forward(self, x):
+        from egm_unet_amd import ops
+        return ops.conv2d(x, self.weight, self.bias)
+
+
+def _grads(modules, x):
+    out = {f"{i}.{k}": p.grad for i, m in enumerate(modules) for k, p in m.named_parameters()}
+    out["x"] = x.grad
+    return out
+
+
+def _nested_function_case(dtype, nested, seen_inside=None):
+    """dc1 -> [identity Function] -> dc2 -> biased conv, backward from a seeded gradient; the identity's backward (nested=True) runs
+    the backward of an independent graph (one biased conv, forwarded once before) inside the outer one; nested=False leaves the identity
+    out and runs that backward on its own.  -> gradients of every parameter and of both inputs."""
+    from egm_unet_amd import ops, unet
+    g = torch.Generator().manual_seed(33)
+    x = torch.randn(2, 24, 24, 8, generator=g).to(DEV).to(dtype).requires_grad_()
+    go = torch.randn(2, 24, 24, 8, generator=g).to(DEV).to(dtype)
+    xi = torch.randn(2, 16, 16, 8, generator=g).to(DEV).to(dtype).requires_grad_()
+    gi = torch.randn(2, 16, 16, 16, generator=g).to(DEV).to(dtype)
+    dc1, dc2 = _seeded(unet.DoubleConv(8, 16), 1), _seeded(unet.DoubleConv(16, 16), 2)
+    head, inner = _seeded(_BiasedConv(16, 8, 3, padding=1), 3), _seeded(_BiasedConv(8, 16, 3, padding=1), 4)
+    yi = inner(xi)
+
+    class Identity(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, t):
+            return t.view_as(t)
+
+        @staticmethod
+        def backward(ctx, gt):
+            if seen_inside is not None:                 # the outer run's record as the inner run finds it
+                run = ops._run(create=False)
+                seen_inside.append(None if run is None else (run.id, len(run.slabs), len(run.wgrads), len(run.bgrads)))
+            yi.backward(gi)
+            return gt
+
+    h = dc1(x)
+    head(dc2(Identity.apply(h) if nested else h)).backward(go)
+    if not nested:
+        yi.backward(gi)
+    torch.cuda.synchronize()
+    got = _grads([dc1, dc2, head, inner], x)
+    got["xi"] = xi.grad
+    return got
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_backward_nested_in_a_function_backward_keeps_the_outer_deferred_gradients(dtype):
+    """A Function whose backward runs another backward: the inner run has a record of deferred work of its own and must not drop what
+    the outer run queued before it (dc2's and the head's slabs, reductions, the head's bias sum) nor what it queues afterwards (dc1's).
+    Same kernels on the same operands, only in launches of the inner run's own: every gradient bit-equal to the two backwards run apart.
+    Two records for the one outer backward(), both with deferred work, so nothing here passes by taking the immediate path."""
+    from egm_unet_amd import ops
+    want = _nested_function_case(dtype, nested=False)
+    finished, inside, orig = [], [], ops._BackwardRun.finish
+
+    def spy(run):
+        finished.append((run.id, len(run.slabs), len(run.wgrads), len(run.bgrads)))
+        return orig(run)
+    ops._BackwardRun.finish = spy
+    try:
+        got = _nested_function_case(dtype, nested=True, seen_inside=inside)
+    finally:
+        ops._BackwardRun.finish = orig
+    assert not ops._runs
+    assert len(finished) == 2 and len(inside) == 1, (finished, inside)
+    (inner_id, *inner_q), (outer_id, *outer_q) = finished
+    assert inner_id != outer_id and inside[0] is not None and inside[0][0] == outer_id
+    assert inner_q == [1, 1, 1], inner_q                            # the inner conv's slab launch, reduction and bias sum
+    assert list(inside[0][1:]) == [3, 3, 1], inside                   # queued by the outer run before the inner one started
+    assert outer_q == [5, 5, 1], outer_q                            # ... still there at its end, with dc1's two convs added
+    assert got.keys() == want.keys() and len(got) == 18
+    for k in want:
+        assert got[k] is not None and torch.equal(got[k], want[k]), k
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_reentrant_checkpoint_gives_the_gradients_of_the_plain_chain(dtype):
+    """dc3(checkpoint(dc2, dc1(x), use_reentrant=True)) against dc3(dc2(dc1(x))): the checkpoint recomputes dc2 and runs its backward
+    as a run nested in the outer one.  Output, every parameter gradient and the input gradient are bit-equal.  (The checkpointed
+    block's forward runs twice, so its BatchNorm running statistics move twice: they are not compared.)"""
+    from torch.utils.checkpoint import checkpoint
+    from egm_unet_amd import ops, unet
+    res = {}
+    for ckpt in (False, True):
+        g = torch.Generator().manual_seed(34)
+        x = torch.randn(2, 24, 24, 8, generator=g).to(DEV).to(dtype).requires_grad_()
+        go = torch.randn(2, 24, 24, 8, generator=g).to(DEV).to(dtype)
+        dc1, dc2, dc3 = (_seeded(unet.DoubleConv(8, 16), 5), _seeded(unet.DoubleConv(16, 16), 6), _seeded(unet.DoubleConv(16, 8), 7))
+        h = dc1(x)
+        out = dc3(checkpoint(dc2, h, use_reentrant=True) if ckpt else dc2(h))
+        out.backward(go)
+        torch.cuda.synchronize()
+        assert not ops._runs
+        res[ckpt] = dict(_grads([dc1, dc2, dc3], x), out=out.detach())
+    assert res[True].keys() == res[False].keys() and len(res[True]) == 20
+    for k in res[False]:
+        assert res[True][k] is not None and torch.equal(res[True][k], res[False][k]), k
 
 
 def test_bias_grad_multi_equals_channel_sums_and_refuses_bad_calls():
