@@ -11,6 +11,7 @@
 // Logits/gradients are fp32 NCHW (the module boundary), targets int64 [N,H,W].  One lane per pixel: all reads of a
 // wave are contiguous in x.  Reductions: per-block partials with plain stores, summed in double in fixed order.
 #include "common.h"
+#include "ensemble_fuse.h"
 #include <stdlib.h>
 
 namespace {
@@ -309,32 +310,14 @@ __global__ void metrics_finalize_kernel(const unsigned long long* __restrict__ h
 // fused = bilinear(clip_logits -> HxW, align_corners=False) + alpha * unet_logits ; prediction = argmax_c fused.
 // One lane per output pixel; the alpha grid search evaluates every alpha of the grid in the same pass and accumulates one
 // confusion matrix per alpha (LDS pre-aggregation, integer atomics).
-__device__ __forceinline__ void bilin_src(int dst, int in_size, int out_size, int& i0, int& i1, float& w1) {
-    const float scale = (float)in_size / (float)out_size;
-    float src = ((float)dst + 0.5f) * scale - 0.5f;            // torch area_pixel_compute_source_index, align_corners=False
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src; if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    w1 = src - (float)i0;
-}
-__device__ __forceinline__ float bilin_at(const float* __restrict__ m, int wc, int y0, int y1, float wy, int x0, int x1, float wx) {
-    const float a = m[(long long)y0 * wc + x0], b = m[(long long)y0 * wc + x1], c = m[(long long)y1 * wc + x0], d = m[(long long)y1 * wc + x1];
-    return (1.f - wy) * ((1.f - wx) * a + wx * b) + wy * ((1.f - wx) * c + wx * d);
-}
+// (bilin_src, bilin_at and the fused argmax live in ensemble_fuse.h: egm_ensemble_mask_u8 evaluates the same expression)
 // pred[n][y][x] = argmax_c (up(clip)[n][c] + alpha * unet[n][c]); fused (optional) receives the fused logits
 __global__ void ensemble_fuse_kernel(const float* __restrict__ clip, const float* __restrict__ unet, float alpha, int N, int C, int hc, int wc,
                                      int H, int W, long long* __restrict__ pred, float* __restrict__ fused) {
     const long long HW = (long long)H * W, total = (long long)N * HW;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int x = (int)(i % W), y = (int)((i / W) % H), n = (int)(i / HW);
-        int y0, y1, x0, x1; float wy, wx;
-        bilin_src(y, hc, H, y0, y1, wy); bilin_src(x, wc, W, x0, x1, wx);
-        int best = 0; float m = -INFINITY;
-        for (int c = 0; c < C; ++c) {
-            const float v = bilin_at(clip + ((long long)n * C + c) * hc * wc, wc, y0, y1, wy, x0, x1, wx) + alpha * unet[((long long)n * C + c) * HW + (i - n * HW)];
-            if (fused) fused[((long long)n * C + c) * HW + (i - n * HW)] = v;
-            if (v > m) { m = v; best = c; }
-        }
+        const int best = ensemble_fused_argmax(clip, unet, alpha, n, C, hc, wc, H, W, y, x, fused);
         if (pred) pred[i] = best;
     }
 }

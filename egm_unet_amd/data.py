@@ -31,18 +31,16 @@ def _resize_output_size(w, h, size):
     return int(size * w / h), size
 
 
-def _bilinear_tables(in_size, out_size, device):
-    key = ("bil", in_size, out_size, device)
-    hit = _table_cache.get(key)
-    if hit is not None:
-        return hit
+def _triangle_filter(in_size, out_size):
+    """Pillow's / ATen's antialiased triangle filter in float64: (bounds int32 [out, 2] = (xmin, xsize), weights float64 [out, ksize]
+    normalised to sum 1, ksize)."""
     scale = filterscale = in_size / out_size
     if filterscale < 1.0:
         filterscale = 1.0
     support = filterscale                                    # triangle filter: support 1
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), dtype=np.int32)
-    coefs = np.zeros((out_size, ksize), dtype=np.int32)
+    kk = np.zeros((out_size, ksize), dtype=np.float64)
     ss = 1.0 / filterscale
     for xx in range(out_size):
         center = (xx + 0.5) * scale
@@ -55,10 +53,75 @@ def _bilinear_tables(in_size, out_size, device):
             k.append(w)
             ww += w
         for x in range(xmax):
-            kv = k[x] / ww if ww != 0.0 else k[x]
-            coefs[xx, x] = int(kv * (1 << _PRECISION_BITS) + (-0.5 if kv < 0 else 0.5))
+            kk[xx, x] = k[x] / ww if ww != 0.0 else k[x]
         bounds[xx] = (xmin, xmax)
+    return bounds, kk, ksize
+
+
+def _bilinear_tables(in_size, out_size, device):
+    key = ("bil", in_size, out_size, device)
+    hit = _table_cache.get(key)
+    if hit is not None:
+        return hit
+    bounds, kk, ksize = _triangle_filter(in_size, out_size)
+    coefs = np.zeros((out_size, ksize), dtype=np.int32)
+    for xx in range(out_size):
+        for x in range(bounds[xx, 1]):
+            kv = kk[xx, x]
+            coefs[xx, x] = int(kv * (1 << _PRECISION_BITS) + (-0.5 if kv < 0 else 0.5))
     out = (torch.from_numpy(bounds).to(device), torch.from_numpy(coefs).to(device), ksize)
+    _table_cache[key] = out
+    return out
+
+
+def _two_tap_filter(in_size, out_size):
+    """Plain bilinear (align_corners=False, no antialias) as a filter table: src = max((i + .5) * scale - .5, 0), taps floor(src) and
+    min(floor(src) + 1, in - 1) with weights (1 - l, l); at the last pixel the two taps coincide and become one of weight 1."""
+    scale = in_size / out_size
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    kk = np.zeros((out_size, 2), dtype=np.float64)
+    for i in range(out_size):
+        src = max((i + 0.5) * scale - 0.5, 0.0)
+        i0 = min(int(math.floor(src)), in_size - 1)
+        lam = src - i0
+        if i0 + 1 <= in_size - 1:
+            bounds[i] = (i0, 2)
+            kk[i] = (1.0 - lam, lam)
+        else:
+            bounds[i] = (i0, 1)
+            kk[i, 0] = 1.0
+    return bounds, kk, 2
+
+
+def float_filter_tables(in_size, out_size, antialias=True, device="cpu"):
+    """The separable filter of F.interpolate(mode="bilinear", align_corners=False, antialias=antialias) along one axis, computed in
+    float64: (bounds int32 [out, 2] = (first tap, tap count), weights fp32 [out, ksize], ksize).  egm_resample_u8's contract with fp32
+    weights; what clip_preprocess hands to egm_clip_preprocess_u8."""
+    key = ("flt", in_size, out_size, bool(antialias), str(device))
+    hit = _table_cache.get(key)
+    if hit is not None:
+        return hit
+    bounds, kk, ksize = _triangle_filter(in_size, out_size) if antialias else _two_tap_filter(in_size, out_size)
+    out = (torch.from_numpy(bounds).to(device), torch.from_numpy(kk.astype(np.float32)).to(device), ksize)
+    _table_cache[key] = out
+    return out
+
+
+def cv_nearest_table(src, dst, device="cpu"):
+    """Source index per destination index of cv2.resize(..., interpolation=cv2.INTER_NEAREST) along one axis of src -> dst pixels:
+    idx[x] = min(floor(x * (1.0 / (dst / src))), src - 1) in float64, in exactly that form (OpenCV computes inv_scale = dst / src and then
+    1. / inv_scale; floor(x * src / dst) differs from it for some (src, dst) pairs).  int32 [dst].
+    The rule is restated from OpenCV's source (resizeNN); it has NOT been checked against a cv2 build."""
+    key = ("cvnn", src, dst, str(device))
+    hit = _table_cache.get(key)
+    if hit is not None:
+        return hit
+    inv_scale = dst / src
+    ifx = 1.0 / inv_scale
+    idx = np.zeros(dst, dtype=np.int32)
+    for x in range(dst):
+        idx[x] = min(int(math.floor(x * ifx)), src - 1)
+    out = torch.from_numpy(idx).to(device)
     _table_cache[key] = out
     return out
 
@@ -134,6 +197,29 @@ def augment(img_u8, mask_u8, hflip, vflip, top, left, crop_h, crop_w, mean, std,
     lib().call("egm_augment_u8", ptr(img), ptr(mask), H, W, int(bool(hflip)), int(bool(vflip)), top, left, crop_h, crop_w,
                ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p), ptr(out_img), ptr(out_target), oh, ow, stream())
     return out_img, out_target
+
+
+def clip_preprocess(img_u8, size=(352, 352), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), antialias=True, out=None):
+    """predict_CLIPseg.py:447-451 (clip_transform: ToTensor -> Normalize -> Resize((352, 352)) of the float tensor) from the decoded
+    uint8 photo [H, W, 3] on the device -> fp32 [1, 3, Sh, Sw], i.e. F.interpolate(normalised, size, mode="bilinear",
+    align_corners=False, antialias=antialias).  antialias=True is torchvision's current default for tensors; False is what older
+    torchvision did.  out: an optional fp32 [1, 3, Sh, Sw] (or [3, Sh, Sw]) buffer to write into."""
+    img = _check_u8(img_u8, 3)
+    H, W, C = img.shape
+    if C != 3:
+        raise RuntimeError("egm_unet_amd.data.clip_preprocess: RGB images ([H,W,3] uint8) expected")
+    Sh, Sw = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    xb, xw, xk = float_filter_tables(W, Sw, antialias, img.device)
+    yb, yw, yk = float_filter_tables(H, Sh, antialias, img.device)
+    if out is None:
+        out = torch.empty((1, 3, Sh, Sw), dtype=torch.float32, device=img.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 3 * Sh * Sw):
+        raise RuntimeError("egm_unet_amd.data.clip_preprocess: out must be a contiguous CUDA float32 tensor of 3 * Sh * Sw elements")
+    tmp = torch.empty((3, H, Sw), dtype=torch.float32, device=img.device)
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    lib().call("egm_clip_preprocess_u8", ptr(img), H, W, ptr(out), Sh, Sw, ptr(xb), ptr(xw), xk, ptr(yb), ptr(yw), yk,
+               ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p), ptr(tmp), stream())
+    return out.view(1, 3, Sh, Sw)
 
 
 class SegmentationPresetTrain:

@@ -136,6 +136,12 @@ class Predictor:
             self._stamp = stamp
         ops.claim_prepack(self._prepack)
 
+    def refresh(self):
+        """Bring the folded packs up to date with the model's parameters and buffers now (what every call does first).  For callers that
+        run this predictor's forward inside a graph of their own: call it before each replay, outside the graph."""
+        with torch.no_grad():
+            self._refresh()
+
     # ---- forward
     def _forward(self, x):
         """One folded eval forward of the model (eager, or being captured): training flags off, this predictor's packs swapped in."""

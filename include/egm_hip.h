@@ -648,6 +648,28 @@ int egm_augment_u8(const void* img_hwc3, const void* mask_hw, int H, int W, int 
                    int crop_w, const float* mean3_host, const float* std3_host, float* out_img_chw, long long* out_target,
                    int out_h, int out_w, egm_stream_t s);
 
+/* ---- per-image ensemble pipeline: the two ends around the models (predict_CLIPseg.py:447-451, :525-534) ------------------
+ * egm_clip_preprocess_u8: ToTensor -> Normalize(mean, std) -> Resize((Sh, Sw)) of the float tensor, i.e.
+ *   F.interpolate(x, (Sh, Sw), mode="bilinear", align_corners=False, antialias=A), from the decoded uint8 photo [H][W][3] to fp32
+ *   [3][Sh][Sw].  The separable filter comes from the caller as for egm_resample_u8, with fp32 weights: per output index
+ *   bounds [out][2] = (b0, n) int32 and weights [out][ksize] fp32 summing to one (x tables over W -> Sw, y tables over H -> Sh; the
+ *   antialiased triangle rule or the two taps of plain bilinear, one kernel serves both).
+ *   out = ((sum_i wy[i] * sum_j wx[j] * img[b0y+i][b0x+j]) / 255 - mean) / std: the filter runs on the bytes and the result is
+ *   normalised, which differs from normalising first by rounding only.  Two launches: horizontal into tmp_chw (fp32 [3][H][Sw],
+ *   supplied by the caller), then vertical.  mean3/std3 are HOST pointers (3 floats each).  ksize <= 64 per
+ *   axis and a horizontal reduction whose staging fits 64 KiB of LDS, otherwise EGM_ERR_ARG.
+ * egm_ensemble_mask_u8: out[n][y][x] = lut[argmax_c fused[n][c][yidx[y]][xidx[x]]] (lut: 256 bytes, NULL = the class id), uint8
+ *   [N][H0][W0], with fused = bilinear(clip_logits -> HxW, align_corners=False) + alpha * unet_logits evaluated by the expression of
+ *   egm_ensemble_fuse (csrc/ensemble_fuse.h), ties to the lowest class: bit-identical to egm_ensemble_fuse followed by a gather.
+ *   yidx [H0] / xidx [W0] int32: the nearest-neighbour tables of cv2.resize(pred, (W0, H0), INTER_NEAREST).  alpha_dev is a DEVICE
+ *   scalar, so a captured graph follows a new alpha. */
+int egm_clip_preprocess_u8(const void* img_hwc3, int H, int W, float* out_chw, int Sh, int Sw, const int* xbounds, const float* xweights,
+                           int xksize, const int* ybounds, const float* yweights, int yksize, const float* mean3_host,
+                           const float* std3_host, float* tmp_chw, egm_stream_t s);
+int egm_ensemble_mask_u8(const float* clip_logits, const float* unet_logits, const float* alpha_dev, int N, int C, int hc, int wc, int H,
+                         int W, const int* yidx, const int* xidx, const unsigned char* lut, unsigned char* out, int H0, int W0,
+                         egm_stream_t s);
+
 /* ---- CLIPSeg decoder training (models/clipseg.py:380-420,452-496; experiments/phrasecut.yaml:1-47) ------------------
  * The backward matrix products run on egm_gemm over transposed copies (egm_transpose: dst[b][c][r] = src[b][r][c]).
  * egm_relu_bwd: dst = g where out > 0.  egm_softmax_bwd_rows: dS = P*(dP - sum_j dP_j P_j)*alpha per row (P storage type,

@@ -1,0 +1,121 @@
+"""predict_CLIPseg.py per image, decoded uint8 photo on the device -> uint8 mask at the photo's size: the path composed from the public
+pieces (what a user could write before EnsemblePredictor existed) against EnsemblePredictor.  ms per call (CUDA events around the Python
+call, median of --iters calls after warm-up), kernel nodes of the captured graph, and the clip-preprocess kernels' time and achieved
+bytes/s against the photo's size.  GRFBUNet(3, 2, base_c=32) bf16 + CLIPDensePredT("ViT-B/16", reduce_dim=64) bf16, seeded weights,
+synthetic photos.  One JSON line per (size, repeat).
+
+    python tools/egm_ensemble_bench.py [--iters 50] [--sizes 768x1024,3000x4000] [--repeats 3] [--step-timeout 240]
+    rocprofv3 --kernel-trace --stats -- python tools/egm_ensemble_bench.py --child 768x1024 --profile-one ens     # or composed: 12 calls
+
+Every size runs in a child process of its own under a time limit; a child that fails ends the run."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+UMEAN, USTD = (0.709, 0.381, 0.224), (0.127, 0.079, 0.043)
+CMEAN, CSTD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def timed(fn, iters, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def child(H0, W0, iters, repeats, profile_one=None):
+    import torch.nn.functional as F
+    from egm_unet_amd import GRFBUNet, data
+    from egm_unet_amd.clipseg import CLIPDensePredT
+    from egm_unet_amd.ensemble import EnsemblePredictor, fuse_predict
+    from egm_unet_amd.infer import Predictor
+    from egm_infer_bench import kernel_nodes
+    dev, dt = "cuda", torch.bfloat16
+    torch.manual_seed(0)
+    unet = GRFBUNet(3, 2, base_c=32).to(dev).eval()
+    clipseg = CLIPDensePredT("ViT-B/16", reduce_dim=64, clip_weights="").to(dev).eval().set_compute_dtype(dt)
+    cond = torch.randn(2, 512, generator=torch.Generator().manual_seed(1)).to(dev)
+    img = torch.randint(0, 256, (H0, W0, 3), generator=torch.Generator().manual_seed(2), dtype=torch.uint8).to(dev)
+    pred = Predictor(unet, dtype=dt)                                   # with its own graph
+    lut = torch.tensor([0, 255], dtype=torch.uint8, device=dev)
+    mean, std = torch.tensor(CMEAN, device=dev).view(1, 3, 1, 1), torch.tensor(CSTD, device=dev).view(1, 3, 1, 1)
+    state = {}
+
+    def composed():
+        with torch.no_grad():
+            r = data.resize_bilinear(img, 565)
+            x, _ = data.augment(r, None, False, False, 0, 0, r.shape[0], r.shape[1], UMEAN, USTD)
+            u = pred(x[None])["out"]
+            xc = F.interpolate((img.permute(2, 0, 1)[None].float() / 255 - mean) / std, (352, 352), mode="bilinear", align_corners=False,
+                               antialias=True)
+            c = clipseg.forward_multi(xc, cond)
+            p = fuse_predict(c, u, 0.5)
+            if "yi" not in state:
+                state["yi"] = data.cv_nearest_table(p.shape[1], H0, dev).long()
+                state["xi"] = data.cv_nearest_table(p.shape[2], W0, dev).long()
+            return lut[p[0][state["yi"]][:, state["xi"]]]
+
+    ens = EnsemblePredictor(unet, clipseg, cond, alpha=0.5, dtype=dt)
+    if profile_one:                                                    # 12 calls of one kind and nothing else
+        fn = composed if profile_one == "composed" else (lambda: ens(img))
+        for _ in range(12):
+            fn()
+        torch.cuda.synchronize()
+        return
+    # the clip-preprocess kernels alone (both launches), events around the call
+    out = torch.empty((1, 3, 352, 352), dtype=torch.float32, device=dev)
+    for rep in range(repeats):
+        comp_ms = timed(composed, iters)
+        ens_ms = timed(lambda: ens(img), iters)
+        pre_ms = timed(lambda: data.clip_preprocess(img, (352, 352), CMEAN, CSTD, out=out), iters)
+        g = ens.captured_graph((H0, W0))
+        print(json.dumps({"photo": [H0, W0], "repeat": rep, "composed_ms": round(comp_ms, 3), "ensemble_ms": round(ens_ms, 3),
+                          "speedup": round(comp_ms / ens_ms, 2), "graph_kernel_nodes": kernel_nodes(g) if g is not None else None,
+                          "clip_preprocess_ms": round(pre_ms, 4), "clip_preprocess_share": round(pre_ms / ens_ms, 3),
+                          "clip_preprocess_GBps_of_photo": round(H0 * W0 * 3 / (pre_ms * 1e-3) / 1e9, 1)}), flush=True)
+    same = float((composed() == ens(img)).float().mean())
+    print(json.dumps({"photo": [H0, W0], "mask_agreement_with_composed": round(same, 6)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--sizes", default="768x1024,3000x4000")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--step-timeout", type=int, default=240, help="seconds per size (one child process each)")
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--profile-one", default=None, choices=["ens", "composed"], help="with --child: 12 calls of one kind (for rocprofv3)")
+    args = ap.parse_args()
+    if args.child:
+        H0, W0 = (int(v) for v in args.child.split("x"))
+        child(H0, W0, args.iters, args.repeats, args.profile_one)
+        return
+    for size in args.sizes.split(","):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", size, "--iters", str(args.iters), "--repeats", str(args.repeats)]
+        try:
+            rc = subprocess.run(cmd, timeout=args.step_timeout).returncode
+        except subprocess.TimeoutExpired:
+            print(json.dumps({"photo": size, "error": f"no result within {args.step_timeout} s"}), flush=True)
+            sys.exit(124)
+        if rc != 0:                                      # nothing more is started on the device after a failed step
+            print(json.dumps({"photo": size, "error": f"exit status {rc}"}), flush=True)
+            sys.exit(rc if rc > 0 else 1)
+
+
+if __name__ == "__main__":
+    main()
