@@ -245,6 +245,18 @@ def bcast_add_(a, r):
     return a
 
 
+def bcast_add(a, r):
+    """a [B*K, L, D] + r [B, L, D] broadcast over the K prompts of each image -> a new [B*K, L, D] (bcast_add_ out of place, same bits)."""
+    B, L, D = r.shape
+    K = a.shape[0] // B
+    if a.shape != (B * K, L, D):
+        raise RuntimeError(f"bcast_add: a {tuple(a.shape)} is not [B*K, L, D] for r {tuple(r.shape)}")
+    a, r = a.contiguous(), r.contiguous()
+    out = torch.empty_like(a)
+    lib().call("egm_bcast_add_out", dtype_code(a.dtype), ptr(a), ptr(r), ptr(out), B, K, L, D, stream())
+    return out
+
+
 def sigmoid_affine_(x, scale, offset):
     """x fp32 [N, C, H, W] <- offset + scale[c] * sigmoid(x) in place (scale fp32 [C] on x's device); returns x."""
     N, C, H, W = x.shape

@@ -252,6 +252,52 @@ class FilmFn(Function):
         return da, dmul, dadd
 
 
+class FilmFanoutFn(Function):
+    """The FiLM at cond_layer for K prompts on each of B images (CLIPDenseBase.forward_multi_train): r [B, L, D], mul / add [K, D] ->
+    [B*K, L, D] with out[b*K + k] = mul[k] * r[b] + add[k] (b-major).  Backward: one pass over g (egm_film_fanout_bwd) gives
+    dr = sum_k g * mul[k] and, through per-workgroup partials summed in fixed order, dmul = sum_{b,t} g * r and dadd = sum_{b,t} g."""
+
+    @staticmethod
+    def forward(ctx, r, mul, add):
+        r, mul, add = r.contiguous(), mul.contiguous(), add.contiguous()
+        ctx.save_for_backward(r, mul)
+        return O.film_fanout(r, mul, add)
+
+    @staticmethod
+    def backward(ctx, g):
+        r, mul = ctx.saved_tensors
+        (B, L, D), K, L_ = r.shape, mul.shape[0], lib()
+        g = g.contiguous()
+        code = dtype_code(r.dtype)
+        ws = torch.empty(L_.query("egm_film_fanout_bwd_workspace", code, B, K, L, D) // 4, dtype=torch.float32, device=r.device)
+        dr, dmul, dadd = torch.empty_like(r), torch.empty_like(mul), torch.empty_like(mul)
+        L_.call("egm_film_fanout_bwd", code, ptr(g), ptr(r), ptr(mul), ptr(dr), ptr(dmul), ptr(dadd), ptr(ws), B, K, L, D, stream())
+        need = ctx.needs_input_grad
+        return dr if need[0] else None, dmul if need[1] else None, dadd if need[2] else None
+
+
+class BcastAddFn(Function):
+    """a [B*K, L, D] + r [B, L, D] broadcast over the K prompts of each image: reduce_i(act_i) of the layers behind cond_layer, computed on
+    B*L rows.  Out of place (a is the saved output of the LayerNorm in front).  Backward: g to a as it is, sum_k g to r -- so the
+    weight and bias gradients of the linear that made r are products over B*L rows."""
+
+    @staticmethod
+    def forward(ctx, a, r):
+        ctx.B = r.shape[0]
+        return O.bcast_add(a, r)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        BK, L, D = g.shape
+        B = ctx.B
+        dr = None
+        if ctx.needs_input_grad[1]:
+            dr = torch.empty((B, L, D), dtype=g.dtype, device=g.device)
+            lib().call("egm_group_sum", dtype_code(g.dtype), ptr(g), ptr(dr), B, BK // B, L, D, stream())
+        return (g if ctx.needs_input_grad[0] else None), dr
+
+
 class TransConvFn(Function):
     """ConvTranspose2d(rd -> 1, kernel = stride = P) on the token grid (models/clipseg.py:489-491): per-token GEMM + pixel shuffle.
     a [B, Ltot, rd] (token 0 = cls, dropped), weight [rd, 1, P, P], bias [1] -> fp32 [B, 1, g*P, g*P]"""

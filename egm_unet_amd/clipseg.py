@@ -131,6 +131,25 @@ class CLIPDenseBase(nn.Module):
             B, K = x_inp.shape[0], cond.shape[0]
             return out.view(B, K, out.shape[-2], out.shape[-1])
 
+    def forward_multi_train(self, inp_image, conditionals):
+        """forward_multi for decoder training: the same inputs -> fp32 logits [B, K, H', W'] with out[b, k] = self(inp_image[b:b+1],
+        prompt k)[0][0, 0] in train mode, differentiable in the decoder parameters (their gradients equal those of the repeat form, the
+        image fed once per prompt); the conditionals are constants.  The frozen backbone runs once per image under no_grad and stops
+        after the last layer the decoder reads; the decoder's dropout draws its masks for the B*K sequences.  In eval mode or with
+        autograd off this is forward_multi.  Loss: clip.train_ops.bce_with_logits(out, target [B, K, H', W'])."""
+        if not (self.training and torch.is_grad_enabled()):
+            return self.forward_multi(inp_image, conditionals)
+        dev = self.model.positional_embedding.device
+        x_inp = inp_image.to(dev)
+        if x_inp.ndim != 4:
+            raise ValueError(f"forward_multi_train: inp_image must be [B, 3, H, W], got {tuple(x_inp.shape)}")
+        with torch.no_grad():
+            cond = self._multi_cond(conditionals)
+            condT = self._cond_in_dtype(cond)
+        out = self._decode_multi_train(x_inp, condT)
+        B, K = x_inp.shape[0], cond.shape[0]
+        return out.view(B, K, out.shape[-2], out.shape[-1])
+
     def _multi_cond(self, conditionals):
         """The K conditional vectors [K, 512] fp32 of forward_multi (get_cond_vec's forms, K in place of the batch size)."""
         width = self.film_mul.in_features
@@ -334,6 +353,34 @@ class CLIPDensePredT(CLIPDenseBase):
         return self._trans_conv_eval(a)
 
 
+    def _decode_multi_train(self, x_inp, condT):
+        """_decode_multi on the autograd operators of clip/train_ops.py: the reduces stay products over B*L rows in both directions
+        (FilmFanoutFn / BcastAddFn hand them the gradients summed over the prompts), encoder layers and heads run on B*K sequences."""
+        from .clip import train_ops as T
+        K = condT.shape[0]
+        with torch.no_grad():
+            _, acts_all = self._visual_run(x_inp, extract_layers=[0] + list(self.extract_layers), stop_after=max(self.extract_layers))
+        acts = acts_all[1:]
+        acts = acts[::-1] if not self.rev_activations else acts
+        a, fanned = None, False
+        for i, (act, blk, red) in enumerate(zip(acts, self.blocks, self.reduces)):
+            if not fanned:
+                a = T.linear(act.detach(), red.weight, red.bias, residual=a)
+                if i == self.cond_layer:
+                    a = T.FilmFanoutFn.apply(a, T.linear(condT, self.film_mul.weight, self.film_mul.bias),
+                                             T.linear(condT, self.film_add.weight, self.film_add.bias))
+                    fanned = True
+            else:
+                a = T.BcastAddFn.apply(a, T.linear(act.detach(), red.weight, red.bias))
+            a = self._encoder_layer_train(blk, a)
+        if not fanned:                                               # cond_layer behind the last layer: no FiLM, every prompt alike
+            one = torch.ones((K, a.shape[-1]), dtype=a.dtype, device=a.device)
+            a = T.FilmFanoutFn.apply(a, one, torch.zeros_like(one))
+        if self.complex_trans_conv:
+            return T.refine(a, self.trans_conv)
+        return T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
+
+
 class CLIPDensePredTMasked(CLIPDensePredT):
     """CLIPSeg conditioned on a support image + its segmentation (models/clipseg.py:500-525): the conditional vector is the CLIP
     image feature of the support image, computed with the class token's attention restricted to the masked region in every layer."""
@@ -437,6 +484,19 @@ class CLIPDenseBaseline(CLIPDenseBase):
         a = O.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
         a = O.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
         return self._trans_conv_eval(a)
+
+    def _decode_multi_train(self, x_inp, condT):
+        """forward_multi_train's head on the composed autograd operators (either dtype): reduce on B*L rows, the FiLM fan-out, then
+        reduce2 / trans_conv on B*K sequences."""
+        from .clip import train_ops as T
+        with torch.no_grad():
+            _, acts = self._visual_run(x_inp, [self.extract_layer], stop_after=self.extract_layer)
+        mul = T.linear(condT, self.film_mul.weight, self.film_mul.bias)
+        add = T.linear(condT, self.film_add.weight, self.film_add.bias)
+        a = T.FilmFanoutFn.apply(T.linear(acts[0].detach(), self.reduce.weight, self.reduce.bias), mul, add)
+        a = T.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
+        a = T.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
+        return T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
 
     def _head_train(self, act, condT):
         from .clip import train_ops as T

@@ -768,6 +768,19 @@ int egm_baseline_fwd_multi(int dtype, const void* x, int tok_off, int Ltot, cons
 int egm_film_fanout(int dtype, const void* r, const void* mul, const void* add, void* out, int B, int K, int L, int D, egm_stream_t s);
 int egm_bcast_add(int dtype, void* a, const void* r, int B, int K, int L, int D, egm_stream_t s);
 int egm_sigmoid_affine(float* x, const float* scale, float offset, int N, int C, long long HW, egm_stream_t s);
+/* Decoder training on K prompts (CLIPDenseBase.forward_multi_train).  fp32 accumulation, one rounding per output, no allocation, no
+ * synchronisation, no atomics: results are bitwise reproducible.
+ * egm_bcast_add_out: out[b*K + k][t][:] = a[b*K + k][t][:] + r[b][t][:], egm_bcast_add out of place (same expression and rounding).
+ * egm_group_sum: out[b][t][:] = sum_k g[b*K + k][t][:] (k ascending), the gradient of egm_bcast_add's r.
+ * egm_film_fanout_bwd: from g [B*K][L][D] (the gradient of egm_film_fanout's out), r and mul:
+ *   dr[b][t][:] = sum_k g[b*K + k][t][:] * mul[k][:] (k ascending),  dmul[k][:] = sum_{b,t} g[b*K + k][t][:] * r[b][t][:],
+ *   dadd[k][:] = sum_{b,t} g[b*K + k][t][:];  dr [B][L][D], dmul / dadd [K][D], all in `dtype`.  One workgroup per (image, token tile)
+ *   writes fp32 partials [block][2][K][D] into ws (egm_film_fanout_bwd_workspace() bytes), a second launch adds them in block order. */
+int egm_bcast_add_out(int dtype, const void* a, const void* r, void* out, int B, int K, int L, int D, egm_stream_t s);
+int egm_group_sum(int dtype, const void* g, void* out, int B, int K, int L, int D, egm_stream_t s);
+long long egm_film_fanout_bwd_workspace(int dtype, int B, int K, int L, int D);
+int egm_film_fanout_bwd(int dtype, const void* g, const void* r, const void* mul, void* dr, void* dmul, void* dadd, void* ws, int B, int K,
+                        int L, int D, egm_stream_t s);
 
 #ifdef __cplusplus
 }
