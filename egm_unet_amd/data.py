@@ -222,6 +222,55 @@ def clip_preprocess(img_u8, size=(352, 352), mean=(0.485, 0.456, 0.406), std=(0.
     return out.view(1, 3, Sh, Sw)
 
 
+def _check_batch_u8(imgs_u8, who):
+    imgs = _check_u8(imgs_u8, 4)
+    if imgs.shape[0] == 0 or imgs.shape[3] != 3:
+        raise RuntimeError(f"egm_unet_amd.data.{who}: a non-empty batch of RGB images ([B,H,W,3] uint8) expected")
+    return imgs
+
+
+def _check_batch_out(out, shape, device, who):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == math.prod(shape)):
+        raise RuntimeError(f"egm_unet_amd.data.{who}: out must be a contiguous CUDA float32 tensor of {math.prod(shape)} elements")
+    return out
+
+
+def unet_preprocess_batch(imgs_u8, base_size, mean, std, out=None):
+    """The UNet branch's preprocessing for B photos of one size: uint8 [B, H, W, 3] on the device -> fp32 [B, 3, h, w] with
+    out[b] == augment(resize_bilinear(imgs_u8[b], base_size), None, False, False, 0, 0, h, w, mean, std)[0] bit for bit ((h, w) by
+    _resize_output_size), in at most two launches whatever B.  out: an optional contiguous fp32 buffer of B * 3 * h * w elements."""
+    imgs = _check_batch_u8(imgs_u8, "unet_preprocess_batch")
+    B, H, W, _ = imgs.shape
+    ow, oh = _resize_output_size(W, H, base_size)
+    out = _check_batch_out(out, (B, 3, oh, ow), imgs.device, "unet_preprocess_batch")
+    xb, xc, xk = _bilinear_tables(W, ow, imgs.device) if ow != W else (None, None, 0)
+    yb, yc, yk = _bilinear_tables(H, oh, imgs.device) if oh != H else (None, None, 0)
+    tmp = torch.empty((B, H, ow, 3), dtype=torch.uint8, device=imgs.device) if ow != W else None
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    lib().call("egm_unet_preprocess_batch_u8", ptr(imgs), B, H, W, ptr(out), oh, ow, ptr(xb), ptr(xc), xk, ptr(yb), ptr(yc), yk,
+               ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p), ptr(tmp), stream())
+    return out.view(B, 3, oh, ow)
+
+
+def clip_preprocess_batch(imgs_u8, size=(352, 352), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), antialias=True, out=None):
+    """clip_preprocess for B photos of one size: uint8 [B, H, W, 3] on the device -> fp32 [B, 3, Sh, Sw] with
+    out[b] == clip_preprocess(imgs_u8[b], size, mean, std, antialias)[0] bit for bit, in two launches whatever B.
+    out: an optional contiguous fp32 buffer of B * 3 * Sh * Sw elements."""
+    imgs = _check_batch_u8(imgs_u8, "clip_preprocess_batch")
+    B, H, W, _ = imgs.shape
+    Sh, Sw = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    xb, xw, xk = float_filter_tables(W, Sw, antialias, imgs.device)
+    yb, yw, yk = float_filter_tables(H, Sh, antialias, imgs.device)
+    out = _check_batch_out(out, (B, 3, Sh, Sw), imgs.device, "clip_preprocess_batch")
+    tmp = torch.empty((3, B, H, Sw), dtype=torch.float32, device=imgs.device)
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    lib().call("egm_clip_preprocess_batch_u8", ptr(imgs), B, H, W, ptr(out), Sh, Sw, ptr(xb), ptr(xw), xk, ptr(yb), ptr(yw), yk,
+               ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p), ptr(tmp), stream())
+    return out.view(B, 3, Sh, Sw)
+
+
 class SegmentationPresetTrain:
     """train.py:14-33 on the device: RandomResize(0.5*base, 1.2*base) -> flips -> RandomCrop(crop) -> ToTensor -> Normalize."""
 

@@ -6,6 +6,11 @@ pipeline of predict_CLIPseg.py -- decoded uint8 photo on the device in, uint8 ma
     mask = ens(img_u8)                      # uint8 [H0, W0] on the device; img_u8 is [H0, W0, 3] uint8 cuda
     clip_l, unet_l = ens.logits(img_u8)     # what predict_CLIPseg.py / eval_CLIPseg.py append to their lists
     best, best_miou, mious = ens.search_alpha(images, labels)
+
+and the same for photos in batches (B photos of one size per replayed graph, both models at batch B):
+
+    masks = ens.predict_batch(imgs_u8)      # uint8 [B, H0, W0]; imgs_u8 is [B, H0, W0, 3] uint8 cuda, or a list of B photos
+    masks = ens.predict_many(photos, 8)     # photos of any sizes -> their masks in input order, grouped by plan_batches
 """
 import collections
 import itertools
@@ -90,6 +95,26 @@ def fuse_mask(clip_logits, unet_logits, alpha, out_size, lut=None, out=None):
     return out
 
 
+def plan_batches(sizes, batch_size):
+    """Group photos by size for batched inference: sizes is a sequence of (H0, W0), one per photo -> a list of
+    (size, input indices, pad count), one per batch.  A batch holds photos of one size only, in input order; sizes come in the order
+    of their first photo; every input index appears exactly once; a batch has len(indices) + pad == batch_size, with pad > 0 only in
+    a size's last batch (the caller repeats that batch's last photo pad times, so every batch of a size has the same shape).
+    Pure host code."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"plan_batches: batch_size must be at least 1, got {batch_size}")
+    groups = collections.OrderedDict()
+    for i, size in enumerate(sizes):
+        groups.setdefault((int(size[0]), int(size[1])), []).append(i)
+    plan = []
+    for size, idx in groups.items():
+        for k in range(0, len(idx), batch_size):
+            part = idx[k:k + batch_size]
+            plan.append((size, part, batch_size - len(part)))
+    return plan
+
+
 class EnsemblePredictor:
     """predict_CLIPseg.py per image (:438-534) as one object: a decoded uint8 photo [H0, W0, 3] already on the device goes in, the uint8
     mask [H0, W0] comes out.
@@ -111,7 +136,11 @@ class EnsemblePredictor:
     weights are folded again before each replay into the same buffers (Predictor.refresh); a change of the CLIPSeg model's parameters
     or compute dtype (stamp of _version, data_ptr and the generation counters that raw-pointer optimizers such as clip.train_ops.AdamW
     bump) drops the captured graphs and recomputes the conditionals, because the cast-weight
-    caches move to new buffers then."""
+    caches move to new buffers then.
+
+    predict_batch / logits_batch / predict_many run B photos of one size through the same pipeline at batch B (_run_batch) under the
+    same protocol, keyed by (B, H0, W0): batched and per-image entries share max_graphs and its eviction order, alpha, the lut, the
+    conditionals and every drop rule above.  Results are per image: nothing in either model reduces over the batch."""
 
     def __init__(self, unet, clipseg, prompts, alpha=0.5, unet_mean=(0.709, 0.381, 0.224), unet_std=(0.127, 0.079, 0.043), base_size=565,
                  clip_size=352, clip_antialias=True, lut=(0, 255), dtype=None, graph=True, max_graphs=4, clip_mean=(0.485, 0.456, 0.406),
@@ -137,7 +166,8 @@ class EnsemblePredictor:
         self.graph = bool(graph)
         self.max_graphs = max(1, int(max_graphs))
         self.num_captures = 0
-        self._graphs = collections.OrderedDict()     # (H0, W0) -> {"tag", "graph", "img", "out": (mask, clip logits, unet logits)}
+        # (H0, W0) of a photo or (B, H0, W0) of a batch -> {"tag", "graph", "img", "out": (mask, clip logits, unet logits)}
+        self._graphs = collections.OrderedDict()
         self._clip_tensors = list(clipseg.parameters()) + list(clipseg.buffers())
         self._clip_stamp = None
         self._condT = None
@@ -177,15 +207,25 @@ class EnsemblePredictor:
         mask = fuse_mask(clip_l, unet_l, self._alpha, (H0, W0), self._lut)
         return mask[0], clip_l, unet_l
 
-    def _call(self, img):
-        img = data._check_u8(img, 3)
-        if img.shape[2] != 3:
-            raise RuntimeError("EnsemblePredictor: RGB images ([H0, W0, 3] uint8) expected")
+    def _run_batch(self, imgs):
+        """_run for B photos of one size [B, H0, W0, 3]: both preprocessing chains in launches that cover the whole batch, both models
+        at batch B, the tail at N = B -> (masks [B, H0, W0], clip logits [B, K, ch, cw], unet logits [B, C, h, w])."""
+        B, H0, W0, _ = imgs.shape
+        x = data.unet_preprocess_batch(imgs, self.base_size, self.unet_mean, self.unet_std)
+        unet_l = self._unet(x)["out"]
+        xc = data.clip_preprocess_batch(imgs, self.clip_size, self.clip_mean, self.clip_std, self.clip_antialias)
+        out = self.clipseg._decode_multi(xc, self._condT)
+        clip_l = out.view(B, self._condT.shape[0], out.shape[-2], out.shape[-1])
+        mask = fuse_mask(clip_l, unet_l, self._alpha, (H0, W0), self._lut)
+        return mask, clip_l, unet_l
+
+    def _replayed(self, key, src, run):
+        """The graph protocol of every entry: `run(src)` eagerly (graph=False), or per key the warm-up call, the capturing call and the
+        replays.  key: (H0, W0) for one photo, (B, H0, W0) for a batch; both kinds share the table, its limit and its eviction order."""
         with torch.no_grad():
             self._refresh()
             if not self.graph:
-                return self._run(img)
-            key = (img.shape[0], img.shape[1])
+                return run(src)
             ent = self._graphs.get(key)
             if ent is None:
                 while len(self._graphs) >= self.max_graphs:
@@ -193,7 +233,7 @@ class EnsemblePredictor:
                 ent = {"tag": ("ensemble", next(_serial)), "graph": None, "img": None, "out": None}
                 try:
                     with ops.table_namespace(ent["tag"]):          # warm-up: tables, positional embedding, cast weights, allocator
-                        out = self._run(img)
+                        out = run(src)
                 except BaseException:
                     ops.drop_table_namespace(ent["tag"])
                     raise
@@ -201,17 +241,33 @@ class EnsemblePredictor:
                 return out
             self._graphs.move_to_end(key)
             if ent["graph"] is None:
-                ent["img"] = img.detach().clone(memory_format=torch.contiguous_format)
+                ent["img"] = src.detach().clone(memory_format=torch.contiguous_format)
                 g = torch.cuda.CUDAGraph(keep_graph=True)
                 with ops.table_namespace(ent["tag"]), torch.cuda.graph(g):
-                    ent["out"] = self._run(ent["img"])
+                    ent["out"] = run(ent["img"])
                 g.instantiate()
                 ent["graph"] = g
                 self.num_captures += 1
             else:
-                ent["img"].copy_(img)
+                ent["img"].copy_(src)
             ent["graph"].replay()
             return ent["out"]
+
+    def _call(self, img):
+        img = data._check_u8(img, 3)
+        if img.shape[2] != 3:
+            raise RuntimeError("EnsemblePredictor: RGB images ([H0, W0, 3] uint8) expected")
+        return self._replayed((img.shape[0], img.shape[1]), img, self._run)
+
+    def _call_batch(self, imgs):
+        if isinstance(imgs, (list, tuple)):
+            if len(imgs) == 0:
+                raise RuntimeError("EnsemblePredictor: an empty batch")
+            imgs = torch.stack([data._check_u8(im, 3) for im in imgs])         # photos of one size, stacked on the device
+        imgs = data._check_u8(imgs, 4)
+        if imgs.shape[0] == 0 or imgs.shape[3] != 3:
+            raise RuntimeError("EnsemblePredictor: a non-empty batch of RGB images ([B, H0, W0, 3] uint8, or a list of [H0, W0, 3]) expected")
+        return self._replayed(tuple(imgs.shape[:3]), imgs, self._run_batch)
 
     def __call__(self, img_u8, clone=False):
         mask = self._call(img_u8)[0]
@@ -222,6 +278,30 @@ class EnsemblePredictor:
         eval_CLIPseg.py collect per image."""
         _, c, u = self._call(img_u8)
         return (c.clone(), u.clone()) if clone else (c, u)
+
+    def predict_batch(self, imgs_u8, clone=False):
+        """B photos of one size, uint8 [B, H0, W0, 3] on the device (or a list of B [H0, W0, 3] tensors) -> uint8 masks [B, H0, W0];
+        row b is what the per-image call computes for photo b, whatever else is in the batch.  The graph protocol of __call__, keyed
+        by (B, H0, W0): warm-up, capture, replays; a replay returns the graph's buffer unless clone=True."""
+        mask = self._call_batch(imgs_u8)[0]
+        return mask.clone() if clone else mask
+
+    def logits_batch(self, imgs_u8, clone=False):
+        """-> (clip_logits [B, K, clip_h, clip_w], unet_logits [B, C, h, w]) fp32 of a batch as for predict_batch."""
+        _, c, u = self._call_batch(imgs_u8)
+        return (c.clone(), u.clone()) if clone else (c, u)
+
+    def predict_many(self, photos, batch_size=8):
+        """A folder's worth of photos: a sequence of [H0, W0, 3] uint8 device tensors of any sizes -> their uint8 masks [H0, W0] in
+        input order, each a tensor of its own.  Photos are grouped by size (plan_batches) and go through predict_batch in groups of
+        batch_size; a short last group is filled up with its last photo, so every batch of a size replays the same graph."""
+        photos = list(photos)
+        masks = [None] * len(photos)
+        for _, idx, pad in plan_batches([tuple(p.shape[:2]) for p in photos], batch_size):
+            out = self.predict_batch([photos[i] for i in idx] + [photos[idx[-1]]] * pad)
+            for row, i in enumerate(idx):
+                masks[i] = out[row].clone()
+        return masks
 
     def _drop(self, key):
         ent = self._graphs.pop(key)
@@ -234,18 +314,26 @@ class EnsemblePredictor:
             self._drop(key)
 
     def captured_graph(self, size):
-        """The captured torch.cuda.CUDAGraph of photo size (H0, W0), or None (for tools that count its kernel nodes)."""
-        ent = self._graphs.get((int(size[0]), int(size[1])))
+        """The captured torch.cuda.CUDAGraph of photo size (H0, W0), or of the batch (B, H0, W0), or None (for tools that count its
+        kernel nodes)."""
+        ent = self._graphs.get(tuple(int(v) for v in size))
         return None if ent is None else ent["graph"]
 
-    def search_alpha(self, images, labels, search_scale=(0.1, 10.0), search_step=100):
+    def search_alpha(self, images, labels, search_scale=(0.1, 10.0), search_step=100, batch_size=None):
         """eval_CLIPseg.py:656-723 over this pipeline: the logits of every image go through the alpha grid search (one confusion matrix per
-        alpha over all images, first maximum wins); labels at the UNet's size [h, w].  Sets self.alpha. -> (best, best_miou, miou per alpha)"""
-        cl, ul = [], []
-        for img in images:
-            c, u = self.logits(img, clone=True)
-            cl.append(c)
-            ul.append(u)
+        alpha over all images, first maximum wins); labels at the UNet's size [h, w].  batch_size=None collects the logits image by
+        image; a number collects them through logits_batch over plan_batches (the grid search still gets them per image, in input
+        order).  Sets self.alpha. -> (best, best_miou, miou per alpha)"""
+        images = list(images)
+        cl, ul = [None] * len(images), [None] * len(images)
+        if batch_size is None:
+            for i, img in enumerate(images):
+                cl[i], ul[i] = self.logits(img, clone=True)
+        else:
+            for _, idx, pad in plan_batches([tuple(im.shape[:2]) for im in images], batch_size):
+                c, u = self.logits_batch([images[i] for i in idx] + [images[idx[-1]]] * pad)
+                for row, i in enumerate(idx):
+                    cl[i], ul[i] = c[row:row + 1].clone(), u[row:row + 1].clone()
         best, best_miou, m = search_best_alpha(cl, ul, labels, search_scale, search_step, self.num_classes)
         self.alpha = best
         return best, best_miou, m

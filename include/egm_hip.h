@@ -670,6 +670,25 @@ int egm_ensemble_mask_u8(const float* clip_logits, const float* unet_logits, con
                          int W, const int* yidx, const int* xidx, const unsigned char* lut, unsigned char* out, int H0, int W0,
                          egm_stream_t s);
 
+/* ---- batched ensemble pipeline: the same two ends for B photos of one size, contiguous uint8 [B][H][W][3] (image b starts b*H*W*3
+ * bytes in, at whatever alignment that is; nothing outside the buffer is read).  Every launch covers the whole batch, so the launch
+ * count does not depend on B.  The tail needs no batched form: egm_ensemble_mask_u8 takes N.
+ * egm_unet_preprocess_batch_u8: egm_resample_u8 along axis 1 (W -> ow), then along axis 0 (H -> oh), then egm_augment_u8 without
+ *   flips and with the full crop, for every image: fp32 [B][3][oh][ow], per element the same expressions, so image b equals the
+ *   per-image chain bit for bit.  Tables as for egm_resample_u8 (bounds [out][2], coefs [out][ksize] int32, 22-bit fixed point).
+ *   A pass whose bounds and coefs are NULL is the identity and is skipped (then ow == W, or oh == H).  tmp_bhwc3: uint8
+ *   [B][H][ow][3] from the caller, used by the horizontal pass only (may be NULL without one).  The vertical pass writes the
+ *   normalised floats directly: two launches, or one without a horizontal pass.  mean3/std3 are HOST pointers.
+ * egm_clip_preprocess_batch_u8: egm_clip_preprocess_u8 for every image, fp32 [B][3][Sh][Sw], bit-identical per image (the same
+ *   horizontal kernel over the B*H rows, the same taps and expressions in the vertical pass).  tmp_cbhw: fp32 [3][B][H][Sw] from the
+ *   caller.  The same limits: ksize <= 64 per axis and the LDS bound, otherwise EGM_ERR_ARG; B*H*W*3 < 2^31.  Two launches. */
+int egm_unet_preprocess_batch_u8(const void* imgs_bhwc3, int B, int H, int W, float* out_bchw, int oh, int ow, const int* xbounds,
+                                 const int* xcoefs, int xksize, const int* ybounds, const int* ycoefs, int yksize,
+                                 const float* mean3_host, const float* std3_host, void* tmp_bhwc3, egm_stream_t s);
+int egm_clip_preprocess_batch_u8(const void* imgs_bhwc3, int B, int H, int W, float* out_bchw, int Sh, int Sw, const int* xbounds,
+                                 const float* xweights, int xksize, const int* ybounds, const float* yweights, int yksize,
+                                 const float* mean3_host, const float* std3_host, float* tmp_cbhw, egm_stream_t s);
+
 /* ---- CLIPSeg decoder training (models/clipseg.py:380-420,452-496; experiments/phrasecut.yaml:1-47) ------------------
  * The backward matrix products run on egm_gemm over transposed copies (egm_transpose: dst[b][c][r] = src[b][r][c]).
  * egm_relu_bwd: dst = g where out > 0.  egm_softmax_bwd_rows: dS = P*(dP - sum_j dP_j P_j)*alpha per row (P storage type,

@@ -7,6 +7,13 @@ synthetic photos.  One JSON line per (size, repeat).
     python tools/egm_ensemble_bench.py [--iters 50] [--sizes 768x1024,3000x4000] [--repeats 3] [--step-timeout 240]
     rocprofv3 --kernel-trace --stats -- python tools/egm_ensemble_bench.py --child 768x1024 --profile-one ens     # or composed: 12 calls
 
+--batches 1,2,4,8,16 measures batched inference in place of the above: per repeat the per-image replay and predict_batch at each B
+alternate in one process, and a line gives ms per photo of both, the per-image replay's over the batched one's, and the kernel nodes
+of each graph.  A B whose photos exceed --max-batch-bytes (default 160 MB: B <= 4 at 3000x4000) is left out.
+
+    python tools/egm_ensemble_bench.py --batches 1,2,4,8,16
+    rocprofv3 --kernel-trace --stats -- python tools/egm_ensemble_bench.py --child 768x1024 --profile-one batch --profile-batch 8
+
 Every size runs in a child process of its own under a time limit; a child that fails ends the run."""
 import argparse
 import json
@@ -38,7 +45,7 @@ def timed(fn, iters, warmup=5):
     return statistics.median(ts)
 
 
-def child(H0, W0, iters, repeats, profile_one=None):
+def child(H0, W0, iters, repeats, profile_one=None, batches=(), profile_batch=8):
     import torch.nn.functional as F
     from egm_unet_amd import GRFBUNet, data
     from egm_unet_amd.clipseg import CLIPDensePredT
@@ -70,12 +77,39 @@ def child(H0, W0, iters, repeats, profile_one=None):
                 state["xi"] = data.cv_nearest_table(p.shape[2], W0, dev).long()
             return lut[p[0][state["yi"]][:, state["xi"]]]
 
-    ens = EnsemblePredictor(unet, clipseg, cond, alpha=0.5, dtype=dt)
+    ens = EnsemblePredictor(unet, clipseg, cond, alpha=0.5, dtype=dt, max_graphs=len(batches) + 4)
+
+    def stack(B):
+        return torch.randint(0, 256, (B, H0, W0, 3), generator=torch.Generator().manual_seed(3), dtype=torch.uint8).to(dev)
     if profile_one:                                                    # 12 calls of one kind and nothing else
-        fn = composed if profile_one == "composed" else (lambda: ens(img))
+        if profile_one == "batch":
+            imgs = stack(profile_batch)
+            fn = lambda: ens.predict_batch(imgs)                       # noqa: E731
+        else:
+            fn = composed if profile_one == "composed" else (lambda: ens(img))
         for _ in range(12):
             fn()
         torch.cuda.synchronize()
+        return
+    if batches:                                                        # per-image replay and predict_batch at each B, alternating
+        stacks = {B: stack(B) for B in batches}
+        for rep in range(repeats):
+            one_ms = []
+            for B in batches:
+                one_ms.append(timed(lambda: ens(img), iters))
+                ms = timed(lambda: ens.predict_batch(stacks[B]), iters)
+                g = ens.captured_graph((B, H0, W0))
+                print(json.dumps({"photo": [H0, W0], "repeat": rep, "batch": B, "batch_ms": round(ms, 3), "ms_per_photo": round(ms / B, 3),
+                                  "per_image_ms_just_before": round(one_ms[-1], 3), "per_image_over_batched": round(one_ms[-1] / (ms / B), 2),
+                                  "graph_kernel_nodes": kernel_nodes(g) if g is not None else None}), flush=True)
+            g = ens.captured_graph((H0, W0))
+            print(json.dumps({"photo": [H0, W0], "repeat": rep, "per_image_ms": round(statistics.median(one_ms), 3),
+                              "per_image_ms_min_max": [round(min(one_ms), 3), round(max(one_ms), 3)],
+                              "graph_kernel_nodes": kernel_nodes(g) if g is not None else None}), flush=True)
+        B = batches[-1]
+        rows = ens.predict_batch(stacks[B], clone=True)
+        same = min(float((rows[b] == ens(stacks[B][b])).float().mean()) for b in range(B))
+        print(json.dumps({"photo": [H0, W0], "batch": B, "min_mask_agreement_with_per_image": round(same, 6)}), flush=True)
         return
     # the clip-preprocess kernels alone (both launches), events around the call
     out = torch.empty((1, 3, 352, 352), dtype=torch.float32, device=dev)
@@ -99,14 +133,22 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--step-timeout", type=int, default=240, help="seconds per size (one child process each)")
     ap.add_argument("--child", default=None)
-    ap.add_argument("--profile-one", default=None, choices=["ens", "composed"], help="with --child: 12 calls of one kind (for rocprofv3)")
+    ap.add_argument("--profile-one", default=None, choices=["ens", "composed", "batch"],
+                    help="with --child: 12 calls of one kind (for rocprofv3)")
+    ap.add_argument("--profile-batch", type=int, default=8, help="B of --profile-one batch")
+    ap.add_argument("--batches", default="", help="e.g. 1,2,4,8,16: measure predict_batch at these B against the per-image replay")
+    ap.add_argument("--max-batch-bytes", type=float, default=160e6, help="leave out a B whose uint8 photos are larger than this")
     args = ap.parse_args()
     if args.child:
         H0, W0 = (int(v) for v in args.child.split("x"))
-        child(H0, W0, args.iters, args.repeats, args.profile_one)
+        batches = [int(v) for v in args.batches.split(",") if v]
+        batches = [B for B in batches if B * H0 * W0 * 3 <= args.max_batch_bytes]
+        child(H0, W0, args.iters, args.repeats, args.profile_one, batches, args.profile_batch)
         return
     for size in args.sizes.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", size, "--iters", str(args.iters), "--repeats", str(args.repeats)]
+        if args.batches:
+            cmd += ["--batches", args.batches, "--max-batch-bytes", str(args.max_batch_bytes)]
         try:
             rc = subprocess.run(cmd, timeout=args.step_timeout).returncode
         except subprocess.TimeoutExpired:
