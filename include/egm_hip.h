@@ -689,6 +689,41 @@ int egm_clip_preprocess_batch_u8(const void* imgs_bhwc3, int B, int H, int W, fl
                                  const float* xweights, int xksize, const int* ybounds, const float* yweights, int yksize,
                                  const float* mean3_host, const float* std3_host, float* tmp_cbhw, egm_stream_t s);
 
+/* ---- batched training data path: B ragged photos with masks -> the batch a train step reads (train.py:14-33, my_dataset.py:118-132)
+ * egm_train_batch_u8: for every image b what egm_resample_u8 (axis 1, then axis 0), egm_gather_u8 and egm_augment_u8 compute one
+ *   after the other, written into slot b of out_img_bchw fp32 [B][3][slot_h][slot_w] and out_target_bhw int64 [B][slot_h][slot_w]: per
+ *   element the same expressions, so slot b equals the per-image chain bit for bit (image 0.0 / target 255 outside the crop, bytes 0 /
+ *   target 0 where the crop window reaches past the resized photo).  Two launches whatever B; one when max_hpass_pixels is 0.
+ * table_dev: DEVICE memory, B rows of egm_train_desc followed by the int32 tables the rows point to; every *_off of a row counts
+ *   int32 elements from table_dev itself (one blob, one upload).  With sy = y + top, sx = x + left, yy = vflip ? oh-1-sy : sy and
+ *   xx = hflip ? ow-1-sx : sx over the crop, the visible resized rows are [y0, y0 + ny) and the visible resized columns [c0, c0 + nc);
+ *   all tables are cut to those windows:
+ *     xb_off  int32 [nc][2]       (first tap, tap count) of resized column c0 + i over the W source columns   (xksize > 0 only)
+ *     xc_off  int32 [nc][xksize]  its 22-bit fixed-point coefficients                                          (xksize > 0 only)
+ *     yb_off  int32 [ny][2], yc_off int32 [ny][yksize]: the same for resized row y0 + i over the H source rows  (yksize > 0 only)
+ *     xnn_off int32 [nc], ynn_off int32 [ny]: source column / row of the mask for resized column c0 + i / row y0 + i (NEAREST)
+ *   xksize == 0 (ow == W) or yksize == 0 (oh == H) flags that pass as the identity.  [r0, r0 + nr) are the source rows the vertical
+ *   taps of the visible rows touch (the visible rows themselves without a vertical pass).  The horizontal pass writes uint8
+ *   [nr][nc][3] at workspace + ws_off; an image without one uses no workspace.
+ * slot_h >= max_crop_h, slot_w >= max_crop_w (the largest crop of the batch).  workspace: uint8 [workspace_bytes], may be NULL when
+ *   max_hpass_pixels (the largest nr * nc among the images with a horizontal pass) is 0.  mean3/std3 are HOST pointers.
+ *   B * 3 * slot_h * slot_w < 2^31 and workspace_bytes < 2^31, otherwise EGM_ERR_ARG.  Rows are built by egm_unet_amd.data.plan_train_batch;
+ *   the kernels clamp every table value into its window, so a wrong row gives wrong pixels, never an access outside the buffers it names. */
+typedef struct egm_train_desc {
+    const void* img;            /* uint8 [H][W][3] */
+    const void* mask;           /* uint8 [H][W] */
+    int H, W, oh, ow;           /* source size, resized size */
+    int hflip, vflip, top, left;
+    int crop_h, crop_w, r0, nr;
+    int c0, nc, y0, ny;
+    int xksize, yksize;
+    long long ws_off;           /* bytes into the workspace */
+    int xb_off, xc_off, yb_off, yc_off, xnn_off, ynn_off;
+} egm_train_desc;               /* 120 bytes */
+int egm_train_batch_u8(const egm_train_desc* table_dev, int B, int slot_h, int slot_w, int max_crop_h, int max_crop_w,
+                       float* out_img_bchw, long long* out_target_bhw, const float* mean3_host, const float* std3_host,
+                       void* workspace, long long workspace_bytes, long long max_hpass_pixels, egm_stream_t s);
+
 /* ---- CLIPSeg decoder training (models/clipseg.py:380-420,452-496; experiments/phrasecut.yaml:1-47) ------------------
  * The backward matrix products run on egm_gemm over transposed copies (egm_transpose: dst[b][c][r] = src[b][r][c]).
  * egm_relu_bwd: dst = g where out > 0.  egm_softmax_bwd_rows: dS = P*(dP - sum_j dP_j P_j)*alpha per row (P storage type,
