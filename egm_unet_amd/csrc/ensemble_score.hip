@@ -1,0 +1,249 @@
+// Scoring at the ground truth's size, the evaluation half of the ensemble workflow:
+//   egm_mask_confusion_u8:      confusion matrix of a predicted uint8 mask against a ground-truth uint8 mask (evaluating_indicator.py:
+//                               347-417, compute_mIoU's fast_hist), one streaming pass over both images
+//   egm_ensemble_alpha_hist_u8: the alpha grid search with the UNet-size argmax resized to the label's size by cv2.resize(INTER_NEAREST)
+//                               (eval_CLIPseg.py:682-711), one confusion matrix per alpha
+//
+// Counts are exact integers.  Both kernels keep 32-bit partial counts on chip and add them to the uint64 matrices with at most one 64-bit
+// atomic per cell and workgroup; the launchers refuse sizes at which a 32-bit partial could wrap (see each launcher).
+#include "common.h"
+#include "ensemble_fuse.h"
+
+namespace {
+
+constexpr int kScoreMaxC = 4;                  // classes, as egm_ensemble_alpha_hist
+constexpr int kScoreCells = kScoreMaxC * kScoreMaxC;
+constexpr int kScoreMaxAlphas = 128;
+constexpr int kConfMaxGrid = 2048;             // 8 workgroups of 256 per CU
+constexpr int kConfUnroll = 4;                 // 16-byte chunk pairs in flight per lane
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned int lo = __shfl_xor((unsigned int)v, o, 64), hi = __shfl_xor((unsigned int)(v >> 32), o, 64);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// Byte -> cell tables in LDS: lt[b] = label class * C, pt[b] = predicted class, 16 for a dropped byte; a pixel's cell is
+// min(lt[l] + pt[p], 16), and cell 16 is a counter row nobody reads, so a dropped pixel needs no branch.  Every lane owns one 32-bit
+// counter per cell, cnt[cell][lane] (lanes of a wave on different banks: an LDS add without conflicts and without a returned value).
+struct ConfLds {
+    unsigned int cnt[kScoreCells + 1][256];
+    unsigned char lt[256], pt[256];
+};
+
+__device__ __forceinline__ void conf_count(ConfLds& L, unsigned int p, unsigned int l) {
+    const int cell = min((int)L.lt[l] + (int)L.pt[p], kScoreCells);
+    atomicAdd(&L.cnt[cell][threadIdx.x], 1u);
+}
+__device__ __forceinline__ void conf_count16(ConfLds& L, const uint4& p, const uint4& l) {
+    const unsigned int pw[4] = {p.x, p.y, p.z, p.w}, lw[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) conf_count(L, (pw[w] >> (b * 8)) & 255u, (lw[w] >> (b * 8)) & 255u);
+}
+// 16 bytes from any address (the label's alignment is whatever it is once the chunks are cut at the prediction's 16-byte boundaries)
+__device__ __forceinline__ uint4 load16_any(const unsigned char* p) {
+    uint4 v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
+// Pixels [0, head) in front of the prediction's first 16-byte boundary and the tail behind the last whole chunk go byte by byte
+// (workgroup 0); the body is nchunks chunks of 16 pixels, grid-strided, kConfUnroll chunk pairs loaded before any is counted.
+__global__ __launch_bounds__(256) void mask_confusion_u8_kernel(const unsigned char* __restrict__ pred, const unsigned char* __restrict__ label,
+                                                                long long npix, const unsigned char* __restrict__ pred_cls,
+                                                                const unsigned char* __restrict__ label_cls, int C,
+                                                                unsigned long long* __restrict__ hist) {
+    __shared__ ConfLds L;
+    {
+        const unsigned int pc = pred_cls[threadIdx.x], lc = label_cls[threadIdx.x];
+        L.pt[threadIdx.x] = (unsigned char)(pc < (unsigned)C ? pc : kScoreCells);
+        L.lt[threadIdx.x] = (unsigned char)(lc < (unsigned)C ? lc * C : kScoreCells);
+        for (int k = 0; k <= kScoreCells; ++k) L.cnt[k][threadIdx.x] = 0u;
+    }
+    __syncthreads();
+    long long head = (long long)((16 - (reinterpret_cast<uintptr_t>(pred) & 15)) & 15);
+    if (head > npix) head = npix;
+    const long long nchunks = (npix - head) >> 4, tail0 = head + (nchunks << 4);
+    const unsigned char* pb = pred + head;
+    const unsigned char* lb = label + head;
+    const long long stride = (long long)gridDim.x * 256;
+    long long c = blockIdx.x * 256LL + threadIdx.x;
+    for (; c + (kConfUnroll - 1) * stride < nchunks; c += kConfUnroll * stride) {
+        uint4 pv[kConfUnroll], lv[kConfUnroll];
+#pragma unroll
+        for (int k = 0; k < kConfUnroll; ++k) {
+            pv[k] = *reinterpret_cast<const uint4*>(pb + ((c + k * stride) << 4));
+            lv[k] = load16_any(lb + ((c + k * stride) << 4));
+        }
+#pragma unroll
+        for (int k = 0; k < kConfUnroll; ++k) conf_count16(L, pv[k], lv[k]);
+    }
+    for (; c < nchunks; c += stride) conf_count16(L, *reinterpret_cast<const uint4*>(pb + (c << 4)), load16_any(lb + (c << 4)));
+    if (blockIdx.x == 0) {
+        for (long long i = threadIdx.x; i < head; i += 256) conf_count(L, pred[i], label[i]);
+        for (long long i = tail0 + threadIdx.x; i < npix; i += 256) conf_count(L, pred[i], label[i]);
+    }
+    __syncthreads();
+    // 64-bit sums of the 256 lanes' counters: wave w takes cells w, w + 4, ...
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int cell = wv; cell < C * C; cell += 4) {
+        unsigned long long v = 0ull;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v += L.cnt[cell][lane + 64 * k];
+        v = wave_sum_u64(v);
+        if (lane == 0 && v) atomicAdd(&hist[cell], v);
+    }
+}
+
+// A workgroup takes tiles of 256 UNet pixels ("source pixels") of image n, in two phases per tile.
+// Phase 1, one lane per source pixel: the label pixels that cv2.resize(INTER_NEAREST) fills from it are the rectangle
+// [ybeg[y], ybeg[y+1]) x [xbeg[x], xbeg[x+1]) (possibly empty); their classes are counted once, the bilinear CLIPSeg value and the UNet
+// logit of every class are evaluated once, and all of it goes to LDS.
+// Phase 2, one lane per ALPHA (two per lane when na > 64): every wave walks 64 of the tile's pixels, whose values all lanes read from
+// one LDS address (a broadcast), runs its alphas' argmax and adds the pixel's class counts to matrices it keeps in registers.  No lane
+// shares a matrix with another, so nothing is atomic until the end, where with one lane per pixel all 64 lanes of a wave would add
+// to the same two or three LDS words per alpha.
+// The fused value is the expression of ensemble_fused_argmax (ensemble_fuse.h): bilin_at(..) + alpha * unet, the first maximum wins.
+template <int C>
+__global__ __launch_bounds__(256) void ensemble_alpha_hist_u8_kernel(const float* __restrict__ clip, const float* __restrict__ unet,
+                                                                     const unsigned char* __restrict__ labels,
+                                                                     const unsigned char* __restrict__ label_cls,
+                                                                     const float* __restrict__ alphas, int na, int N, int hc, int wc, int H, int W,
+                                                                     int Hl, int Wl, const int* __restrict__ ybeg,
+                                                                     const int* __restrict__ xbeg, unsigned long long* __restrict__ hist) {
+    __shared__ unsigned int lh[kScoreMaxAlphas * C * C];          // [na][C][C]
+    __shared__ float s_cv[C][256], s_uv[C][256];
+    __shared__ unsigned int s_cnt[C][256];
+    __shared__ unsigned char lt[256];
+    for (int i = threadIdx.x; i < na * C * C; i += 256) lh[i] = 0u;
+    lt[threadIdx.x] = label_cls[threadIdx.x];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float al[2];
+    unsigned int acc[2][C][C];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        al[k] = lane + 64 * k < na ? alphas[lane + 64 * k] : 0.f;
+#pragma unroll
+        for (int t = 0; t < C; ++t)
+#pragma unroll
+            for (int p = 0; p < C; ++p) acc[k][t][p] = 0u;
+    }
+    __syncthreads();
+    const long long HW = (long long)H * W, total = (long long)N * HW, tiles = (total + 255) >> 8;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long i = (tile << 8) + threadIdx.x;
+        unsigned int cnt[C];
+#pragma unroll
+        for (int t = 0; t < C; ++t) cnt[t] = 0u;
+        if (i < total) {
+            int n, y, x;
+            egm_pix_nyx(i, H, W, n, y, x);
+            // the tables are clamped, so none can make the kernel read outside the label
+            const int Y0 = clampi(ybeg[y], 0, Hl), Y1 = clampi(ybeg[y + 1], Y0, Hl);
+            const int X0 = clampi(xbeg[x], 0, Wl), X1 = clampi(xbeg[x + 1], X0, Wl);
+            const unsigned char* lab = labels + (long long)n * Hl * Wl;
+            for (int Y = Y0; Y < Y1; ++Y) {
+                const unsigned char* row = lab + (long long)Y * Wl;
+                for (int X = X0; X < X1; ++X) {
+                    const int t = lt[row[X]];
+#pragma unroll
+                    for (int k = 0; k < C; ++k) cnt[k] += (t == k) ? 1u : 0u;
+                }
+            }
+            int y0, y1, x0, x1; float wy, wx;
+            bilin_src(y, hc, H, y0, y1, wy); bilin_src(x, wc, W, x0, x1, wx);
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                s_cv[c][threadIdx.x] = bilin_at(clip + ((long long)n * C + c) * hc * wc, wc, y0, y1, wy, x0, x1, wx);
+                s_uv[c][threadIdx.x] = unet[((long long)n * C + c) * HW + (i - n * HW)];
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < C; ++t) s_cnt[t][threadIdx.x] = cnt[t];              // (zeros behind the last pixel: skipped below)
+        __syncthreads();
+        for (int j = wv * 64; j < wv * 64 + 64; ++j) {
+            unsigned int pc[C], any = 0u;
+#pragma unroll
+            for (int t = 0; t < C; ++t) { pc[t] = s_cnt[t][j]; any |= pc[t]; }
+            if (!any) continue;                                                  // the same for every lane
+            float cv[C], uv[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) { cv[c] = s_cv[c][j]; uv[c] = s_uv[c][j]; }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (k * 64 >= na) break;
+                const float alpha = al[k];
+                int best = 0; float m = -INFINITY;
+#pragma unroll
+                for (int c = 0; c < C; ++c) { const float v = cv[c] + alpha * uv[c]; if (v > m) { m = v; best = c; } }
+#pragma unroll
+                for (int t = 0; t < C; ++t)
+#pragma unroll
+                    for (int p = 0; p < C; ++p) acc[k][t][p] += (best == p) ? pc[t] : 0u;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int a = lane + 64 * k;
+        if (a < na) {
+#pragma unroll
+            for (int t = 0; t < C; ++t)
+#pragma unroll
+                for (int p = 0; p < C; ++p) if (acc[k][t][p]) atomicAdd(&lh[(a * C + t) * C + p], acc[k][t][p]);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < na * C * C; i += 256) if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
+}
+
+}  // namespace
+
+// Partial counts: 32 bits per lane and cell, summed in 64 bits per workgroup.  A lane counts at most 16 * ceil(chunks / (grid * 256))
+// pixels plus the 30 of head and tail; the grid is min(ceil(chunks / (256 * 4)), 2048): a lane has 4 chunks (one pass of the unrolled
+// body) up to 33.5 M pixels and more beyond, and npix <= 2^40 keeps it below 2^22 pixels.
+extern "C" int egm_mask_confusion_u8(const unsigned char* pred, const unsigned char* label, long long npix, const unsigned char* pred_cls,
+                                     const unsigned char* label_cls, int C, unsigned long long* hist, egm_stream_t s) {
+    EGM_REQUIRE(pred && label && pred_cls && label_cls && hist, "mask_confusion_u8: null pointer");
+    EGM_REQUIRE(C > 0 && C <= kScoreMaxC, "mask_confusion_u8: %d classes, between 1 and %d are supported", C, kScoreMaxC);
+    EGM_REQUIRE(npix > 0 && npix <= (1ll << 40), "mask_confusion_u8: %lld pixels, between 1 and 2^40 are supported", npix);
+    long long grid = ((npix >> 4) + 256 * kConfUnroll - 1) / (256 * kConfUnroll);   // kConfUnroll chunks per lane, so the unrolled body runs
+    if (grid > kConfMaxGrid) grid = kConfMaxGrid;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(mask_confusion_u8_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)s, pred, label, npix, pred_cls, label_cls, C, hist);
+    EGM_CHECK_LAUNCH("mask_confusion_u8");
+    return EGM_OK;
+}
+
+// Partial counts: 32 bits per lane, alpha and cell, then per workgroup.  Either is at most the call's label pixels, N * Hl * Wl, so
+// the call is refused from 2^32 label pixels on (357 photos of 3000 x 4000); split such a batch over several calls.
+extern "C" int egm_ensemble_alpha_hist_u8(const float* clip_logits, const float* unet_logits, const unsigned char* labels,
+                                          const unsigned char* label_cls, const float* alphas, int na, int N, int C, int hc, int wc, int H,
+                                          int W, int Hl, int Wl, const int* ybeg, const int* xbeg, unsigned long long* hist, egm_stream_t s) {
+    EGM_REQUIRE(clip_logits && unet_logits && labels && label_cls && alphas && ybeg && xbeg && hist, "ensemble_alpha_hist_u8: null pointer");
+    EGM_REQUIRE(na > 0 && na <= kScoreMaxAlphas && C > 0 && C <= kScoreMaxC && N > 0 && hc > 0 && wc > 0 && H > 0 && W > 0 && Hl > 0 && Wl > 0,
+                "ensemble_alpha_hist_u8: bad shape (na<=128, C<=4)");
+    EGM_REQUIRE((long long)N <= ((1ll << 32) - 1) / ((long long)Hl * Wl),
+                "ensemble_alpha_hist_u8: %d labels of %d x %d in one call, fewer than 2^32 label pixels are supported", N, Hl, Wl);
+    long long grid = ((long long)N * H * W + 255) / 256;                       // tiles of 256 source pixels
+    if (grid > 2048) grid = 2048;                                              // (565 x 753 is 1662 tiles: one each)
+#define EGM_ALPHA_HIST_U8(CC) hipLaunchKernelGGL(ensemble_alpha_hist_u8_kernel<CC>, dim3((int)grid), dim3(256), 0, (hipStream_t)s, clip_logits, \
+                                                 unet_logits, labels, label_cls, alphas, na, N, hc, wc, H, W, Hl, Wl, ybeg, xbeg, hist)
+    switch (C) {
+        case 1: EGM_ALPHA_HIST_U8(1); break;
+        case 2: EGM_ALPHA_HIST_U8(2); break;
+        case 3: EGM_ALPHA_HIST_U8(3); break;
+        default: EGM_ALPHA_HIST_U8(4); break;
+    }
+#undef EGM_ALPHA_HIST_U8
+    EGM_CHECK_LAUNCH("ensemble_alpha_hist_u8");
+    return EGM_OK;
+}

@@ -126,6 +126,21 @@ def cv_nearest_table(src, dst, device="cpu"):
     return out
 
 
+def cv_nearest_spans(src, dst, device="cpu"):
+    """cv_nearest_table(src, dst) seen from the source: int32 [src + 1], spans[i] = the first destination index whose source is >= i,
+    spans[src] = dst.  The table is non-decreasing, so the destination indices that read source i are exactly
+    [spans[i], spans[i + 1]) (an empty range for some i when dst < src).  Cached like the table; it inherits the table's caveat."""
+    key = ("cvnn_spans", src, dst, str(device))
+    hit = _table_cache.get(key)
+    if hit is not None:
+        return hit
+    table = cv_nearest_table(src, dst).numpy()
+    spans = np.searchsorted(table, np.arange(src + 1), side="left").astype(np.int32)
+    out = torch.from_numpy(spans).to(device)
+    _table_cache[key] = out
+    return out
+
+
 def _nearest_table(in_size, out_size, device):
     key = ("nn", in_size, out_size, device)
     hit = _table_cache.get(key)

@@ -115,6 +115,140 @@ def plan_batches(sizes, batch_size):
     return plan
 
 
+_MAX_SCORE_CLASSES = 4                      # egm_mask_confusion_u8 / egm_ensemble_alpha_hist_u8
+_class_table_cache = {}
+
+
+def class_table(values, num_classes):
+    """Byte value -> class as a uint8 numpy table of 256 entries; 255 marks a byte that is dropped.  values=None: the reference's
+    rule for a PNG divided by 255 and cast to int (evaluating_indicator.py:368-372,328; np.where(label == 255, 1, 0) of
+    eval_CLIPseg.py:647): 255 -> 1, everything else -> 0.  Otherwise values[k] is the byte of class k, k = 0..num_classes-1 (the
+    inverse of a colour map such as lut=(0, 255)); bytes not listed are dropped.  Two classes on one byte raise ValueError."""
+    C = int(num_classes)
+    if not 1 <= C <= _MAX_SCORE_CLASSES:
+        raise ValueError(f"class_table: {C} classes, between 1 and {_MAX_SCORE_CLASSES} are supported")
+    if values is None:
+        tab = np.zeros(256, dtype=np.uint8)
+        tab[255] = 1                             # (with one class, 1 >= C: dropped)
+        return tab
+    vals = [int(v) for v in (values.tolist() if isinstance(values, (torch.Tensor, np.ndarray)) else values)]
+    if len(vals) != C or any(v < 0 or v > 255 for v in vals):
+        raise ValueError(f"class_table: {C} byte values (0..255) expected, one per class, got {vals}")
+    if len(set(vals)) != C:
+        raise ValueError(f"class_table: byte values {vals} map two classes to one byte")
+    tab = np.full(256, 255, dtype=np.uint8)
+    for k, v in enumerate(vals):
+        tab[v] = k
+    return tab
+
+
+def _class_table_dev(values, C, device):
+    key = (None if values is None else tuple(int(v) for v in (values.tolist() if isinstance(values, (torch.Tensor, np.ndarray)) else values)),
+           int(C), str(device))
+    hit = _class_table_cache.get(key)
+    if hit is None:
+        hit = _class_table_cache[key] = torch.from_numpy(class_table(values, C)).to(device)
+    return hit
+
+
+def confusion_u8(pred_u8, label_u8, num_classes=2, pred_values=None, label_values=None, out=None):
+    """Confusion matrix of a predicted mask against its ground truth on the device (evaluating_indicator.py:347-417, fast_hist at the
+    masks' own size): uint8 CUDA tensors of equal shape ([H0, W0], or a batch [N, H0, W0]) -> int64 [C, C], rows = ground truth,
+    columns = prediction.  pred_values / label_values: see class_table (None = the reference's rule for 0/255 PNGs).  out: an int64
+    [C, C] CUDA tensor to accumulate into (and returned).  One launch, no host wait.  ValueError for anything but two uint8 CUDA
+    tensors of one shape."""
+    require_gpu()
+    for name, t in (("pred_u8", pred_u8), ("label_u8", label_u8)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8):
+            raise ValueError(f"confusion_u8: {name} must be a uint8 CUDA tensor")
+    if pred_u8.shape != label_u8.shape or pred_u8.numel() == 0:
+        raise ValueError(f"confusion_u8: pred {tuple(pred_u8.shape)} and label {tuple(label_u8.shape)} must have one non-empty shape")
+    C = int(num_classes)
+    dev = pred_u8.device
+    pt, lt = _class_table_dev(pred_values, C, dev), _class_table_dev(label_values, C, dev)
+    if out is None:
+        out = torch.zeros((C, C), dtype=torch.int64, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (C, C) and out.is_contiguous()):
+        raise ValueError(f"confusion_u8: out must be a contiguous int64 CUDA tensor [{C}, {C}]")
+    p, t = pred_u8.contiguous(), label_u8.contiguous()
+    lib().call("egm_mask_confusion_u8", ptr(p), ptr(t), p.numel(), ptr(pt), ptr(lt), C, ptr(out), stream())
+    return out
+
+
+def score_report(hist):
+    """The numbers evaluating_indicator.py reports from a confusion matrix (rows = ground truth), in numpy float64 with its own
+    expressions (per_class_iu, per_class_PA_Recall, per_class_Precision, per_Accuracy, :331-344, and np.nanmean, :415): an empty class
+    gives 0 / max(.., 1) = 0, not NaN.  hist: [C, C] tensor or array -> dict(hist int64, iou, recall, precision [C], accuracy, miou,
+    mpa)."""
+    h = np.asarray(hist.detach().cpu() if isinstance(hist, torch.Tensor) else hist).astype(np.int64)
+    f = h.astype(np.float64)                                                  # (the reference accumulates in a float64 matrix)
+    iou = np.diag(f) / np.maximum((f.sum(1) + f.sum(0) - np.diag(f)), 1)
+    recall = np.diag(f) / np.maximum(f.sum(1), 1)
+    precision = np.diag(f) / np.maximum(f.sum(0), 1)
+    accuracy = np.sum(np.diag(f)) / np.maximum(np.sum(f), 1)
+    return {"hist": h, "iou": iou, "recall": recall, "precision": precision, "accuracy": float(accuracy), "miou": float(np.nanmean(iou)),
+            "mpa": float(np.nanmean(recall))}
+
+
+def _label_u8(t, device):
+    """A ground-truth mask (numpy or tensor, 0..255) as a contiguous uint8 tensor on the device, [N, Hl, Wl]."""
+    t = torch.as_tensor(t)
+    if t.dtype != torch.uint8:
+        t = t.to(torch.uint8)
+    t = t.to(device)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"ground-truth masks are [Hl, Wl] or [N, Hl, Wl], got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _alpha_hist_fullres(c, u, lab, lcls, a_dev, hist):
+    """hist [S, C, C] += the confusion matrices of every alpha for logits c [N, C, hc, wc], u [N, C, H, W] against labels uint8
+    [N, Hl, Wl] at the labels' size (one launch)."""
+    c, u = c.contiguous().float(), u.contiguous().float()
+    N, C, H, W = u.shape
+    if c.dim() != 4 or c.shape[0] != N or c.shape[1] != C or lab.shape[0] != N or hist.shape[-1] != C:
+        raise ValueError(f"alpha search: clip logits {tuple(c.shape)}, unet logits {tuple(u.shape)} and labels {tuple(lab.shape)} must agree "
+                         f"in N and in C = {hist.shape[-1]}")
+    Hl, Wl = lab.shape[1:]
+    lib().call("egm_ensemble_alpha_hist_u8", ptr(c), ptr(u), ptr(lab), ptr(lcls), ptr(a_dev), a_dev.numel(), N, C, c.shape[2], c.shape[3],
+               H, W, Hl, Wl, ptr(data.cv_nearest_spans(H, Hl, u.device)), ptr(data.cv_nearest_spans(W, Wl, u.device)), ptr(hist), stream())
+
+
+def _best_of_hist(hist, alphas, num_classes):
+    miou = torch.empty(len(alphas), dtype=torch.float32, device=hist.device)
+    lib().call("egm_ensemble_miou", ptr(hist), len(alphas), num_classes, ptr(miou), stream())
+    m = miou.cpu().numpy()
+    best, best_miou = 0.0, 0.0
+    for a, v in zip(alphas, m):
+        if v > best_miou:
+            best_miou, best = float(v), float(a)
+    return best, best_miou, m
+
+
+def search_best_alpha_fullres(clip_logits_list, unet_logits_list, labels_u8_list, search_scale=(0.1, 10.0), search_step=100, num_classes=2,
+                              label_values=None, return_hist=False):
+    """eval_CLIPseg.py:656-723 as the reference scores it: for every alpha the UNet-size argmax is resized to the LABEL's size with
+    cv2.resize(INTER_NEAREST) (:696-702) and the confusion matrix is counted there, against the dataset's full-size masks.  Labels:
+    uint8 [Hl, Wl] per image (or [N, Hl, Wl] with [N, ...] logits), numpy or tensor, of any size per image; label_values as for
+    class_table (None = load_labels_from_mask's 255 -> 1, everything else -> 0).  search_best_alpha is the same search with the labels
+    shrunk to the UNet's size beforehand, which weighs every UNet pixel 1 instead of by the label pixels it covers.
+    -> (best_alpha, best_miou, miou per alpha), plus the int64 [S, C, C] matrices with return_hist; first maximum wins.
+    The nearest-neighbour rule is data.cv_nearest_table's (restated from OpenCV's source, not checked against a cv2 build)."""
+    require_gpu()
+    S, C = int(search_step), int(num_classes)
+    alphas = np.linspace(search_scale[0], search_scale[1], S)
+    dev = unet_logits_list[0].device
+    a_dev = torch.tensor(alphas, dtype=torch.float32, device=dev)
+    lcls = _class_table_dev(label_values, C, dev)
+    hist = torch.zeros((S, C, C), dtype=torch.int64, device=dev)
+    for c, u, t in zip(clip_logits_list, unet_logits_list, labels_u8_list):
+        _alpha_hist_fullres(c.to(dev), u.to(dev), _label_u8(t, dev), lcls, a_dev, hist)
+    best, best_miou, m = _best_of_hist(hist, alphas, C)
+    return (best, best_miou, m, hist) if return_hist else (best, best_miou, m)
+
+
 class EnsemblePredictor:
     """predict_CLIPseg.py per image (:438-534) as one object: a decoded uint8 photo [H0, W0, 3] already on the device goes in, the uint8
     mask [H0, W0] comes out.
@@ -160,6 +294,8 @@ class EnsemblePredictor:
         self.clip_size = (clip_size, clip_size) if isinstance(clip_size, int) else (int(clip_size[0]), int(clip_size[1]))
         self.clip_antialias = bool(clip_antialias)
         self._lut = _lut256(lut, self.num_classes, dev)
+        # the byte of every class on the host, for evaluate (None = class ids)
+        self._lut_values = None if lut is None else tuple(int(v) for v in torch.as_tensor(lut).flatten()[:self.num_classes].tolist())
         self._alpha = torch.empty(1, dtype=torch.float32, device=dev)
         self._alpha_value = None
         self.alpha = alpha
@@ -337,3 +473,62 @@ class EnsemblePredictor:
         best, best_miou, m = search_best_alpha(cl, ul, labels, search_scale, search_step, self.num_classes)
         self.alpha = best
         return best, best_miou, m
+
+    def search_alpha_fullres(self, images, gt_masks, search_scale=(0.1, 10.0), search_step=100, batch_size=None, label_values=None):
+        """search_best_alpha_fullres over this pipeline: the alpha grid search scored at each ground truth's own size, as the reference
+        scores it (eval_CLIPseg.py:656-723 with the dataset's full-size masks; search_alpha wants labels at the UNet's size).  gt_masks:
+        one uint8 [Hl, Wl] mask per image, numpy or tensor, of any size.  Every image's (or batch's) matrices are accumulated right
+        after its logits / logits_batch call, before the next replay overwrites the graph's buffers: nothing is cloned and nothing is
+        kept per image.  With batch_size the photos go through logits_batch over plan_batches, and a batch whose masks share a size is
+        one kernel call at N = its photos (padded rows are left out).  Sets self.alpha. -> (best, best_miou, miou per alpha)"""
+        images, gt_masks = list(images), list(gt_masks)
+        if len(images) != len(gt_masks):
+            raise ValueError(f"search_alpha_fullres: {len(images)} images and {len(gt_masks)} ground-truth masks")
+        S, C, dev = int(search_step), self.num_classes, self.device
+        alphas = np.linspace(search_scale[0], search_scale[1], S)
+        a_dev = torch.tensor(alphas, dtype=torch.float32, device=dev)
+        lcls = _class_table_dev(label_values, C, dev)
+        hist = torch.zeros((S, C, C), dtype=torch.int64, device=dev)
+        if batch_size is None:
+            for img, gt in zip(images, gt_masks):
+                c, u = self.logits(img)
+                _alpha_hist_fullres(c, u, _label_u8(gt, dev), lcls, a_dev, hist)
+        else:
+            for _, idx, pad in plan_batches([tuple(im.shape[:2]) for im in images], batch_size):
+                c, u = self.logits_batch([images[i] for i in idx] + [images[idx[-1]]] * pad)
+                labs = [_label_u8(gt_masks[i], dev) for i in idx]
+                if all(lab.shape == labs[0].shape for lab in labs):
+                    _alpha_hist_fullres(c[:len(idx)], u[:len(idx)], torch.cat(labs), lcls, a_dev, hist)
+                else:
+                    for row, lab in enumerate(labs):
+                        _alpha_hist_fullres(c[row:row + 1], u[row:row + 1], lab, lcls, a_dev, hist)
+        best, best_miou, m = _best_of_hist(hist, alphas, C)
+        self.alpha = best
+        return best, best_miou, m
+
+    def evaluate(self, images, gt_masks, batch_size=None):
+        """evaluating_indicator.py's compute_mIoU (:347-417) over this pipeline without the PNGs in between: every photo's mask
+        (__call__, or predict_batch over plan_batches with batch_size) is counted against its uint8 ground truth [H0, W0] (0/255 PNG
+        bytes, the reference's / 255 rule) on the device, one confusion_u8 call per photo or batch into one matrix, and one copy to the
+        host at the end.  The predictor's own lut says which byte is which class; a lut that maps two classes to one byte raises
+        ValueError.  A ground truth whose size differs from its photo's is left out and counted in report["skipped"] (:375-380).
+        -> score_report's dict plus "skipped"."""
+        images, gt_masks = list(images), list(gt_masks)
+        if len(images) != len(gt_masks):
+            raise ValueError(f"evaluate: {len(images)} images and {len(gt_masks)} ground-truth masks")
+        C, dev = self.num_classes, self.device
+        pred_values = tuple(range(C)) if self._lut_values is None else self._lut_values
+        class_table(pred_values, C)                                        # raises for a lut that is not invertible
+        hist = torch.zeros((C, C), dtype=torch.int64, device=dev)
+        keep = [i for i, (im, gt) in enumerate(zip(images, gt_masks)) if tuple(im.shape[:2]) == tuple(gt.shape)]
+        if batch_size is None:
+            for i in keep:
+                confusion_u8(self(images[i]), _label_u8(gt_masks[i], dev)[0], C, pred_values, None, out=hist)
+        else:
+            for _, idx, pad in plan_batches([tuple(images[i].shape[:2]) for i in keep], batch_size):
+                idx = [keep[k] for k in idx]
+                masks = self.predict_batch([images[i] for i in idx] + [images[idx[-1]]] * pad)
+                confusion_u8(masks[:len(idx)], torch.cat([_label_u8(gt_masks[i], dev) for i in idx]), C, pred_values, None, out=hist)
+        report = score_report(hist)
+        report["skipped"] = len(images) - len(keep)
+        return report

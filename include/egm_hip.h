@@ -689,6 +689,32 @@ int egm_clip_preprocess_batch_u8(const void* imgs_bhwc3, int B, int H, int W, fl
                                  const float* xweights, int xksize, const int* ybounds, const float* yweights, int yksize,
                                  const float* mean3_host, const float* std3_host, float* tmp_cbhw, egm_stream_t s);
 
+/* ---- ensemble scoring at the ground truth's size (evaluating_indicator.py:347-417, eval_CLIPseg.py:682-711) ---------------------
+ * Both accumulate exact integer counts into caller-zeroed uint64 matrices (hist[label class][predicted class], across calls), in one
+ * launch each, and are capturable.  C <= 4; na <= 128.  A class table is 256 bytes of DEVICE memory, byte value -> class; a value
+ * >= C drops the pixel.
+ * egm_mask_confusion_u8: hist[label_cls[label[i]]][pred_cls[pred[i]]] += 1 for the npix pixels of two uint8 images (a batch
+ *   [N][H0][W0] is npix = N*H0*W0).  One streaming pass with 16-byte loads in the body; any base alignment of either image and any
+ *   npix >= 1.  Partial counts are 32 bits per lane and summed in 64 bits per workgroup, then at most C*C 64-bit atomics per
+ *   workgroup; a lane counts fewer than 2^22 pixels at any admitted size, and npix > 2^40 is refused (EGM_ERR_ARG).
+ * egm_ensemble_alpha_hist_u8: the alpha grid search scored at the label's size.  hist [na][C][C] (the layout egm_ensemble_miou
+ *   reads): hist[a][t][p] = number of label pixels (n, Y, X) of class t = label_cls[labels[n][Y][X]] whose source pixel
+ *   (yidx[Y], xidx[X]) has fused argmax p under alphas[a], where yidx / xidx are the nearest-neighbour tables of
+ *   cv2.resize(pred, (Wl, Hl), INTER_NEAREST) from H x W.  The tables come in as their spans: ybeg [H+1] / xbeg [W+1] int32,
+ *   non-decreasing, beg[i] = the first label index whose source is >= i and beg[H] = Hl, so source pixel (y, x) owns the label
+ *   rectangle [ybeg[y], ybeg[y+1]) x [xbeg[x], xbeg[x+1]) (empty for some pixels when the label is the smaller one).  The
+ *   rectangle's classes are counted once and the na argmaxes run once per SOURCE pixel: one read of the labels plus N*H*W*na
+ *   argmaxes whatever the label's size (one lane per source pixel counts and stages, then one lane per alpha accumulates).
+ *   Fused value and argmax are those of egm_ensemble_mask_u8 (csrc/ensemble_fuse.h, ties to the lowest class): bit-identical to
+ *   running it once per alpha with lut = NULL and counting.  labels: uint8 [N][Hl][Wl]; logits as for egm_ensemble_fuse.
+ *   Partial counts are 32 bits per lane, then per workgroup; either is at most the call's label pixels, so N*Hl*Wl >= 2^32 is
+ *   refused (EGM_ERR_ARG): split such a batch. */
+int egm_mask_confusion_u8(const unsigned char* pred, const unsigned char* label, long long npix, const unsigned char* pred_cls,
+                          const unsigned char* label_cls, int C, unsigned long long* hist, egm_stream_t s);
+int egm_ensemble_alpha_hist_u8(const float* clip_logits, const float* unet_logits, const unsigned char* labels,
+                               const unsigned char* label_cls, const float* alphas, int na, int N, int C, int hc, int wc, int H, int W,
+                               int Hl, int Wl, const int* ybeg, const int* xbeg, unsigned long long* hist, egm_stream_t s);
+
 /* ---- batched training data path: B ragged photos with masks -> the batch a train step reads (train.py:14-33, my_dataset.py:118-132)
  * egm_train_batch_u8: for every image b what egm_resample_u8 (axis 1, then axis 0), egm_gather_u8 and egm_augment_u8 compute one
  *   after the other, written into slot b of out_img_bchw fp32 [B][3][slot_h][slot_w] and out_target_bhw int64 [B][slot_h][slot_w]: per
