@@ -1,5 +1,5 @@
 // The fused logit of the CLIPSeg (+) UNet ensemble (predict_CLIPseg.py:501-525), shared by every kernel that evaluates it
-// (loss.hip: egm_ensemble_fuse, egm_ensemble_alpha_hist; ensemble_pipe.hip: egm_ensemble_mask_u8), so that all of them produce the
+// (ensemble_score.hip: egm_ensemble_fuse, egm_ensemble_alpha_hist; ensemble_pipe.hip: egm_ensemble_mask_u8), so that all of them produce the
 // same bits: fused = bilinear(clip_logits -> HxW, align_corners=False) + alpha * unet_logits, argmax with ties to the lowest class.
 #pragma once
 #include "common.h"

@@ -98,35 +98,10 @@ __global__ __launch_bounds__(256) void clip_hfilter_u8_kernel(const unsigned cha
     }
 }
 
-// vertical pass over the fp32 intermediate + ToTensor / Normalize: out[c][yo][x] = (sum_j w[yo][j] * tmp[c][b0 + j][x] / 255 - mean) / std
-__global__ __launch_bounds__(256) void clip_vfilter_norm_kernel(const float* __restrict__ tmp, int H, int Sw, float* __restrict__ out, int Sh,
-                                                                const int* __restrict__ bounds, const float* __restrict__ wts, int ksize,
-                                                                float m0, float m1, float m2, float s0, float s1, float s2) {
-    __shared__ float wl[kClipMaxTaps];
-    const int yo = blockIdx.y;
-    const int b0 = clampi(bounds[yo * 2], 0, H - 1);
-    const int n = clampi(bounds[yo * 2 + 1], 0, min(ksize, H - b0));
-    if ((int)threadIdx.x < n) wl[threadIdx.x] = wts[(long long)yo * ksize + threadIdx.x];
-    __syncthreads();
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    if (x >= Sw) return;
-    const long long plane = (long long)H * Sw;
-    const float* p = tmp + (long long)b0 * Sw + x;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int j = 0; j < n; ++j) {
-        const float w = wl[j];
-        const float* q = p + (long long)j * Sw;
-        a0 += w * q[0]; a1 += w * q[plane]; a2 += w * q[2 * plane];
-    }
-    const long long oplane = (long long)Sh * Sw, o = (long long)yo * Sw + x;
-    out[o] = (a0 / 255.0f - m0) / s0;
-    out[oplane + o] = (a1 / 255.0f - m1) / s1;
-    out[2 * oplane + o] = (a2 / 255.0f - m2) / s2;
-}
-
-// The batched form of clip_vfilter_norm_kernel: blockIdx.z is the image.  The horizontal pass ran over the B * H rows of the whole
-// batch, so the intermediate is [3][B][H][Sw] (one plane set per image inside each channel); tap order and expressions per output
-// element are those of the per-image kernel.
+// Vertical pass over the fp32 intermediate + ToTensor / Normalize, blockIdx.z is the image:
+//   out[b][c][yo][x] = (sum_j w[yo][j] * tmp[c][b][b0 + j][x] / 255 - mean) / std
+// The horizontal pass ran over the B * H rows of the whole batch, so the intermediate is [3][B][H][Sw] (one plane set per image inside
+// each channel); a single photo is B = 1.
 __global__ __launch_bounds__(256) void clip_vfilter_norm_batch_kernel(const float* __restrict__ tmp, int B, int H, int Sw, float* __restrict__ out,
                                                                       int Sh, const int* __restrict__ bounds, const float* __restrict__ wts,
                                                                       int ksize, float m0, float m1, float m2, float s0, float s1, float s2) {
@@ -196,65 +171,52 @@ __global__ __launch_bounds__(256) void ensemble_mask_u8_kernel(const float* __re
 
 }  // namespace
 
-extern "C" int egm_clip_preprocess_u8(const void* img_hwc3, int H, int W, float* out_chw, int Sh, int Sw, const int* xbounds, const float* xweights,
-                                      int xksize, const int* ybounds, const float* yweights, int yksize, const float* mean3_host,
-                                      const float* std3_host, float* tmp_chw, egm_stream_t s) {
-    EGM_REQUIRE(img_hwc3 && out_chw && xbounds && xweights && ybounds && yweights && mean3_host && std3_host && tmp_chw,
-                "clip_preprocess_u8: null pointer");
-    EGM_REQUIRE(H > 0 && W > 0 && Sh > 0 && Sw > 0 && xksize > 0 && yksize > 0, "clip_preprocess_u8: bad shape");
-    EGM_REQUIRE((long long)H * W * 3 < (1ll << 31) && (long long)H * Sw * 3 < (1ll << 31), "clip_preprocess_u8: image too large");
+// Both CLIP preprocess entry points (`who` names the one that was called).  The horizontal kernel is row-independent and bounds its
+// aligned 16-byte staging by the buffer it is given, so it runs over the B * H rows of the batch as over one tall image (image b
+// starts b*H*W*3 bytes in, at any alignment); only the vertical pass needs the image index.  Two launches whatever B.
+static int clip_preprocess_launch(const char* who, const void* imgs_bhwc3, int B, int H, int W, float* out_bchw, int Sh, int Sw,
+                                  const int* xbounds, const float* xweights, int xksize, const int* ybounds, const float* yweights, int yksize,
+                                  const float* mean3_host, const float* std3_host, float* tmp_cbhw, egm_stream_t s) {
+    EGM_REQUIRE(imgs_bhwc3 && out_bchw && xbounds && xweights && ybounds && yweights && mean3_host && std3_host && tmp_cbhw,
+                "%s: null pointer", who);
+    EGM_REQUIRE(B > 0 && H > 0 && W > 0 && Sh > 0 && Sw > 0 && xksize > 0 && yksize > 0, "%s: bad shape", who);
+    EGM_REQUIRE((long long)B * H * W * 3 < (1ll << 31) && (long long)B * H * Sw * 3 < (1ll << 31) && (long long)B * 3 * Sh * Sw < (1ll << 31),
+                "%s: input too large", who);
+    EGM_REQUIRE(B <= 65535 && Sh <= 65535 && egm_cdiv((long long)B * H, kClipRows) <= 65535, "%s: too many rows for one launch", who);
     EGM_REQUIRE(xksize <= kClipMaxTaps && yksize <= kClipMaxTaps,
-                "clip_preprocess_u8: %d x %d filter taps, at most %d per axis are supported (an antialiased reduction by up to 31.5)", yksize,
-                xksize, kClipMaxTaps);
-    EGM_REQUIRE(std3_host[0] != 0.f && std3_host[1] != 0.f && std3_host[2] != 0.f, "clip_preprocess_u8: zero std");
+                "%s: %d x %d filter taps, at most %d per axis are supported (an antialiased reduction by up to 31.5)", who, yksize, xksize,
+                kClipMaxTaps);
+    EGM_REQUIRE(std3_host[0] != 0.f && std3_host[1] != 0.f && std3_host[2] != 0.f, "%s: zero std", who);
     // input pixels the 64 output columns of a workgroup can span: 63 steps of the scale plus one window (both table rules)
     long long cap = (63ll * W + Sw - 1) / Sw + xksize + 2;
     if (cap > W) cap = W;
     const long long rowbuf = (cap * 3 + 15 + 15) & ~15ll;
     const long long lds = (long long)xksize * 256 + 4 * rowbuf;
-    EGM_REQUIRE(lds <= kClipMaxLds, "clip_preprocess_u8: a reduction of %d -> %d columns needs %lld bytes of LDS per workgroup, at most %d are supported",
-                W, Sw, lds, kClipMaxLds);
-    hipLaunchKernelGGL(clip_hfilter_u8_kernel, dim3(egm_cdiv(Sw, 64), egm_cdiv(H, kClipRows)), dim3(256), (size_t)lds, (hipStream_t)s,
-                       (const unsigned char*)img_hwc3, H, W, tmp_chw, Sw, xbounds, xweights, xksize, (int)cap, (int)rowbuf);
-    EGM_CHECK_LAUNCH("clip_preprocess_u8 (horizontal)");
-    hipLaunchKernelGGL(clip_vfilter_norm_kernel, dim3(egm_cdiv(Sw, 256), Sh), dim3(256), 0, (hipStream_t)s, (const float*)tmp_chw, H, Sw, out_chw, Sh,
-                       ybounds, yweights, yksize, mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0], std3_host[1], std3_host[2]);
-    EGM_CHECK_LAUNCH("clip_preprocess_u8 (vertical)");
-    return EGM_OK;
-}
-
-// B photos of one size: the horizontal kernel is row-independent and bounds its aligned 16-byte staging by the buffer it is given,
-// so it runs unchanged over the B * H rows of the batch (image b starts b*H*W*3 bytes in, at any alignment); only the vertical pass
-// needs the image index.  Two launches whatever B.
-extern "C" int egm_clip_preprocess_batch_u8(const void* imgs_bhwc3, int B, int H, int W, float* out_bchw, int Sh, int Sw, const int* xbounds,
-                                            const float* xweights, int xksize, const int* ybounds, const float* yweights, int yksize,
-                                            const float* mean3_host, const float* std3_host, float* tmp_cbhw, egm_stream_t s) {
-    EGM_REQUIRE(imgs_bhwc3 && out_bchw && xbounds && xweights && ybounds && yweights && mean3_host && std3_host && tmp_cbhw,
-                "clip_preprocess_batch_u8: null pointer");
-    EGM_REQUIRE(B > 0 && H > 0 && W > 0 && Sh > 0 && Sw > 0 && xksize > 0 && yksize > 0, "clip_preprocess_batch_u8: bad shape");
-    EGM_REQUIRE((long long)B * H * W * 3 < (1ll << 31) && (long long)B * H * Sw * 3 < (1ll << 31) && (long long)B * 3 * Sh * Sw < (1ll << 31),
-                "clip_preprocess_batch_u8: batch too large");
-    EGM_REQUIRE(B <= 65535 && Sh <= 65535 && egm_cdiv((long long)B * H, kClipRows) <= 65535, "clip_preprocess_batch_u8: too many rows for one launch");
-    EGM_REQUIRE(xksize <= kClipMaxTaps && yksize <= kClipMaxTaps,
-                "clip_preprocess_batch_u8: %d x %d filter taps, at most %d per axis are supported (an antialiased reduction by up to 31.5)",
-                yksize, xksize, kClipMaxTaps);
-    EGM_REQUIRE(std3_host[0] != 0.f && std3_host[1] != 0.f && std3_host[2] != 0.f, "clip_preprocess_batch_u8: zero std");
-    long long cap = (63ll * W + Sw - 1) / Sw + xksize + 2;                     // as in egm_clip_preprocess_u8
-    if (cap > W) cap = W;
-    const long long rowbuf = (cap * 3 + 15 + 15) & ~15ll;
-    const long long lds = (long long)xksize * 256 + 4 * rowbuf;
-    EGM_REQUIRE(lds <= kClipMaxLds,
-                "clip_preprocess_batch_u8: a reduction of %d -> %d columns needs %lld bytes of LDS per workgroup, at most %d are supported", W, Sw,
-                lds, kClipMaxLds);
+    EGM_REQUIRE(lds <= kClipMaxLds, "%s: a reduction of %d -> %d columns needs %lld bytes of LDS per workgroup, at most %d are supported", who, W,
+                Sw, lds, kClipMaxLds);
     const int rows = B * H;
     hipLaunchKernelGGL(clip_hfilter_u8_kernel, dim3(egm_cdiv(Sw, 64), egm_cdiv(rows, kClipRows)), dim3(256), (size_t)lds, (hipStream_t)s,
                        (const unsigned char*)imgs_bhwc3, rows, W, tmp_cbhw, Sw, xbounds, xweights, xksize, (int)cap, (int)rowbuf);
-    EGM_CHECK_LAUNCH("clip_preprocess_batch_u8 (horizontal)");
+    EGM_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(clip_vfilter_norm_batch_kernel, dim3(egm_cdiv(Sw, 256), Sh, B), dim3(256), 0, (hipStream_t)s, (const float*)tmp_cbhw, B, H,
                        Sw, out_bchw, Sh, ybounds, yweights, yksize, mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0], std3_host[1],
                        std3_host[2]);
-    EGM_CHECK_LAUNCH("clip_preprocess_batch_u8 (vertical)");
+    EGM_CHECK_LAUNCH(who);
     return EGM_OK;
+}
+
+extern "C" int egm_clip_preprocess_u8(const void* img_hwc3, int H, int W, float* out_chw, int Sh, int Sw, const int* xbounds, const float* xweights,
+                                      int xksize, const int* ybounds, const float* yweights, int yksize, const float* mean3_host,
+                                      const float* std3_host, float* tmp_chw, egm_stream_t s) {
+    return clip_preprocess_launch("clip_preprocess_u8", img_hwc3, 1, H, W, out_chw, Sh, Sw, xbounds, xweights, xksize, ybounds, yweights, yksize,
+                                  mean3_host, std3_host, tmp_chw, s);
+}
+
+extern "C" int egm_clip_preprocess_batch_u8(const void* imgs_bhwc3, int B, int H, int W, float* out_bchw, int Sh, int Sw, const int* xbounds,
+                                            const float* xweights, int xksize, const int* ybounds, const float* yweights, int yksize,
+                                            const float* mean3_host, const float* std3_host, float* tmp_cbhw, egm_stream_t s) {
+    return clip_preprocess_launch("clip_preprocess_batch_u8", imgs_bhwc3, B, H, W, out_bchw, Sh, Sw, xbounds, xweights, xksize, ybounds, yweights,
+                                  yksize, mean3_host, std3_host, tmp_cbhw, s);
 }
 
 extern "C" int egm_ensemble_mask_u8(const float* clip_logits, const float* unet_logits, const float* alpha_dev, int N, int C, int hc, int wc, int H,

@@ -13,7 +13,6 @@ and the same for photos in batches (B photos of one size per replayed graph, bot
     masks = ens.predict_many(photos, 8)     # photos of any sizes -> their masks in input order, grouped by plan_batches
 """
 import collections
-import itertools
 
 import numpy as np
 import torch
@@ -21,9 +20,8 @@ import torch
 from . import data, ops
 from .clip import ops as clip_ops
 from ._lib import lib, ptr, require_gpu, stream
-from .infer import Predictor
-
-_serial = itertools.count()
+from .infer import Predictor, lut256
+from .replay import ReplayCache
 
 
 def fuse_predict(clip_logits, unet_logits, alpha, return_fused=False):
@@ -51,23 +49,7 @@ def search_best_alpha(clip_logits_list, unet_logits_list, labels_list, search_sc
         t = torch.as_tensor(t).to(dev).to(torch.int64).reshape(u.shape[0], u.shape[2], u.shape[3]).contiguous()
         lib().call("egm_ensemble_alpha_hist", ptr(c), ptr(u), ptr(t), ptr(a_dev), search_step, u.shape[0], u.shape[1], c.shape[2], c.shape[3],
                    u.shape[2], u.shape[3], ptr(hist), stream())
-    miou = torch.empty(search_step, dtype=torch.float32, device=dev)
-    lib().call("egm_ensemble_miou", ptr(hist), search_step, num_classes, ptr(miou), stream())
-    m = miou.cpu().numpy()
-    best, best_miou = 0.0, 0.0
-    for a, v in zip(alphas, m):
-        if v > best_miou:
-            best_miou, best = float(v), float(a)
-    return best, best_miou, m
-
-
-def _lut256(lut, C, device):
-    if lut is None:
-        return None
-    lt = torch.as_tensor(lut).to(torch.uint8).flatten()
-    if lt.numel() < C or lt.numel() > 256:
-        raise ValueError(f"lut must have between {C} and 256 entries, got {lt.numel()}")
-    return torch.cat([lt.cpu(), torch.zeros(256 - lt.numel(), dtype=torch.uint8)]).to(device)
+    return _best_of_hist(hist, alphas, num_classes)
 
 
 def fuse_mask(clip_logits, unet_logits, alpha, out_size, lut=None, out=None):
@@ -87,7 +69,7 @@ def fuse_mask(clip_logits, unet_logits, alpha, out_size, lut=None, out=None):
     if not (isinstance(alpha, torch.Tensor) and alpha.is_cuda and alpha.dtype == torch.float32 and alpha.numel() == 1):
         alpha = torch.full((1,), float(alpha), dtype=torch.float32, device=u.device)
     if not (isinstance(lut, torch.Tensor) and lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 256):
-        lut = _lut256(lut, C, u.device)
+        lut = lut256(lut, C, u.device)
     if out is None:
         out = torch.empty((N, H0, W0), dtype=torch.uint8, device=u.device)
     lib().call("egm_ensemble_mask_u8", ptr(c), ptr(u), ptr(alpha), N, C, hc, wc, H, W, ptr(data.cv_nearest_table(H, H0, u.device)),
@@ -113,6 +95,15 @@ def plan_batches(sizes, batch_size):
             part = idx[k:k + batch_size]
             plan.append((size, part, batch_size - len(part)))
     return plan
+
+
+def _padded_batches(photos, batch_size, keep=None):
+    """plan_batches over photos (over photos[i] for i in keep, when given) -> per batch (input indices, the batch's photos with a short
+    group filled up with its last photo, so every batch of a size replays the same graph)."""
+    keep = range(len(photos)) if keep is None else keep
+    for _, part, pad in plan_batches([tuple(photos[i].shape[:2]) for i in keep], batch_size):
+        idx = [keep[k] for k in part]
+        yield idx, [photos[i] for i in idx] + [photos[idx[-1]]] * pad
 
 
 _MAX_SCORE_CLASSES = 4                      # egm_mask_confusion_u8 / egm_ensemble_alpha_hist_u8
@@ -253,10 +244,10 @@ class EnsemblePredictor:
     """predict_CLIPseg.py per image (:438-534) as one object: a decoded uint8 photo [H0, W0, 3] already on the device goes in, the uint8
     mask [H0, W0] comes out.
 
-      UNet branch    data.resize_bilinear(img, base_size) (Pillow-exact, transforms.Resize(base_size) of the PIL image) -> data.augment
-                     (ToTensor, Normalize(unet_mean, unet_std)) -> the folded forward of an infer.Predictor
-      CLIPSeg branch data.clip_preprocess (ToTensor, Normalize(clip_mean, clip_std), Resize((clip_size, clip_size)) of the tensor) ->
-                     the model's multi-prompt decoder on one backbone pass, in the model's compute dtype
+      UNet branch    data.unet_preprocess_batch: bit for bit data.resize_bilinear(img, base_size) (Pillow-exact, transforms.Resize(base_size)
+                     of the PIL image) -> data.augment (ToTensor, Normalize(unet_mean, unet_std)) -> the folded forward of an infer.Predictor
+      CLIPSeg branch data.clip_preprocess_batch (ToTensor, Normalize(clip_mean, clip_std), Resize((clip_size, clip_size)) of the tensor;
+                     bit for bit data.clip_preprocess) -> the model's multi-prompt decoder on one backbone pass, in its compute dtype
       tail           fuse_mask: clip + alpha * unet -> argmax -> nearest resize to the photo's size -> lut
 
     prompts: K strings or a [K, 512] tensor, K = the UNet's class count; the conditional vectors are computed once.  dtype: the UNet's
@@ -272,9 +263,10 @@ class EnsemblePredictor:
     bump) drops the captured graphs and recomputes the conditionals, because the cast-weight
     caches move to new buffers then.
 
-    predict_batch / logits_batch / predict_many run B photos of one size through the same pipeline at batch B (_run_batch) under the
-    same protocol, keyed by (B, H0, W0): batched and per-image entries share max_graphs and its eviction order, alpha, the lut, the
-    conditionals and every drop rule above.  Results are per image: nothing in either model reduces over the batch."""
+    predict_batch / logits_batch / predict_many run B photos of one size through the same pipeline at batch B (_run_batch; the
+    per-image call is its batch of one) under the same protocol (replay.ReplayCache), keyed by (B, H0, W0): batched and per-image
+    entries share max_graphs and its eviction order, alpha, the lut, the conditionals and every drop rule above.  Results are per
+    image: nothing in either model reduces over the batch."""
 
     def __init__(self, unet, clipseg, prompts, alpha=0.5, unet_mean=(0.709, 0.381, 0.224), unet_std=(0.127, 0.079, 0.043), base_size=565,
                  clip_size=352, clip_antialias=True, lut=(0, 255), dtype=None, graph=True, max_graphs=4, clip_mean=(0.485, 0.456, 0.406),
@@ -293,17 +285,16 @@ class EnsemblePredictor:
         self.base_size = int(base_size)
         self.clip_size = (clip_size, clip_size) if isinstance(clip_size, int) else (int(clip_size[0]), int(clip_size[1]))
         self.clip_antialias = bool(clip_antialias)
-        self._lut = _lut256(lut, self.num_classes, dev)
+        self._lut = lut256(lut, self.num_classes, dev)
         # the byte of every class on the host, for evaluate (None = class ids)
         self._lut_values = None if lut is None else tuple(int(v) for v in torch.as_tensor(lut).flatten()[:self.num_classes].tolist())
         self._alpha = torch.empty(1, dtype=torch.float32, device=dev)
         self._alpha_value = None
         self.alpha = alpha
         self.graph = bool(graph)
-        self.max_graphs = max(1, int(max_graphs))
-        self.num_captures = 0
-        # (H0, W0) of a photo or (B, H0, W0) of a batch -> {"tag", "graph", "img", "out": (mask, clip logits, unet logits)}
-        self._graphs = collections.OrderedDict()
+        self._replay = ReplayCache("ensemble", max_graphs)
+        # (H0, W0) of a photo or (B, H0, W0) of a batch -> {"tag", "graph", "src", "out": (mask, clip logits, unet logits)}
+        self._graphs = self._replay.entries
         self._clip_tensors = list(clipseg.parameters()) + list(clipseg.buffers())
         self._clip_stamp = None
         self._condT = None
@@ -333,19 +324,13 @@ class EnsemblePredictor:
 
     # ---- the pipeline (eager, or being captured)
     def _run(self, img):
-        H0, W0, _ = img.shape
-        r = data.resize_bilinear(img, self.base_size)
-        x, _ = data.augment(r, None, False, False, 0, 0, r.shape[0], r.shape[1], self.unet_mean, self.unet_std)
-        unet_l = self._unet(x.unsqueeze(0))["out"]
-        xc = data.clip_preprocess(img, self.clip_size, self.clip_mean, self.clip_std, self.clip_antialias)
-        out = self.clipseg._decode_multi(xc, self._condT)
-        clip_l = out.view(1, self._condT.shape[0], out.shape[-2], out.shape[-1])
-        mask = fuse_mask(clip_l, unet_l, self._alpha, (H0, W0), self._lut)
+        """One photo [H0, W0, 3] is the batch of one -> (mask [H0, W0], clip logits [1, K, ch, cw], unet logits [1, C, h, w])."""
+        mask, clip_l, unet_l = self._run_batch(img.unsqueeze(0))
         return mask[0], clip_l, unet_l
 
     def _run_batch(self, imgs):
-        """_run for B photos of one size [B, H0, W0, 3]: both preprocessing chains in launches that cover the whole batch, both models
-        at batch B, the tail at N = B -> (masks [B, H0, W0], clip logits [B, K, ch, cw], unet logits [B, C, h, w])."""
+        """B photos of one size [B, H0, W0, 3]: both preprocessing chains in launches that cover the whole batch, both models at
+        batch B, the tail at N = B -> (masks [B, H0, W0], clip logits [B, K, ch, cw], unet logits [B, C, h, w])."""
         B, H0, W0, _ = imgs.shape
         x = data.unet_preprocess_batch(imgs, self.base_size, self.unet_mean, self.unet_std)
         unet_l = self._unet(x)["out"]
@@ -356,38 +341,11 @@ class EnsemblePredictor:
         return mask, clip_l, unet_l
 
     def _replayed(self, key, src, run):
-        """The graph protocol of every entry: `run(src)` eagerly (graph=False), or per key the warm-up call, the capturing call and the
-        replays.  key: (H0, W0) for one photo, (B, H0, W0) for a batch; both kinds share the table, its limit and its eviction order."""
+        """`run(src)` eagerly (graph=False), or through the replay cache.  key: (H0, W0) for one photo, (B, H0, W0) for a batch; both
+        kinds share the table, its limit and its eviction order."""
         with torch.no_grad():
             self._refresh()
-            if not self.graph:
-                return run(src)
-            ent = self._graphs.get(key)
-            if ent is None:
-                while len(self._graphs) >= self.max_graphs:
-                    self._drop(next(iter(self._graphs)))
-                ent = {"tag": ("ensemble", next(_serial)), "graph": None, "img": None, "out": None}
-                try:
-                    with ops.table_namespace(ent["tag"]):          # warm-up: tables, positional embedding, cast weights, allocator
-                        out = run(src)
-                except BaseException:
-                    ops.drop_table_namespace(ent["tag"])
-                    raise
-                self._graphs[key] = ent                            # only a size that warmed up is captured by the next call
-                return out
-            self._graphs.move_to_end(key)
-            if ent["graph"] is None:
-                ent["img"] = src.detach().clone(memory_format=torch.contiguous_format)
-                g = torch.cuda.CUDAGraph(keep_graph=True)
-                with ops.table_namespace(ent["tag"]), torch.cuda.graph(g):
-                    ent["out"] = run(ent["img"])
-                g.instantiate()
-                ent["graph"] = g
-                self.num_captures += 1
-            else:
-                ent["img"].copy_(src)
-            ent["graph"].replay()
-            return ent["out"]
+            return self._replay(key, src, run) if self.graph else run(src)
 
     def _call(self, img):
         img = data._check_u8(img, 3)
@@ -433,21 +391,18 @@ class EnsemblePredictor:
         batch_size; a short last group is filled up with its last photo, so every batch of a size replays the same graph."""
         photos = list(photos)
         masks = [None] * len(photos)
-        for _, idx, pad in plan_batches([tuple(p.shape[:2]) for p in photos], batch_size):
-            out = self.predict_batch([photos[i] for i in idx] + [photos[idx[-1]]] * pad)
+        for idx, batch in _padded_batches(photos, batch_size):
+            out = self.predict_batch(batch)
             for row, i in enumerate(idx):
                 masks[i] = out[row].clone()
         return masks
 
-    def _drop(self, key):
-        ent = self._graphs.pop(key)
-        ent["graph"] = None
-        ops.drop_table_namespace(ent["tag"])
+    max_graphs = property(lambda self: self._replay.max_graphs)
+    num_captures = property(lambda self: self._replay.num_captures)
 
     def reset_graphs(self):
         """Forget every captured graph (the next call at each photo size warms up again)."""
-        for key in list(self._graphs):
-            self._drop(key)
+        self._replay.reset()
 
     def captured_graph(self, size):
         """The captured torch.cuda.CUDAGraph of photo size (H0, W0), or of the batch (B, H0, W0), or None (for tools that count its
@@ -466,8 +421,8 @@ class EnsemblePredictor:
             for i, img in enumerate(images):
                 cl[i], ul[i] = self.logits(img, clone=True)
         else:
-            for _, idx, pad in plan_batches([tuple(im.shape[:2]) for im in images], batch_size):
-                c, u = self.logits_batch([images[i] for i in idx] + [images[idx[-1]]] * pad)
+            for idx, batch in _padded_batches(images, batch_size):
+                c, u = self.logits_batch(batch)
                 for row, i in enumerate(idx):
                     cl[i], ul[i] = c[row:row + 1].clone(), u[row:row + 1].clone()
         best, best_miou, m = search_best_alpha(cl, ul, labels, search_scale, search_step, self.num_classes)
@@ -494,8 +449,8 @@ class EnsemblePredictor:
                 c, u = self.logits(img)
                 _alpha_hist_fullres(c, u, _label_u8(gt, dev), lcls, a_dev, hist)
         else:
-            for _, idx, pad in plan_batches([tuple(im.shape[:2]) for im in images], batch_size):
-                c, u = self.logits_batch([images[i] for i in idx] + [images[idx[-1]]] * pad)
+            for idx, batch in _padded_batches(images, batch_size):
+                c, u = self.logits_batch(batch)
                 labs = [_label_u8(gt_masks[i], dev) for i in idx]
                 if all(lab.shape == labs[0].shape for lab in labs):
                     _alpha_hist_fullres(c[:len(idx)], u[:len(idx)], torch.cat(labs), lcls, a_dev, hist)
@@ -525,9 +480,8 @@ class EnsemblePredictor:
             for i in keep:
                 confusion_u8(self(images[i]), _label_u8(gt_masks[i], dev)[0], C, pred_values, None, out=hist)
         else:
-            for _, idx, pad in plan_batches([tuple(images[i].shape[:2]) for i in keep], batch_size):
-                idx = [keep[k] for k in idx]
-                masks = self.predict_batch([images[i] for i in idx] + [images[idx[-1]]] * pad)
+            for idx, batch in _padded_batches(images, batch_size, keep):
+                masks = self.predict_batch(batch)
                 confusion_u8(masks[:len(idx)], torch.cat([_label_u8(gt_masks[i], dev) for i in idx]), C, pred_values, None, out=hist)
         report = score_report(hist)
         report["skipped"] = len(images) - len(keep)

@@ -10,8 +10,6 @@ as a hipGraph per input shape (the reference's predict.py:64-75 / predict_CLIPse
 The predictor always uses the running statistics, whatever model.training is, and leaves the model as it found it (training flags,
 parameters, buffers, num_batches_tracked).  model(x) itself is unchanged in train and eval mode.
 """
-import collections
-import itertools
 import struct
 import types
 
@@ -20,10 +18,20 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import dtype_code, lib, ptr, require_gpu, stream
+from .replay import ReplayCache
 
 _FOLD_ENTRY = struct.Struct("<8Qf9i")             # egm_conv_fold_pack_multi table entry (include/egm_hip.h), 104 bytes
-_serial = itertools.count()
 _MISSING = object()
+
+
+def lut256(lut, C, device, who="lut"):
+    """A colour map (None, or a sequence / tensor of C..256 values) as the 256-entry uint8 table on the device the mask kernels read."""
+    if lut is None:
+        return None
+    lt = torch.as_tensor(lut).to(torch.uint8).flatten()
+    if lt.numel() < C or lt.numel() > 256:
+        raise ValueError(f"{who} must have between {C} and 256 entries, got {lt.numel()}")
+    return torch.cat([lt.cpu(), torch.zeros(256 - lt.numel(), dtype=torch.uint8)]).to(device)
 
 
 def _conv_bn_pairs(model):
@@ -71,9 +79,8 @@ class Predictor:
         self.dtype = model.compute_dtype if dtype is None else dtype
         dtype_code(self.dtype)
         self.graph = bool(graph)
-        self.max_graphs = max(1, int(max_graphs))
-        self.num_captures = 0
-        self._graphs = collections.OrderedDict()     # (N, H, W, dtype) -> {"tag", "graph", "x", "out"}
+        self._replay = ReplayCache("infer", max_graphs)
+        self._graphs = self._replay.entries          # (N, H, W, dtype) -> {"tag", "graph", "src", "out"}
         self._tensors = params + list(model.buffers())
         self._stamp = None
         dev = params[0].device
@@ -174,54 +181,22 @@ class Predictor:
             if not self.graph:
                 out = self._forward(x)
             else:
-                key = (x.shape[0], x.shape[2], x.shape[3], self.dtype)
-                ent = self._graphs.get(key)
-                if ent is None:
-                    while len(self._graphs) >= self.max_graphs:
-                        self._drop(next(iter(self._graphs)))
-                    ent = self._graphs[key] = {"tag": ("infer", next(_serial)), "graph": None, "x": None, "out": None}
-                    with ops.table_namespace(ent["tag"]):          # warm-up: allocator, device tables, lazy kernel attributes
-                        out = self._forward(x)
-                elif ent["graph"] is None or ent["x"].shape != x.shape or ent["x"].dtype != x.dtype:
-                    self._graphs.move_to_end(key)
-                    ent["graph"] = None
-                    ent["x"] = x.detach().clone(memory_format=torch.contiguous_format)
-                    g = torch.cuda.CUDAGraph(keep_graph=True)          # the graph stays inspectable (raw_cuda_graph: kernel-node counts)
-                    with ops.table_namespace(ent["tag"]), torch.cuda.graph(g):
-                        ent["out"] = self._forward(ent["x"])
-                    g.instantiate()
-                    ent["graph"] = g
-                    self.num_captures += 1
-                    g.replay()
-                    out = ent["out"]
-                else:
-                    self._graphs.move_to_end(key)
-                    ent["x"].copy_(x)
-                    ent["graph"].replay()
-                    out = ent["out"]
+                out = self._replay((x.shape[0], x.shape[2], x.shape[3], self.dtype), x, self._forward)
         return {"out": out.clone() if clone else out}
 
-    def _drop(self, key):
-        ent = self._graphs.pop(key)
-        ent["graph"] = None
-        ops.drop_table_namespace(ent["tag"])
+    max_graphs = property(lambda self: self._replay.max_graphs)
+    num_captures = property(lambda self: self._replay.num_captures)
 
     def reset_graphs(self):
         """Forget every captured graph (the next call at each shape warms up again)."""
-        for key in list(self._graphs):
-            self._drop(key)
+        self._replay.reset()
 
     def predict_mask(self, x, lut=None):
         """-> uint8 [N, H, W] class ids (argmax over the logits, ties to the lowest class), mapped through lut when given (a sequence
         or tensor of <= 256 values, e.g. predict.py's color_map {0: 0, 1: 255} as [0, 255])."""
         logits = self(x)["out"]
         N, C, H, W = logits.shape
-        lt = None
-        if lut is not None:
-            lt = torch.as_tensor(lut).to(torch.uint8).flatten()
-            if lt.numel() < C or lt.numel() > 256:
-                raise ValueError(f"predict_mask: lut must have between {C} and 256 entries, got {lt.numel()}")
-            lt = torch.cat([lt, torch.zeros(256 - lt.numel(), dtype=torch.uint8)]).to(logits.device)
+        lt = lut256(lut, C, logits.device, "predict_mask: lut")
         mask = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device)
         lib().call("egm_argmax_u8", ptr(logits), ptr(lt), ptr(mask), N, C, H, W, stream())
         return mask

@@ -276,6 +276,28 @@ def test_graph_replay_matches_eager_and_evicts():
     assert torch.equal(pg(x)["out"], pe(x)["out"])
 
 
+def test_predictor_failed_warmup_is_not_captured():
+    """A first call that raises leaves no entry (and no table namespace) behind: the next call at that shape warms up eagerly again
+    before any capture.  The raising function is host Python and runs before any launch."""
+    from egm_unet_amd.infer import Predictor
+    m = _small_model(6)
+    pred, pe = Predictor(m, max_graphs=1), Predictor(m, graph=False)
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(1, 3, 64, 96, generator=g).to(DEV)
+    forward = pred._forward
+    pred._forward = lambda x: (_ for _ in ()).throw(RuntimeError("warm-up failed"))
+    with pytest.raises(RuntimeError, match="warm-up failed"):
+        pred(x)
+    pred._forward = forward
+    assert len(pred._graphs) == 0
+    ref = pe(x)["out"]
+    assert torch.equal(pred(x)["out"], ref) and pred.num_captures == 0         # the warm-up
+    assert torch.equal(pred(x)["out"], ref) and pred.num_captures == 1
+    x2 = torch.randn(1, 3, 96, 64, generator=g).to(DEV)                        # max_graphs=1: a second shape evicts the first key
+    assert torch.equal(pred(x2)["out"], pe(x2)["out"])
+    assert list(pred._graphs) == [(1, 96, 64, torch.float32)] and pred.num_captures == 1
+
+
 def test_refold_without_recapture():
     from egm_unet_amd.infer import Predictor
     m = _small_model(1)
