@@ -11,6 +11,11 @@ and the same for photos in batches (B photos of one size per replayed graph, bot
 
     masks = ens.predict_batch(imgs_u8)      # uint8 [B, H0, W0]; imgs_u8 is [B, H0, W0, 3] uint8 cuda, or a list of B photos
     masks = ens.predict_many(photos, 8)     # photos of any sizes -> their masks in input order, grouped by plan_batches
+
+and with a connected-component clean-up (postprocess.MaskCleanup) of the class map between the argmax and the resize, inside the graph:
+
+    ens = EnsemblePredictor(unet, clipseg, prompts, cleanup=MaskCleanup(min_area=0.002, max_hole=200))
+    ens.cleanup = MaskCleanup(min_area=0.004, max_hole=200)        # new numbers: followed by the captured graphs
 """
 import collections
 
@@ -21,6 +26,7 @@ from . import data, ops
 from .clip import ops as clip_ops
 from ._lib import lib, ptr, require_gpu, stream
 from .infer import Predictor, lut256
+from .postprocess import CleanupState, MaskCleanup, _state_for, clean_mask, label_components      # noqa: F401 (re-exported)
 from .replay import ReplayCache
 
 
@@ -74,6 +80,35 @@ def fuse_mask(clip_logits, unet_logits, alpha, out_size, lut=None, out=None):
         out = torch.empty((N, H0, W0), dtype=torch.uint8, device=u.device)
     lib().call("egm_ensemble_mask_u8", ptr(c), ptr(u), ptr(alpha), N, C, hc, wc, H, W, ptr(data.cv_nearest_table(H, H0, u.device)),
                ptr(data.cv_nearest_table(W, W0, u.device)), ptr(lut), ptr(out), H0, W0, stream())
+    return out
+
+
+def fuse_mask_clean(clip_logits, unet_logits, alpha, out_size, cleanup, lut=None, out=None, state=None):
+    """fuse_mask with a connected-component clean-up (postprocess.MaskCleanup) between the argmax and the nearest resize:
+    lut[clean(fuse_predict(...))][:, yidx][:, :, xidx] -> uint8 [N, H0, W0], bit for bit.  The class map at the UNet's size comes from
+    egm_ensemble_mask_u8 at out_size = (H, W) without a lut (the bytes of fuse_predict, alpha read on the device), the clean-up runs on
+    it, and its last pass writes the photo-size mask through the tables and the lut: ten launches instead of fuse_mask's one, whatever
+    the content and the rule's numbers.  A neutral rule gives fuse_mask's bytes.  alpha, lut, out as for fuse_mask; state: a
+    postprocess.CleanupState for [N, H, W] maps to work in (otherwise a private one per call)."""
+    require_gpu()
+    c, u = clip_logits.contiguous().float(), unet_logits.contiguous().float()
+    N, C, hc, wc = c.shape
+    if u.dim() != 4 or u.shape[0] != N or u.shape[1] != C:
+        raise ValueError(f"fuse_mask_clean: clip_logits {tuple(c.shape)} and unet_logits {tuple(u.shape)} must agree in N and C")
+    H, W = u.shape[2:]
+    H0, W0 = int(out_size[0]), int(out_size[1])
+    state = _state_for(state, cleanup, N, H, W, u.device, "fuse_mask_clean")
+    if not (isinstance(alpha, torch.Tensor) and alpha.is_cuda and alpha.dtype == torch.float32 and alpha.numel() == 1):
+        alpha = torch.full((1,), float(alpha), dtype=torch.float32, device=u.device)
+    if not (isinstance(lut, torch.Tensor) and lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 256):
+        lut = lut256(lut, C, u.device)
+    if out is None:
+        out = torch.empty((N, H0, W0), dtype=torch.uint8, device=u.device)
+    L, st = lib(), stream()
+    L.call("egm_ensemble_mask_u8", ptr(c), ptr(u), ptr(alpha), N, C, hc, wc, H, W, ptr(data.cv_nearest_table(H, H, u.device)),
+           ptr(data.cv_nearest_table(W, W, u.device)), None, ptr(state.cls), H, W, st)
+    L.call("egm_mask_clean_u8", ptr(state.cls), N, H, W, cleanup.connectivity, ptr(state.params), ptr(state.workspace), None,
+           ptr(data.cv_nearest_table(H, H0, u.device)), ptr(data.cv_nearest_table(W, W0, u.device)), ptr(lut), ptr(out), H0, W0, st)
     return out
 
 
@@ -266,12 +301,23 @@ class EnsemblePredictor:
     predict_batch / logits_batch / predict_many run B photos of one size through the same pipeline at batch B (_run_batch; the
     per-image call is its batch of one) under the same protocol (replay.ReplayCache), keyed by (B, H0, W0): batched and per-image
     entries share max_graphs and its eviction order, alpha, the lut, the conditionals and every drop rule above.  Results are per
-    image: nothing in either model reduces over the batch."""
+    image: nothing in either model reduces over the batch.
+
+    cleanup: None (the tail is fuse_mask, exactly the pipeline without this option) or a postprocess.MaskCleanup: the tail is
+    fuse_mask_clean, i.e. the class map at the UNet's size is cleaned between the argmax and the resize, inside the graph.  Every
+    result that is a mask goes through it (__call__, predict_batch, predict_many, evaluate); the logits do not.  The workspace and
+    the parameter table of a photo size are owned by the predictor, next to that size's graph; area fractions are resolved against
+    the UNet-size map of each photo size.  `ens.cleanup = MaskCleanup(...)` with other numbers only rewrites the tables (fill
+    kernels, no host wait, no new capture: every stage's launches are in the graph whatever the numbers); a switch between None
+    and a rule, or another connectivity, drops the captured graphs as a change of the compute dtype does.  cleanup_status() reads
+    the kernels' status words (0 = no device loop ever ran into its trip bound)."""
 
     def __init__(self, unet, clipseg, prompts, alpha=0.5, unet_mean=(0.709, 0.381, 0.224), unet_std=(0.127, 0.079, 0.043), base_size=565,
                  clip_size=352, clip_antialias=True, lut=(0, 255), dtype=None, graph=True, max_graphs=4, clip_mean=(0.485, 0.456, 0.406),
-                 clip_std=(0.229, 0.224, 0.225)):
+                 clip_std=(0.229, 0.224, 0.225), cleanup=None):
         require_gpu()
+        if cleanup is not None and not isinstance(cleanup, MaskCleanup):
+            raise ValueError("EnsemblePredictor: cleanup must be None or a MaskCleanup")
         self._unet = Predictor(unet, dtype=dtype, graph=False)
         self.clipseg = clipseg
         dev = next(self._unet.model.parameters()).device
@@ -298,6 +344,47 @@ class EnsemblePredictor:
         self._clip_tensors = list(clipseg.parameters()) + list(clipseg.buffers())
         self._clip_stamp = None
         self._condT = None
+        self._cleanup = cleanup
+        self._clean_states = collections.OrderedDict()     # (B, H0, W0) -> CleanupState of that size's UNet-size maps
+
+    # ---- clean-up: a rule whose numbers live in device tables the kernels read
+    @property
+    def cleanup(self):
+        return self._cleanup
+
+    @cleanup.setter
+    def cleanup(self, rule):
+        if rule is not None and not isinstance(rule, MaskCleanup):
+            raise ValueError("EnsemblePredictor: cleanup must be None or a MaskCleanup")
+        old, self._cleanup = self._cleanup, rule
+        if (old is None) != (rule is None) or (rule is not None and rule.connectivity != old.connectivity):
+            self.reset_graphs()                            # other launches in the tail
+        elif rule is not None:
+            for state in self._clean_states.values():
+                state.set(rule)
+
+    def cleanup_status(self):
+        """The OR of the status words of every live clean-up workspace (one small copy to the host each)."""
+        st = 0
+        for state in self._clean_states.values():
+            st |= state.status()
+        return st
+
+    def _clean_state(self, key, B, H, W):
+        state = self._clean_states.get(key)
+        if state is None or state.shape != (B, H, W):
+            state = self._clean_states[key] = CleanupState(B, H, W, self.device)
+        self._clean_states.move_to_end(key)
+        state.set(self._cleanup)
+        return state
+
+    def _prune_clean_states(self):
+        """Keep the states of the sizes that have a graph entry (graph=True), or the max_graphs most recent ones (eager)."""
+        if self.graph:
+            for key in [k for k in self._clean_states if k not in self._graphs and not (k[0] == 1 and k[1:] in self._graphs)]:
+                del self._clean_states[key]                # (a photo's entry is keyed (H0, W0), a batch's (B, H0, W0))
+        while len(self._clean_states) > self.max_graphs:
+            del self._clean_states[next(iter(self._clean_states))]
 
     # ---- alpha: a device scalar the fuse kernel reads
     @property
@@ -337,7 +424,11 @@ class EnsemblePredictor:
         xc = data.clip_preprocess_batch(imgs, self.clip_size, self.clip_mean, self.clip_std, self.clip_antialias)
         out = self.clipseg._decode_multi(xc, self._condT)
         clip_l = out.view(B, self._condT.shape[0], out.shape[-2], out.shape[-1])
-        mask = fuse_mask(clip_l, unet_l, self._alpha, (H0, W0), self._lut)
+        if self._cleanup is None:
+            mask = fuse_mask(clip_l, unet_l, self._alpha, (H0, W0), self._lut)
+        else:
+            state = self._clean_state((B, H0, W0), B, unet_l.shape[2], unet_l.shape[3])
+            mask = fuse_mask_clean(clip_l, unet_l, self._alpha, (H0, W0), self._cleanup, self._lut, state=state)
         return mask, clip_l, unet_l
 
     def _replayed(self, key, src, run):
@@ -345,7 +436,10 @@ class EnsemblePredictor:
         kinds share the table, its limit and its eviction order."""
         with torch.no_grad():
             self._refresh()
-            return self._replay(key, src, run) if self.graph else run(src)
+            out = self._replay(key, src, run) if self.graph else run(src)
+            if self._clean_states:
+                self._prune_clean_states()
+            return out
 
     def _call(self, img):
         img = data._check_u8(img, 3)
@@ -403,6 +497,7 @@ class EnsemblePredictor:
     def reset_graphs(self):
         """Forget every captured graph (the next call at each photo size warms up again)."""
         self._replay.reset()
+        self._clean_states.clear()
 
     def captured_graph(self, size):
         """The captured torch.cuda.CUDAGraph of photo size (H0, W0), or of the batch (B, H0, W0), or None (for tools that count its
@@ -414,7 +509,8 @@ class EnsemblePredictor:
         """eval_CLIPseg.py:656-723 over this pipeline: the logits of every image go through the alpha grid search (one confusion matrix per
         alpha over all images, first maximum wins); labels at the UNet's size [h, w].  batch_size=None collects the logits image by
         image; a number collects them through logits_batch over plan_batches (the grid search still gets them per image, in input
-        order).  Sets self.alpha. -> (best, best_miou, miou per alpha)"""
+        order).  The search scores the raw argmax of the fused logits: a cleanup rule is not applied here (evaluate scores the cleaned
+        masks).  Sets self.alpha. -> (best, best_miou, miou per alpha)"""
         images = list(images)
         cl, ul = [None] * len(images), [None] * len(images)
         if batch_size is None:
@@ -435,7 +531,8 @@ class EnsemblePredictor:
         one uint8 [Hl, Wl] mask per image, numpy or tensor, of any size.  Every image's (or batch's) matrices are accumulated right
         after its logits / logits_batch call, before the next replay overwrites the graph's buffers: nothing is cloned and nothing is
         kept per image.  With batch_size the photos go through logits_batch over plan_batches, and a batch whose masks share a size is
-        one kernel call at N = its photos (padded rows are left out).  Sets self.alpha. -> (best, best_miou, miou per alpha)"""
+        one kernel call at N = its photos (padded rows are left out).  Like search_alpha it scores the raw argmax, without the cleanup
+        rule.  Sets self.alpha. -> (best, best_miou, miou per alpha)"""
         images, gt_masks = list(images), list(gt_masks)
         if len(images) != len(gt_masks):
             raise ValueError(f"search_alpha_fullres: {len(images)} images and {len(gt_masks)} ground-truth masks")
@@ -467,6 +564,7 @@ class EnsemblePredictor:
         bytes, the reference's / 255 rule) on the device, one confusion_u8 call per photo or batch into one matrix, and one copy to the
         host at the end.  The predictor's own lut says which byte is which class; a lut that maps two classes to one byte raises
         ValueError.  A ground truth whose size differs from its photo's is left out and counted in report["skipped"] (:375-380).
+        With a cleanup rule the masks scored are the cleaned ones, so a rule can be judged by the mIoU it gives on a dataset.
         -> score_report's dict plus "skipped"."""
         images, gt_masks = list(images), list(gt_masks)
         if len(images) != len(gt_masks):

@@ -715,6 +715,31 @@ int egm_ensemble_alpha_hist_u8(const float* clip_logits, const float* unet_logit
                                const unsigned char* label_cls, const float* alphas, int na, int N, int C, int hc, int wc, int H, int W,
                                int Hl, int Wl, const int* ybeg, const int* xbeg, unsigned long long* hist, egm_stream_t s);
 
+/* ---- connected components of uint8 class maps and the mask clean-up on them (csrc/ccl.hip) -------------------------
+ * cls: uint8 [N][H][W], 0 = background; images are independent.  Two pixels are joined when they hold the same byte and are neighbours:
+ * `connectivity` (8 or 4) for foreground bytes, the dual (4 or 8) for background.  Any H, W >= 1 and any alignment; H*W <= 2^30,
+ * otherwise EGM_ERR_ARG.  Launch count and grids depend on the shapes only, every launch covers the batch, nothing waits for the
+ * device or for another workgroup, and every device loop has a trip bound derived from H*W.
+ * workspace: egm_ccl_workspace(N, H, W) bytes of device memory owned by the caller (egm_ccl_label_u8 touches only its first 256 bytes).
+ *   Its first int32 is a status word: a loop that ran into its bound ORs a bit in (1 find, 2 union) and leaves.  It is never cleared
+ *   by these calls: the caller zeroes it once and reads it whenever it likes; 0 = every call since then ran to completion.
+ * egm_ccl_label_u8: labels int32 [N][H][W] = raster index y*W + x of the first pixel, in raster order, of the pixel's component
+ *   (background components included); areas int32 [N][H][W] (may be NULL) = the pixel count at a component's first pixel, 0 elsewhere.
+ *   Three launches.
+ * egm_mask_clean_u8: params_dev = int32 {min_area, keep_largest, max_hole} in DEVICE memory (a captured graph follows new values).
+ *   Stage 1 (max_hole > 0): a background component that touches no image border and has at most max_hole pixels takes the byte of
+ *   the pixel left of its first pixel.  Stage 2 (min_area > 1 or keep_largest), on the relabelled result: a foreground component
+ *   smaller than min_area becomes 0; with keep_largest only the largest component of each byte value stays (ties: the smaller first
+ *   index), if it passes min_area.  Results: out_cls uint8 [N][H][W] (may be NULL), the cleaned map, and, when out != NULL,
+ *   out [N][H0][W0] = lut[cleaned[yidx[y]][xidx[x]]] written by the last pass itself (tables and lut as for egm_ensemble_mask_u8;
+ *   any alignment of out).  out_cls and out may not both be NULL.  Nine launches whatever the parameters. */
+long long egm_ccl_workspace(int N, int H, int W);
+int egm_ccl_label_u8(const unsigned char* cls, int N, int H, int W, int connectivity, int* labels, int* areas, void* workspace,
+                     egm_stream_t s);
+int egm_mask_clean_u8(const unsigned char* cls, int N, int H, int W, int connectivity, const int* params_dev, void* workspace,
+                      unsigned char* out_cls, const int* yidx, const int* xidx, const unsigned char* lut, unsigned char* out, int H0,
+                      int W0, egm_stream_t s);
+
 /* ---- batched training data path: B ragged photos with masks -> the batch a train step reads (train.py:14-33, my_dataset.py:118-132)
  * egm_train_batch_u8: for every image b what egm_resample_u8 (axis 1, then axis 0), egm_gather_u8 and egm_augment_u8 compute one
  *   after the other, written into slot b of out_img_bchw fp32 [B][3][slot_h][slot_w] and out_target_bhw int64 [B][slot_h][slot_w]: per

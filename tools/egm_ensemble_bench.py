@@ -14,6 +14,15 @@ of each graph.  A B whose photos exceed --max-batch-bytes (default 160 MB: B <= 
     python tools/egm_ensemble_bench.py --batches 1,2,4,8,16
     rocprofv3 --kernel-trace --stats -- python tools/egm_ensemble_bench.py --child 768x1024 --profile-one batch --profile-batch 8
 
+--cleanup MIN_AREA,MAX_HOLE,KEEP_LARGEST (e.g. 0.002,200,0; a value with a dot is a fraction of the map) measures the connected-component
+clean-up inside the graph in place of the above: per repeat the predictor with cleanup=None and the one with the rule alternate in one
+process (per image, and predict_batch at each B of --batches), and a line gives both times, the added ms per photo and the kernel
+nodes of both graphs.  Where scipy is installed the host route the clean-up replaces is timed for the same photo (mask to the host,
+scipy.ndimage.label, area filter, mask back); otherwise the line says that scipy is absent.
+
+    python tools/egm_ensemble_bench.py --cleanup 0.002,200,0 --batches 8
+    rocprofv3 --kernel-trace --stats -- python tools/egm_ensemble_bench.py --child 768x1024 --profile-one clean --cleanup 0.002,200,0
+
 Every size runs in a child process of its own under a time limit; a child that fails ends the run."""
 import argparse
 import json
@@ -45,7 +54,38 @@ def timed(fn, iters, warmup=5):
     return statistics.median(ts)
 
 
-def child(H0, W0, iters, repeats, profile_one=None, batches=(), profile_batch=8):
+def parse_cleanup(text):
+    from egm_unet_amd.ensemble import MaskCleanup
+    a, h, k = text.split(",")
+    num = lambda v: float(v) if "." in v else int(v)                   # noqa: E731
+    return MaskCleanup(min_area=num(a), max_hole=num(h), keep_largest=bool(int(k)))
+
+
+def host_route_ms(mask_dev, min_area_px, iters):
+    """What the clean-up replaces: the photo-size mask to the host, scipy.ndimage.label (8-connected), drop components below min_area,
+    the mask back to the device.  Wall-clock ms (median), or None without scipy."""
+    try:
+        import numpy as np
+        from scipy import ndimage as ndi
+    except ImportError:
+        return None
+    import time
+    ts = []
+    for _ in range(max(3, iters // 10)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m = mask_dev.cpu().numpy()
+        lab, n = ndi.label(m > 0, structure=np.ones((3, 3), int))
+        small = np.bincount(lab.reshape(-1), minlength=n + 1) < min_area_px
+        small[0] = False
+        m = np.where(small[lab], 0, m).astype(np.uint8)
+        torch.from_numpy(m).to(mask_dev.device)
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts)
+
+
+def child(H0, W0, iters, repeats, profile_one=None, batches=(), profile_batch=8, cleanup=None):
     import torch.nn.functional as F
     from egm_unet_amd import GRFBUNet, data
     from egm_unet_amd.clipseg import CLIPDensePredT
@@ -81,6 +121,33 @@ def child(H0, W0, iters, repeats, profile_one=None, batches=(), profile_batch=8)
 
     def stack(B):
         return torch.randint(0, 256, (B, H0, W0, 3), generator=torch.Generator().manual_seed(3), dtype=torch.uint8).to(dev)
+    if cleanup is not None:                                            # cleanup=None against the rule, alternating
+        import math
+        rule = parse_cleanup(cleanup)
+        clean = EnsemblePredictor(unet, clipseg, cond, alpha=0.5, dtype=dt, max_graphs=len(batches) + 4, cleanup=rule)
+        if profile_one:
+            for _ in range(12):
+                clean(img)
+            torch.cuda.synchronize()
+            return
+        stacks = {B: stack(B) for B in batches}
+        nodes = lambda e, key: kernel_nodes(e.captured_graph(key)) if e.captured_graph(key) is not None else None     # noqa: E731
+        for rep in range(repeats):
+            plain_ms, clean_ms = timed(lambda: ens(img), iters), timed(lambda: clean(img), iters)
+            print(json.dumps({"photo": [H0, W0], "repeat": rep, "cleanup": repr(rule), "plain_ms": round(plain_ms, 3),
+                              "clean_ms": round(clean_ms, 3), "added_ms": round(clean_ms - plain_ms, 3),
+                              "plain_kernel_nodes": nodes(ens, (H0, W0)), "clean_kernel_nodes": nodes(clean, (H0, W0))}), flush=True)
+            for B in batches:
+                pb, cb = timed(lambda: ens.predict_batch(stacks[B]), iters), timed(lambda: clean.predict_batch(stacks[B]), iters)
+                print(json.dumps({"photo": [H0, W0], "repeat": rep, "batch": B, "plain_ms_per_photo": round(pb / B, 3),
+                                  "clean_ms_per_photo": round(cb / B, 3), "added_ms_per_photo": round((cb - pb) / B, 3),
+                                  "plain_kernel_nodes": nodes(ens, (B, H0, W0)), "clean_kernel_nodes": nodes(clean, (B, H0, W0))}), flush=True)
+        min_px = rule.min_area if isinstance(rule.min_area, int) else math.ceil(rule.min_area * H0 * W0)
+        host = host_route_ms(ens(img, clone=True), min_px, iters)
+        print(json.dumps({"photo": [H0, W0], "host_route_ms": None if host is None else round(host, 2),
+                          "host_route": "mask to host, scipy.ndimage.label, area filter, mask back" if host is not None else "scipy is absent",
+                          "cleanup_status": clean.cleanup_status()}), flush=True)
+        return
     if profile_one:                                                    # 12 calls of one kind and nothing else
         if profile_one == "batch":
             imgs = stack(profile_batch)
@@ -133,20 +200,23 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--step-timeout", type=int, default=240, help="seconds per size (one child process each)")
     ap.add_argument("--child", default=None)
-    ap.add_argument("--profile-one", default=None, choices=["ens", "composed", "batch"],
+    ap.add_argument("--profile-one", default=None, choices=["ens", "composed", "batch", "clean"],
                     help="with --child: 12 calls of one kind (for rocprofv3)")
     ap.add_argument("--profile-batch", type=int, default=8, help="B of --profile-one batch")
     ap.add_argument("--batches", default="", help="e.g. 1,2,4,8,16: measure predict_batch at these B against the per-image replay")
+    ap.add_argument("--cleanup", default=None, help="MIN_AREA,MAX_HOLE,KEEP_LARGEST, e.g. 0.002,200,0: time the clean-up against cleanup=None")
     ap.add_argument("--max-batch-bytes", type=float, default=160e6, help="leave out a B whose uint8 photos are larger than this")
     args = ap.parse_args()
     if args.child:
         H0, W0 = (int(v) for v in args.child.split("x"))
         batches = [int(v) for v in args.batches.split(",") if v]
         batches = [B for B in batches if B * H0 * W0 * 3 <= args.max_batch_bytes]
-        child(H0, W0, args.iters, args.repeats, args.profile_one, batches, args.profile_batch)
+        child(H0, W0, args.iters, args.repeats, args.profile_one, batches, args.profile_batch, args.cleanup)
         return
     for size in args.sizes.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", size, "--iters", str(args.iters), "--repeats", str(args.repeats)]
+        if args.cleanup:
+            cmd += ["--cleanup", args.cleanup]
         if args.batches:
             cmd += ["--batches", args.batches, "--max-batch-bytes", str(args.max_batch_bytes)]
         try:
