@@ -18,6 +18,7 @@ and with a connected-component clean-up (postprocess.MaskCleanup) of the class m
     ens.cleanup = MaskCleanup(min_area=0.004, max_hole=200)        # new numbers: followed by the captured graphs
 """
 import collections
+import math
 
 import numpy as np
 import torch
@@ -214,6 +215,125 @@ def score_report(hist):
     accuracy = np.sum(np.diag(f)) / np.maximum(np.sum(f), 1)
     return {"hist": h, "iou": iou, "recall": recall, "precision": precision, "accuracy": float(accuracy), "miou": float(np.nanmean(iou)),
             "mpa": float(np.nanmean(recall))}
+
+
+def boundary_radius(H, W, boundary):
+    """The Boundary IoU band's radius d in pixels for an H x W image.  boundary as a float in (0, 1) is the paper's dilation_ratio
+    (Cheng et al., CVPR 2021; 0.02 by default there): d = max(1, int(round(ratio * sqrt(H^2 + W^2)))) with Python's round, so d depends
+    on the image size; as an int >= 1 it is d itself (the int-or-fraction convention of MaskCleanup).  ValueError for a bool, a float
+    outside (0, 1), an int < 1 or any other type.  Pure host code."""
+    if isinstance(boundary, (bool, np.bool_)):
+        raise ValueError(f"boundary: a ratio in (0, 1) or a radius >= 1 in pixels expected, got {boundary!r}")
+    if isinstance(boundary, (int, np.integer)):
+        if boundary < 1:
+            raise ValueError(f"boundary: a radius in pixels must be at least 1, got {boundary}")
+        return int(boundary)
+    if isinstance(boundary, (float, np.floating)):
+        if not 0.0 < boundary < 1.0:
+            raise ValueError(f"boundary: a ratio must lie in (0, 1), got {boundary}")
+        return max(1, int(round(float(boundary) * math.sqrt(int(H) ** 2 + int(W) ** 2))))
+    raise ValueError(f"boundary: a ratio in (0, 1) or a radius >= 1 in pixels expected, got {type(boundary).__name__}")
+
+
+_BOUNDARY_WORKSPACES = 4                    # shapes whose workspace is kept (3000 x 4000 at N = 8 is 192 MB)
+_boundary_workspace_cache = collections.OrderedDict()
+
+
+def boundary_workspace(N, H, W, device):
+    """A workspace for boundary_counts_u8 / boundary_band_u8 on [N, H, W] images that the caller owns: for calls captured into a graph
+    (a graph keeps the address) and for calls of one shape on several streams (one workspace per stream)."""
+    return torch.empty(lib().query("egm_boundary_workspace", int(N), int(H), int(W)), dtype=torch.uint8, device=device)
+
+
+def _boundary_workspace(N, H, W, device, workspace):
+    """The caller's workspace, checked, or the module's for this shape: the last _BOUNDARY_WORKSPACES shapes used are kept (least
+    recently used dropped first), so evaluate()'s loop allocates nothing while a few sizes repeat and memory stays bounded when the
+    sizes never do."""
+    if workspace is not None:
+        need = lib().query("egm_boundary_workspace", N, H, W)
+        if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == device and workspace.dtype == torch.uint8
+                and workspace.is_contiguous() and workspace.numel() >= need):
+            raise ValueError(f"boundary: workspace must be a contiguous uint8 tensor of at least {need} bytes on {device}")
+        return workspace
+    key = (N, H, W, str(device))
+    ws = _boundary_workspace_cache.pop(key, None)
+    if ws is None:
+        ws = boundary_workspace(N, H, W, device)
+    _boundary_workspace_cache[key] = ws
+    while len(_boundary_workspace_cache) > _BOUNDARY_WORKSPACES:
+        _boundary_workspace_cache.popitem(last=False)
+    return ws
+
+
+def _boundary_images(name, tensors):
+    """uint8 CUDA tensors of one non-empty shape [H, W] or [N, H, W] -> contiguous [N, H, W] views."""
+    for arg, t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8):
+            raise ValueError(f"{name}: {arg} must be a uint8 CUDA tensor")
+    first = tensors[0][1]
+    if any(t.shape != first.shape for _, t in tensors) or first.numel() == 0 or first.dim() not in (2, 3):
+        raise ValueError(f"{name}: " + " and ".join(f"{arg} {tuple(t.shape)}" for arg, t in tensors)
+                         + " must have one non-empty shape [H, W] or [N, H, W]")
+    return [(t.unsqueeze(0) if t.dim() == 2 else t).contiguous() for _, t in tensors]
+
+
+def boundary_counts_u8(pred_u8, label_u8, boundary=0.02, num_classes=2, pred_values=None, label_values=None, out=None, workspace=None):
+    """Boundary IoU counts of a predicted mask against its ground truth on the device: uint8 CUDA tensors of equal shape ([H, W], or a
+    batch [N, H, W] of independent images) -> int64 [N, C, 3] ([1, C, 3] for [H, W]), per image and class {|Bp and Bg|, |Bp|, |Bg|},
+    where a side's band B_k is its class-k mask minus that mask's erosion by a (2d + 1) x (2d + 1) box with zeros outside the image,
+    d = boundary_radius(H, W, boundary).  This is mask_to_boundary of the Boundary IoU paper's published code (one zero pixel of
+    padding, cv2.erode with a 3 x 3 kernel of ones, d iterations), restated from that source, not checked against a cv2 build.
+    pred_values / label_values: see class_table (None = the reference's rule for 0/255 PNGs); a dropped byte is in no class and erodes
+    its neighbours.  out: an int64 [N, C, 3] CUDA tensor to accumulate into (and returned).  Two launches, no host wait.  ValueError
+    for anything but two uint8 CUDA tensors of one shape.
+    workspace: None = the module's workspace for this shape, shared by every call of the shape and kept for the last few shapes only:
+    right for calls on one stream that are not captured.  Calls of one shape on several streams would race on it, and a captured
+    graph would keep the address of a buffer that may be dropped later: both pass a boundary_workspace(N, H, W, device) of their own."""
+    require_gpu()
+    p, t = _boundary_images("boundary_counts_u8", [("pred", pred_u8), ("label", label_u8)])
+    N, H, W = p.shape
+    d, C, dev = boundary_radius(H, W, boundary), int(num_classes), p.device
+    pt, lt = _class_table_dev(pred_values, C, dev), _class_table_dev(label_values, C, dev)
+    if out is None:
+        out = torch.zeros((N, C, 3), dtype=torch.int64, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (N, C, 3)
+              and out.is_contiguous()):
+        raise ValueError(f"boundary_counts_u8: out must be a contiguous int64 CUDA tensor [{N}, {C}, 3]")
+    ws = _boundary_workspace(N, H, W, dev, workspace)
+    lib().call("egm_mask_boundary_u8", ptr(p), ptr(t), N, H, W, d, ptr(pt), ptr(lt), C, ptr(ws), ptr(out), None, None, stream())
+    return out
+
+
+def boundary_band_u8(mask_u8, boundary=0.02, num_classes=2, values=None, workspace=None):
+    """The band boundary_counts_u8 counts, to look at: a uint8 CUDA mask [H, W] or [N, H, W] -> uint8 of the same shape, bit k set where
+    the pixel lies in the band of class k (values: see class_table; workspace: see boundary_counts_u8).  Two launches, no host wait."""
+    require_gpu()
+    m, = _boundary_images("boundary_band_u8", [("mask", mask_u8)])
+    N, H, W = m.shape
+    d, C = boundary_radius(H, W, boundary), int(num_classes)
+    band = torch.empty_like(m)
+    lib().call("egm_mask_boundary_u8", ptr(m), None, N, H, W, d, ptr(_class_table_dev(values, C, m.device)), None, C,
+               ptr(_boundary_workspace(N, H, W, m.device, workspace)), None, ptr(band), None, stream())
+    return band.reshape(mask_u8.shape)
+
+
+def boundary_report(counts):
+    """Boundary IoU from boundary_counts_u8's counts ([N, C, 3] tensor or array; [C, 3] is one image), in numpy float64 in the style of
+    score_report: dict(counts int64 [C, 3] summed over the images, biou [C] = inter / (npred + ngt - inter) of the sums with an empty
+    union giving 0, mbiou = the mean of biou over the classes, biou_images [N, C] = the same per image, NaN where an image's union is
+    empty)."""
+    c = np.asarray(counts.detach().cpu() if isinstance(counts, torch.Tensor) else counts).astype(np.int64)
+    if c.ndim == 2:
+        c = c[None]
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError(f"boundary_report: counts [N, C, 3] expected, got {c.shape}")
+    total = c.sum(0)
+    f = total.astype(np.float64)
+    biou = f[:, 0] / np.maximum(f[:, 1] + f[:, 2] - f[:, 0], 1)
+    g = c.astype(np.float64)
+    union = g[..., 1] + g[..., 2] - g[..., 0]
+    biou_images = np.where(union > 0, g[..., 0] / np.maximum(union, 1), np.nan)
+    return {"counts": total, "biou": biou, "mbiou": float(np.mean(biou)) if biou.size else 0.0, "biou_images": biou_images}
 
 
 def _label_u8(t, device):
@@ -558,14 +678,18 @@ class EnsemblePredictor:
         self.alpha = best
         return best, best_miou, m
 
-    def evaluate(self, images, gt_masks, batch_size=None):
+    def evaluate(self, images, gt_masks, batch_size=None, boundary=None):
         """evaluating_indicator.py's compute_mIoU (:347-417) over this pipeline without the PNGs in between: every photo's mask
         (__call__, or predict_batch over plan_batches with batch_size) is counted against its uint8 ground truth [H0, W0] (0/255 PNG
         bytes, the reference's / 255 rule) on the device, one confusion_u8 call per photo or batch into one matrix, and one copy to the
         host at the end.  The predictor's own lut says which byte is which class; a lut that maps two classes to one byte raises
         ValueError.  A ground truth whose size differs from its photo's is left out and counted in report["skipped"] (:375-380).
         With a cleanup rule the masks scored are the cleaned ones, so a rule can be judged by the mIoU it gives on a dataset.
-        -> score_report's dict plus "skipped"."""
+        boundary (None = off; otherwise boundary_radius's ratio or radius): every kept photo's mask also goes through
+        boundary_counts_u8 against its ground truth, right behind the confusion matrix and under the same tables, and the report
+        gains "boundary" = boundary_report's dict, biou_images in input order of the kept photos: the score that moves with the
+        contour, which the region scores hardly see.
+        -> score_report's dict plus "skipped" (plus "boundary")."""
         images, gt_masks = list(images), list(gt_masks)
         if len(images) != len(gt_masks):
             raise ValueError(f"evaluate: {len(images)} images and {len(gt_masks)} ground-truth masks")
@@ -574,13 +698,32 @@ class EnsemblePredictor:
         class_table(pred_values, C)                                        # raises for a lut that is not invertible
         hist = torch.zeros((C, C), dtype=torch.int64, device=dev)
         keep = [i for i, (im, gt) in enumerate(zip(images, gt_masks)) if tuple(im.shape[:2]) == tuple(gt.shape)]
+        if boundary is not None:
+            for i in keep:
+                boundary_radius(*gt_masks[i].shape, boundary)              # raises before any photo is run
+        order, bcounts = [], []                                            # photos in the order scored, their [n, C, 3] counts
         if batch_size is None:
             for i in keep:
-                confusion_u8(self(images[i]), _label_u8(gt_masks[i], dev)[0], C, pred_values, None, out=hist)
+                mask, gt = self(images[i]), _label_u8(gt_masks[i], dev)[0]
+                confusion_u8(mask, gt, C, pred_values, None, out=hist)
+                if boundary is not None:
+                    order.append(i)
+                    bcounts.append(boundary_counts_u8(mask, gt, boundary, C, pred_values, None))
         else:
             for idx, batch in _padded_batches(images, batch_size, keep):
-                masks = self.predict_batch(batch)
-                confusion_u8(masks[:len(idx)], torch.cat([_label_u8(gt_masks[i], dev) for i in idx]), C, pred_values, None, out=hist)
+                masks = self.predict_batch(batch)[:len(idx)]
+                gts = torch.cat([_label_u8(gt_masks[i], dev) for i in idx])
+                confusion_u8(masks, gts, C, pred_values, None, out=hist)
+                if boundary is not None:
+                    order.extend(idx)
+                    bcounts.append(boundary_counts_u8(masks, gts, boundary, C, pred_values, None))
+        if boundary is not None:
+            counts = torch.cat(bcounts) if bcounts else torch.zeros((0, C, 3), dtype=torch.int64, device=dev)
+            both = torch.cat([hist.reshape(-1), counts.reshape(-1)]).cpu()             # the one copy to the host
+            hist, counts = both[:C * C].reshape(C, C), both[C * C:].reshape(-1, C, 3).numpy()
+            by_input = np.argsort(np.asarray(order, dtype=np.int64), kind="stable")
         report = score_report(hist)
         report["skipped"] = len(images) - len(keep)
+        if boundary is not None:
+            report["boundary"] = boundary_report(counts[by_input])
         return report

@@ -740,6 +740,25 @@ int egm_mask_clean_u8(const unsigned char* cls, int N, int H, int W, int connect
                       unsigned char* out_cls, const int* yidx, const int* xidx, const unsigned char* lut, unsigned char* out, int H0,
                       int W0, egm_stream_t s);
 
+/* ---- Boundary IoU counts of uint8 masks at their own size (csrc/boundary.hip) ----------------------------------------
+ * pred, label: uint8 [N][H][W]; images are independent.  Class tables as for egm_mask_confusion_u8 (256 bytes of DEVICE memory, a
+ * value >= C puts the pixel in no class); 1 <= C <= 4.  With M_k = "the pixel's class is k", the eroded mask is E_k(y, x) = 1 iff
+ * M_k = 1 at every (y + dy, x + dx), |dy|, |dx| <= radius, all of them inside the image (outside counts as 0), and the band is
+ * B_k = M_k and not E_k: mask_to_boundary of the Boundary IoU paper (Cheng et al., CVPR 2021) with dilation radius `radius` pixels.
+ * A window larger than the image leaves E_k empty, so the band is the whole mask.
+ * counts [N][C][3] uint64, caller-zeroed and accumulated across calls (may be NULL): {|Bpred_k and Blabel_k|, |Bpred_k|, |Blabel_k|}
+ *   of image n.  band_pred / band_label uint8 [N][H][W] (may be NULL): bit k = B_k of that side.  label == NULL is the one-sided
+ *   form and needs counts == NULL and band_label == NULL.  At least one output must be given.
+ * workspace: egm_boundary_workspace(N, H, W) bytes of device memory owned by the caller (two bytes per pixel of a padded row).
+ * Two launches whatever the content, each covering the batch (rows, then columns); nothing waits for the device or for another
+ * workgroup; every device loop has a trip count derived from H, W and radius; capturable on one stream.  Any H, W >= 1 with
+ * H*W <= 2^30 and N*H <= 2^31, any radius >= 1, any base alignment of the images and of the band outputs; otherwise EGM_ERR_ARG.
+ * Counts are exact: a lane counts at most 512 pixels in 32 bits, a wave's sum goes to counts with one 64-bit atomic per cell. */
+long long egm_boundary_workspace(int N, int H, int W);
+int egm_mask_boundary_u8(const unsigned char* pred, const unsigned char* label, int N, int H, int W, int radius,
+                         const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
+                         unsigned long long* counts, unsigned char* band_pred, unsigned char* band_label, egm_stream_t s);
+
 /* ---- batched training data path: B ragged photos with masks -> the batch a train step reads (train.py:14-33, my_dataset.py:118-132)
  * egm_train_batch_u8: for every image b what egm_resample_u8 (axis 1, then axis 0), egm_gather_u8 and egm_augment_u8 compute one
  *   after the other, written into slot b of out_img_bchw fp32 [B][3][slot_h][slot_w] and out_target_bhw int64 [B][slot_h][slot_w]: per
