@@ -19,57 +19,14 @@
 // When 2 radius + 1 exceeds H or W nothing is eroded: the column pass then ignores the flags and walks its own rows only.
 // No workgroup waits for another and no loop depends on the data.
 #include "common.h"
+#include "mask_scan.h"
 
 namespace {
 
-constexpr int kBoundaryMaxC = 4;
-constexpr unsigned int kNoClass = 255u;        // a byte that belongs to no class (table entry >= C), also the padding behind a row
-constexpr int kRowLanePix = 16;                // row pass: pixels per lane
-constexpr int kRowChunk = 64 * kRowLanePix;    //           and per wave and step
 constexpr int kBoundaryRows = 128;             // column pass: image rows per wave (tests/test_gpu_boundary.py restates it)
 constexpr int kColLanePix = 4;                 //              columns per lane
 constexpr int kColWave = 64 * kColLanePix;     //              and per wave
 constexpr int kColUnroll = 8;                  //              rows loaded before any is used
-
-__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint4 load16_any(const unsigned char* p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
-__device__ __forceinline__ unsigned int load4_any(const unsigned char* p) {
-    unsigned int v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-// bytes [x0, x0 + 4) of a row of `width` bytes, 0 behind its end
-__device__ __forceinline__ unsigned int load4_row(const unsigned char* row, int x0, int width) {
-    if (x0 + 4 <= width) return load4_any(row + x0);
-    unsigned int v = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (x0 + j < width) v |= (unsigned int)row[x0 + j] << (8 * j);
-    return v;
-}
-__device__ __forceinline__ void store4_row(unsigned char* row, int x0, int width, unsigned int v) {
-    if (x0 + 4 <= width) { __builtin_memcpy(row + x0, &v, 4); return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (x0 + j < width) row[x0 + j] = (unsigned char)(v >> (8 * j));
-}
-
-// byte -> class tables in LDS, kNoClass for a dropped byte (and for every byte of a side that is not there)
-__device__ __forceinline__ void boundary_tables(unsigned char* pt, unsigned char* lt, const unsigned char* pred_cls, const unsigned char* label_cls,
-                                                int C) {
-    const unsigned int pc = pred_cls[threadIdx.x], lc = label_cls ? label_cls[threadIdx.x] : kNoClass;
-    pt[threadIdx.x] = (unsigned char)(pc < (unsigned)C ? pc : kNoClass);
-    lt[threadIdx.x] = (unsigned char)(lc < (unsigned)C ? lc : kNoClass);
-    __syncthreads();
-}
 
 // One side of the row pass for a lane's 16 pixels [p0, p0 + 16): cls = their classes, prev_cls / carry_start = the class of pixel
 // p0 - 1 of the chunk before (256 in front of the row: equal to no class) and the latest run start so far.  -> bit (1 << class) per pixel
@@ -105,18 +62,6 @@ __device__ __forceinline__ void row_side(const unsigned int (&cls)[kRowLanePix],
     }
     carry_start = max(carry_start, __shfl(inc, 63, 64));
     prev_cls = __shfl(cls[kRowLanePix - 1], 63, 64);
-}
-
-__device__ __forceinline__ void row_classes(const unsigned char* row, int p0, int W, const unsigned char* tab, unsigned int (&cls)[kRowLanePix]) {
-    if (row && p0 + kRowLanePix <= W) {
-        const uint4 v = load16_any(row + p0);
-        const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < kRowLanePix; ++i) cls[i] = tab[(w[i >> 2] >> (8 * (i & 3))) & 255u];
-    } else {
-#pragma unroll
-        for (int i = 0; i < kRowLanePix; ++i) cls[i] = (row && p0 + i < W) ? (unsigned int)tab[row[p0 + i]] : kNoClass;
-    }
 }
 
 // flags[row][p]: bit k = pred class k fills columns [p - 2 radius, p] of the row, bit 4 + k = the label's; member[row][p]: the class
@@ -223,9 +168,6 @@ __global__ __launch_bounds__(256) void boundary_cols_kernel(int H, int W, int pi
             if (lane == 0 && v) atomicAdd(&counts[(n * C + k) * 3 + t], (unsigned long long)v);
         }
 }
-
-constexpr long long kBoundaryMaxPix = 1ll << 30;
-inline int boundary_pitch(int W) { return (W + 15) & ~15; }
 
 }  // namespace
 

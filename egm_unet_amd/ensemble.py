@@ -237,6 +237,9 @@ def boundary_radius(H, W, boundary):
 
 _BOUNDARY_WORKSPACES = 4                    # shapes whose workspace is kept (3000 x 4000 at N = 8 is 192 MB)
 _boundary_workspace_cache = collections.OrderedDict()
+_contour_workspace_cache = collections.OrderedDict()
+_CONTOUR_MAX_RADIUS = 254                   # kContourMaxRadius of csrc/contour.hip: a row distance is kept in a byte, 255 = none
+_BOUNDARY_METRICS = ("box", "euclid")
 
 
 def boundary_workspace(N, H, W, device):
@@ -245,24 +248,53 @@ def boundary_workspace(N, H, W, device):
     return torch.empty(lib().query("egm_boundary_workspace", int(N), int(H), int(W)), dtype=torch.uint8, device=device)
 
 
-def _boundary_workspace(N, H, W, device, workspace):
-    """The caller's workspace, checked, or the module's for this shape: the last _BOUNDARY_WORKSPACES shapes used are kept (least
-    recently used dropped first), so evaluate()'s loop allocates nothing while a few sizes repeat and memory stays bounded when the
-    sizes never do."""
+def contour_workspace(N, H, W, num_classes, device):
+    """boundary_workspace for the calls of csrc/contour.hip on [N, H, W] images of num_classes classes: contour_u8, contour_f_counts_u8
+    and boundary_counts_u8 / boundary_band_u8 with metric="euclid" (max(3, 2 C + 1) bytes per pixel)."""
+    return torch.empty(lib().query("egm_contour_workspace", int(N), int(H), int(W), int(num_classes)), dtype=torch.uint8, device=device)
+
+
+def _cached_workspace(cache, query, shape, device, workspace):
+    """The caller's workspace, checked, or the module's for this shape: the last _BOUNDARY_WORKSPACES shapes used are kept per cache
+    (least recently used dropped first), so evaluate()'s loop allocates nothing while a few sizes repeat and memory stays bounded when
+    the sizes never do.  query: the entry point that gives the size in bytes for `shape`."""
     if workspace is not None:
-        need = lib().query("egm_boundary_workspace", N, H, W)
+        need = lib().query(query, *shape)
         if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == device and workspace.dtype == torch.uint8
                 and workspace.is_contiguous() and workspace.numel() >= need):
             raise ValueError(f"boundary: workspace must be a contiguous uint8 tensor of at least {need} bytes on {device}")
         return workspace
-    key = (N, H, W, str(device))
-    ws = _boundary_workspace_cache.pop(key, None)
+    key = tuple(shape) + (str(device),)
+    ws = cache.pop(key, None)
     if ws is None:
-        ws = boundary_workspace(N, H, W, device)
-    _boundary_workspace_cache[key] = ws
-    while len(_boundary_workspace_cache) > _BOUNDARY_WORKSPACES:
-        _boundary_workspace_cache.popitem(last=False)
+        ws = torch.empty(lib().query(query, *shape), dtype=torch.uint8, device=device)
+    cache[key] = ws
+    while len(cache) > _BOUNDARY_WORKSPACES:
+        cache.popitem(last=False)
     return ws
+
+
+def _boundary_workspace(N, H, W, device, workspace):
+    return _cached_workspace(_boundary_workspace_cache, "egm_boundary_workspace", (N, H, W), device, workspace)
+
+
+def _contour_workspace(N, H, W, C, device, workspace):
+    return _cached_workspace(_contour_workspace_cache, "egm_contour_workspace", (N, H, W, C), device, workspace)
+
+
+def _boundary_metric(metric):
+    if metric not in _BOUNDARY_METRICS:
+        raise ValueError(f"boundary: metric must be one of {_BOUNDARY_METRICS}, got {metric!r}")
+    return metric
+
+
+def contour_radius(H, W, radius, what="boundary"):
+    """boundary_radius for the Euclidean band and the contour tolerance, whose kernels keep a row distance in a byte: ValueError above
+    254 pixels (the ratio 0.02 gets there at a diagonal of 12 700 pixels).  Pure host code."""
+    d = boundary_radius(H, W, radius)
+    if d > _CONTOUR_MAX_RADIUS:
+        raise ValueError(f"{what}: {d} pixels on a {H} x {W} image, at most {_CONTOUR_MAX_RADIUS} are supported")
+    return d
 
 
 def _boundary_images(name, tensors):
@@ -277,7 +309,8 @@ def _boundary_images(name, tensors):
     return [(t.unsqueeze(0) if t.dim() == 2 else t).contiguous() for _, t in tensors]
 
 
-def boundary_counts_u8(pred_u8, label_u8, boundary=0.02, num_classes=2, pred_values=None, label_values=None, out=None, workspace=None):
+def boundary_counts_u8(pred_u8, label_u8, boundary=0.02, num_classes=2, pred_values=None, label_values=None, out=None, workspace=None,
+                       metric="box"):
     """Boundary IoU counts of a predicted mask against its ground truth on the device: uint8 CUDA tensors of equal shape ([H, W], or a
     batch [N, H, W] of independent images) -> int64 [N, C, 3] ([1, C, 3] for [H, W]), per image and class {|Bp and Bg|, |Bp|, |Bg|},
     where a side's band B_k is its class-k mask minus that mask's erosion by a (2d + 1) x (2d + 1) box with zeros outside the image,
@@ -288,32 +321,41 @@ def boundary_counts_u8(pred_u8, label_u8, boundary=0.02, num_classes=2, pred_val
     for anything but two uint8 CUDA tensors of one shape.
     workspace: None = the module's workspace for this shape, shared by every call of the shape and kept for the last few shapes only:
     right for calls on one stream that are not captured.  Calls of one shape on several streams would race on it, and a captured
-    graph would keep the address of a buffer that may be dropped later: both pass a boundary_workspace(N, H, W, device) of their own."""
+    graph would keep the address of a buffer that may be dropped later: both pass a boundary_workspace(N, H, W, device) of their own.
+    metric: "box" is the band above.  "euclid" is the distance the paper describes (csrc/contour.hip): BE_k = the pixels
+    of class k with some q in Z^2, |p - q|^2 <= d^2 in integers, that is outside the image or not of class k; BE_k is a subset of the
+    box band, which reaches 1.41 d along the diagonals.  There d is at most 254 (ValueError above) and the workspace is a
+    contour_workspace(N, H, W, num_classes, device).  Any other metric raises ValueError."""
     require_gpu()
+    euclid = _boundary_metric(metric) == "euclid"
     p, t = _boundary_images("boundary_counts_u8", [("pred", pred_u8), ("label", label_u8)])
     N, H, W = p.shape
-    d, C, dev = boundary_radius(H, W, boundary), int(num_classes), p.device
+    d, C, dev = (contour_radius if euclid else boundary_radius)(H, W, boundary), int(num_classes), p.device
     pt, lt = _class_table_dev(pred_values, C, dev), _class_table_dev(label_values, C, dev)
     if out is None:
         out = torch.zeros((N, C, 3), dtype=torch.int64, device=dev)
     elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (N, C, 3)
               and out.is_contiguous()):
         raise ValueError(f"boundary_counts_u8: out must be a contiguous int64 CUDA tensor [{N}, {C}, 3]")
-    ws = _boundary_workspace(N, H, W, dev, workspace)
-    lib().call("egm_mask_boundary_u8", ptr(p), ptr(t), N, H, W, d, ptr(pt), ptr(lt), C, ptr(ws), ptr(out), None, None, stream())
+    ws = _contour_workspace(N, H, W, C, dev, workspace) if euclid else _boundary_workspace(N, H, W, dev, workspace)
+    lib().call("egm_mask_boundary_euclid_u8" if euclid else "egm_mask_boundary_u8", ptr(p), ptr(t), N, H, W, d, ptr(pt), ptr(lt), C, ptr(ws),
+               ptr(out), None, None, stream())
     return out
 
 
-def boundary_band_u8(mask_u8, boundary=0.02, num_classes=2, values=None, workspace=None):
+def boundary_band_u8(mask_u8, boundary=0.02, num_classes=2, values=None, workspace=None, metric="box"):
     """The band boundary_counts_u8 counts, to look at: a uint8 CUDA mask [H, W] or [N, H, W] -> uint8 of the same shape, bit k set where
-    the pixel lies in the band of class k (values: see class_table; workspace: see boundary_counts_u8).  Two launches, no host wait."""
+    the pixel lies in the band of class k (values: see class_table; workspace, metric: see boundary_counts_u8).  Two launches, no host
+    wait."""
     require_gpu()
+    euclid = _boundary_metric(metric) == "euclid"
     m, = _boundary_images("boundary_band_u8", [("mask", mask_u8)])
     N, H, W = m.shape
-    d, C = boundary_radius(H, W, boundary), int(num_classes)
+    d, C = (contour_radius if euclid else boundary_radius)(H, W, boundary), int(num_classes)
     band = torch.empty_like(m)
-    lib().call("egm_mask_boundary_u8", ptr(m), None, N, H, W, d, ptr(_class_table_dev(values, C, m.device)), None, C,
-               ptr(_boundary_workspace(N, H, W, m.device, workspace)), None, ptr(band), None, stream())
+    ws = _contour_workspace(N, H, W, C, m.device, workspace) if euclid else _boundary_workspace(N, H, W, m.device, workspace)
+    lib().call("egm_mask_boundary_euclid_u8" if euclid else "egm_mask_boundary_u8", ptr(m), None, N, H, W, d,
+               ptr(_class_table_dev(values, C, m.device)), None, C, ptr(ws), None, ptr(band), None, stream())
     return band.reshape(mask_u8.shape)
 
 
@@ -334,6 +376,74 @@ def boundary_report(counts):
     union = g[..., 1] + g[..., 2] - g[..., 0]
     biou_images = np.where(union > 0, g[..., 0] / np.maximum(union, 1), np.nan)
     return {"counts": total, "biou": biou, "mbiou": float(np.mean(biou)) if biou.size else 0.0, "biou_images": biou_images}
+
+
+def contour_u8(mask_u8, num_classes=2, values=None, workspace=None):
+    """The contours contour_f_counts_u8 matches, to look at: a uint8 CUDA mask [H, W] or [N, H, W] -> uint8 of the same shape, bit k set
+    where the pixel is of class k and one of its 4-neighbours INSIDE THE IMAGE is not (a dropped byte is in no class and is "not k" for
+    every k).  The image frame makes no contour: an object cut by the frame has no true edge there.  This is the convention of the
+    F-measure's published forms and differs from the band of boundary_band_u8 on purpose, where outside the image counts as "not k".
+    values: see class_table; workspace: a contour_workspace(N, H, W, num_classes, device), see boundary_counts_u8.  Two launches, no
+    host wait."""
+    require_gpu()
+    m, = _boundary_images("contour_u8", [("mask", mask_u8)])
+    N, H, W = m.shape
+    C = int(num_classes)
+    out = torch.empty_like(m)
+    lib().call("egm_mask_contour_f_u8", ptr(m), None, N, H, W, 1, ptr(_class_table_dev(values, C, m.device)), None, C,
+               ptr(_contour_workspace(N, H, W, C, m.device, workspace)), None, ptr(out), None, stream())
+    return out.reshape(mask_u8.shape)
+
+
+def contour_f_counts_u8(pred_u8, label_u8, tolerance=0.008, num_classes=2, pred_values=None, label_values=None, out=None, workspace=None):
+    """The counts of the boundary F-measure (Csurka et al., BMVC 2013; the contour score of DAVIS) of a predicted mask against its
+    ground truth on the device: uint8 CUDA tensors of equal shape ([H, W], or a batch [N, H, W] of independent images) -> int64
+    [N, C, 4], per image and class {mp, |Kp|, mg, |Kg|}: K = the side's contour (contour_u8: 4-neighbours inside the image, so the
+    image frame makes no contour, unlike the Boundary IoU band), mp = the pixels of Kp with a pixel of Kg within theta pixels
+    (|p - g|^2 <= theta^2 in integers), mg the mirror image.  theta = boundary_radius(H, W, tolerance): an int is theta itself, a float a
+    ratio of the diagonal with boundary_radius's rounding; the default 0.008 is the ratio of the DAVIS evaluation.  The rule is
+    restated from the papers, not checked against the published code (which matches dilated contours, as here, but builds them with
+    its own rounding of theta).  theta is at most 254 (ValueError above).  pred_values / label_values: see class_table.  out: an int64
+    [N, C, 4] CUDA tensor to accumulate into (and returned).  workspace: a contour_workspace(N, H, W, num_classes, device), see
+    boundary_counts_u8.  Two launches, no host wait."""
+    require_gpu()
+    p, t = _boundary_images("contour_f_counts_u8", [("pred", pred_u8), ("label", label_u8)])
+    N, H, W = p.shape
+    theta, C, dev = contour_radius(H, W, tolerance, "contour_f"), int(num_classes), p.device
+    pt, lt = _class_table_dev(pred_values, C, dev), _class_table_dev(label_values, C, dev)
+    if out is None:
+        out = torch.zeros((N, C, 4), dtype=torch.int64, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (N, C, 4)
+              and out.is_contiguous()):
+        raise ValueError(f"contour_f_counts_u8: out must be a contiguous int64 CUDA tensor [{N}, {C}, 4]")
+    lib().call("egm_mask_contour_f_u8", ptr(p), ptr(t), N, H, W, theta, ptr(pt), ptr(lt), C, ptr(_contour_workspace(N, H, W, C, dev, workspace)),
+               ptr(out), None, None, stream())
+    return out
+
+
+def contour_f_report(counts):
+    """The boundary F-measure from contour_f_counts_u8's counts ([N, C, 4] tensor or array; [C, 4] is one image), in numpy float64 in
+    the style of boundary_report: dict(counts int64 [C, 4] summed over the images, precision [C] = mp / |Kp|, recall [C] = mg / |Kg|,
+    f [C] = 2 P R / (P + R) of the sums with an empty denominator giving 0, mean_f = the mean of f over the classes, f_images [N, C] =
+    the same per image: NaN where both contours of the image and class are empty, 0 where exactly one is, mean_f_images [C] = the
+    nanmean of f_images over the images (NaN for a class with no contour in any image))."""
+    c = np.asarray(counts.detach().cpu() if isinstance(counts, torch.Tensor) else counts).astype(np.int64)
+    if c.ndim == 2:
+        c = c[None]
+    if c.ndim != 3 or c.shape[2] != 4:
+        raise ValueError(f"contour_f_report: counts [N, C, 4] expected, got {c.shape}")
+
+    def prf(v):
+        v = v.astype(np.float64)
+        pr, rc = v[..., 0] / np.maximum(v[..., 1], 1), v[..., 2] / np.maximum(v[..., 3], 1)
+        return pr, rc, np.where(pr + rc > 0, 2 * pr * rc / np.where(pr + rc > 0, pr + rc, 1), 0.0)
+    total = c.sum(0)
+    precision, recall, f = prf(total)
+    f_images = np.where((c[..., 1] + c[..., 3]) > 0, prf(c)[2], np.nan)
+    seen = ~np.isnan(f_images)
+    mean_f_images = np.where(seen.any(0), np.where(seen, f_images, 0.0).sum(0) / np.maximum(seen.sum(0), 1), np.nan)
+    return {"counts": total, "precision": precision, "recall": recall, "f": f, "mean_f": float(np.mean(f)) if f.size else 0.0,
+            "f_images": f_images, "mean_f_images": mean_f_images}
 
 
 def _label_u8(t, device):
@@ -678,7 +788,7 @@ class EnsemblePredictor:
         self.alpha = best
         return best, best_miou, m
 
-    def evaluate(self, images, gt_masks, batch_size=None, boundary=None):
+    def evaluate(self, images, gt_masks, batch_size=None, boundary=None, boundary_metric="box", contour_f=None):
         """evaluating_indicator.py's compute_mIoU (:347-417) over this pipeline without the PNGs in between: every photo's mask
         (__call__, or predict_batch over plan_batches with batch_size) is counted against its uint8 ground truth [H0, W0] (0/255 PNG
         bytes, the reference's / 255 rule) on the device, one confusion_u8 call per photo or batch into one matrix, and one copy to the
@@ -688,8 +798,12 @@ class EnsemblePredictor:
         boundary (None = off; otherwise boundary_radius's ratio or radius): every kept photo's mask also goes through
         boundary_counts_u8 against its ground truth, right behind the confusion matrix and under the same tables, and the report
         gains "boundary" = boundary_report's dict, biou_images in input order of the kept photos: the score that moves with the
-        contour, which the region scores hardly see.
-        -> score_report's dict plus "skipped" (plus "boundary")."""
+        contour, which the region scores hardly see.  boundary_metric: the band's metric, "box" or "euclid" (boundary_counts_u8).
+        contour_f (None = off; otherwise the tolerance of contour_f_counts_u8 as a ratio or in pixels): the masks also go through
+        contour_f_counts_u8 in the same place, and the report gains "contour_f" = contour_f_report's dict, f_images in input order.
+        Both arguments and the metric are checked against every kept photo's size before any photo is run; all counts travel in the
+        one copy to the host.
+        -> score_report's dict plus "skipped" (plus "boundary", plus "contour_f")."""
         images, gt_masks = list(images), list(gt_masks)
         if len(images) != len(gt_masks):
             raise ValueError(f"evaluate: {len(images)} images and {len(gt_masks)} ground-truth masks")
@@ -698,32 +812,39 @@ class EnsemblePredictor:
         class_table(pred_values, C)                                        # raises for a lut that is not invertible
         hist = torch.zeros((C, C), dtype=torch.int64, device=dev)
         keep = [i for i, (im, gt) in enumerate(zip(images, gt_masks)) if tuple(im.shape[:2]) == tuple(gt.shape)]
-        if boundary is not None:
-            for i in keep:
-                boundary_radius(*gt_masks[i].shape, boundary)              # raises before any photo is run
-        order, bcounts = [], []                                            # photos in the order scored, their [n, C, 3] counts
+        radius_of = contour_radius if _boundary_metric(boundary_metric) == "euclid" else boundary_radius
+        for i in keep:                                                     # raises before any photo is run
+            if boundary is not None:
+                radius_of(*gt_masks[i].shape, boundary)
+            if contour_f is not None:
+                contour_radius(*gt_masks[i].shape, contour_f, "contour_f")
+        order, bcounts, fcounts = [], [], []                               # photos in the order scored, their [n, C, 3] and [n, C, 4] counts
+
+        def score(idx, masks, gts):
+            confusion_u8(masks, gts, C, pred_values, None, out=hist)
+            if boundary is not None or contour_f is not None:
+                order.extend(idx)
+            if boundary is not None:
+                bcounts.append(boundary_counts_u8(masks, gts, boundary, C, pred_values, None, metric=boundary_metric))
+            if contour_f is not None:
+                fcounts.append(contour_f_counts_u8(masks, gts, contour_f, C, pred_values, None))
         if batch_size is None:
             for i in keep:
-                mask, gt = self(images[i]), _label_u8(gt_masks[i], dev)[0]
-                confusion_u8(mask, gt, C, pred_values, None, out=hist)
-                if boundary is not None:
-                    order.append(i)
-                    bcounts.append(boundary_counts_u8(mask, gt, boundary, C, pred_values, None))
+                score([i], self(images[i]), _label_u8(gt_masks[i], dev)[0])
         else:
             for idx, batch in _padded_batches(images, batch_size, keep):
-                masks = self.predict_batch(batch)[:len(idx)]
-                gts = torch.cat([_label_u8(gt_masks[i], dev) for i in idx])
-                confusion_u8(masks, gts, C, pred_values, None, out=hist)
-                if boundary is not None:
-                    order.extend(idx)
-                    bcounts.append(boundary_counts_u8(masks, gts, boundary, C, pred_values, None))
-        if boundary is not None:
-            counts = torch.cat(bcounts) if bcounts else torch.zeros((0, C, 3), dtype=torch.int64, device=dev)
-            both = torch.cat([hist.reshape(-1), counts.reshape(-1)]).cpu()             # the one copy to the host
-            hist, counts = both[:C * C].reshape(C, C), both[C * C:].reshape(-1, C, 3).numpy()
+                score(idx, self.predict_batch(batch)[:len(idx)], torch.cat([_label_u8(gt_masks[i], dev) for i in idx]))
+        if boundary is not None or contour_f is not None:
+            parts = [hist.reshape(-1)] + [torch.cat(c).reshape(-1) for c in (bcounts, fcounts) if c]
+            both = torch.cat(parts).cpu()                                  # the one copy to the host
+            hist, rest = both[:C * C].reshape(C, C), both[C * C:].numpy()
             by_input = np.argsort(np.asarray(order, dtype=np.int64), kind="stable")
+            n = len(order)
         report = score_report(hist)
         report["skipped"] = len(images) - len(keep)
         if boundary is not None:
-            report["boundary"] = boundary_report(counts[by_input])
+            report["boundary"] = boundary_report(rest[:n * C * 3].reshape(n, C, 3)[by_input])
+            rest = rest[n * C * 3:]
+        if contour_f is not None:
+            report["contour_f"] = contour_f_report(rest.reshape(n, C, 4)[by_input])
         return report

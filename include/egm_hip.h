@@ -759,6 +759,32 @@ int egm_mask_boundary_u8(const unsigned char* pred, const unsigned char* label, 
                          const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
                          unsigned long long* counts, unsigned char* band_pred, unsigned char* band_label, egm_stream_t s);
 
+/* ---- Contour scores of uint8 masks at their own size (csrc/contour.hip) --------------------------------------------------
+ * Images, class tables, C and the independence of a batch's images as for egm_mask_boundary_u8; every distance is a squared integer
+ * distance compared with radius^2.
+ * egm_mask_boundary_euclid_u8: egm_mask_boundary_u8 with a Euclidean band.  BE_k = the pixels of class k with some q in Z^2,
+ *   |p - q|^2 <= radius^2, that is outside the image or not of class k (a pixel in no class is in no band and is "not k" for every k).
+ *   Arguments, outputs ({|BEpred_k and BElabel_k|, |BEpred_k|, |BElabel_k|}, bit k = BE_k) and the one-sided form as there.  BE_k is a
+ *   subset of the box band of the same radius; a disc larger than the image makes the band the whole mask.
+ * egm_mask_contour_f_u8: the counts of the boundary F-measure.  The contour K_k = the pixels of class k with a 4-neighbour INSIDE THE
+ *   IMAGE whose class is not k (the image frame makes no contour, unlike the band).  counts [N][C][4] uint64, caller-zeroed and
+ *   accumulated across calls (may be NULL): {mp, |Kpred_k|, mg, |Klabel_k|} of image n, mp = the pixels of Kpred_k with a pixel of
+ *   Klabel_k within `radius` (the tolerance), mg the mirror image.  contour_pred / contour_label uint8 [N][H][W] (may be NULL): bit k =
+ *   K_k of that side.  label == NULL needs counts == NULL and contour_label == NULL.  At least one output must be given.
+ * workspace: egm_contour_workspace(N, H, W, C) bytes of device memory owned by the caller, good for both calls (max(3, 2 C + 1) bytes
+ *   per pixel of a padded row).
+ * Two launches per call whatever the content, N, C and radius (rows, then columns); nothing waits for the device or for another
+ * workgroup; capturable on one stream.  1 <= radius <= 254 (a row distance is kept in a byte, 255 = none), H*W <= 2^30, N*H <= 2^31,
+ * any base alignment of the images and of the outputs; otherwise EGM_ERR_ARG.  Counts are exact: a lane counts at most 64 pixels in
+ * 32 bits, a wave's sum goes to counts with one 64-bit atomic per non-zero cell. */
+long long egm_contour_workspace(int N, int H, int W, int C);
+int egm_mask_boundary_euclid_u8(const unsigned char* pred, const unsigned char* label, int N, int H, int W, int radius,
+                                const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
+                                unsigned long long* counts, unsigned char* band_pred, unsigned char* band_label, egm_stream_t s);
+int egm_mask_contour_f_u8(const unsigned char* pred, const unsigned char* label, int N, int H, int W, int radius,
+                          const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
+                          unsigned long long* counts, unsigned char* contour_pred, unsigned char* contour_label, egm_stream_t s);
+
 /* ---- batched training data path: B ragged photos with masks -> the batch a train step reads (train.py:14-33, my_dataset.py:118-132)
  * egm_train_batch_u8: for every image b what egm_resample_u8 (axis 1, then axis 0), egm_gather_u8 and egm_augment_u8 compute one
  *   after the other, written into slot b of out_img_bchw fp32 [B][3][slot_h][slot_w] and out_target_bhw int64 [B][slot_h][slot_w]: per
