@@ -1,0 +1,360 @@
+"""Case tables, integer operands and the plain reference of the exact-integer convolution tests (test_gpu_conv_exact.py on the GPU,
+test_conv_exact_cpu.py without one).
+
+Operands are small nonzero integers (x, dy from {+-1, +-2}; w from {+-1} with zeros mixed in; bias from [-3, 3]), all exactly
+representable in bf16.  Every product and every partial sum of a convolution, a data gradient or a weight gradient over them is an
+integer far below 2^24, hence exact in fp32 in ANY summation order, tiling or K-split: a kernel that accumulates in fp32 must
+reproduce the reference bit for bit, and one wrong, missing or repeated term anywhere is a mismatch.
+
+The reference is torch.nn.functional.conv2d and its autograd on the CPU, in float64 (float32 for the cases flagged `fast`, which
+test_conv_exact_cpu.py shows to agree with float64 exactly)."""
+import functools
+from collections import namedtuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+# Cin / Cout are the REAL channel counts; the activation buffers carry pad8() of them.  `fwd` / `dgrad` / `wgrad` name the kernel the
+# planner gives the case (egm_conv_kernel_name with the padded counts, with them swapped, egm_conv_wgrad_kernel_name), read from the
+# planner queries at tile mode `mode`; the GPU test asserts them so that a planner change cannot silently move a case elsewhere.
+Case = namedtuple("Case", "dtype N H W Cin Cout k dil groups bias mode fast seed fwd dgrad wgrad uneven", defaults=(1, False, 5, False, 0, None, None, None, False))
+
+VALUE_LIMIT = 256          # forward / data-gradient values: integers up to 256 are bf16 numbers
+SUM_LIMIT = 2 ** 24        # fp32 holds every integer below 2^24
+
+
+def pad8(c):
+    return (c + 7) // 8 * 8
+
+
+def case_id(c):
+    s = f"{c.dtype}-{c.N}x{c.H}x{c.W}-{c.Cin}to{c.Cout}-k{c.k}d{c.dil}"
+    return s + (f"-g{c.groups}" if c.groups > 1 else "") + ("-b" if c.bias else "") + (f"-m{c.mode}" if c.mode != 5 else "")
+
+
+def torch_dtype(c):
+    return torch.bfloat16 if c.dtype == "bf16" else torch.float32
+
+
+def density(c):
+    """Share of nonzero weights: the longer of the two reductions (forward: Cin/groups * k^2 terms, data gradient: Cout/groups * k^2)
+    keeps about 400 nonzero terms, so a sum of +-1 * {+-1, +-2} has a standard deviation of at most sqrt(2.5 * 400) ~ 32 and 256 lies
+    eight of them out."""
+    terms = max(c.Cin, c.Cout) // c.groups * c.k * c.k
+    return min(1.0, 400.0 / terms)
+
+
+def operands(c):
+    """-> x [N, Cin, H, W], w [Cout, Cin/groups, k, k], b [Cout] or None, dy [N, Cout, H, W]: float64 CPU tensors of integers."""
+    g = torch.Generator().manual_seed(1000 + c.seed)
+
+    def pm12(*shape):
+        return (torch.randint(1, 3, shape, generator=g) * (torch.randint(0, 2, shape, generator=g) * 2 - 1)).double()
+
+    x = pm12(c.N, c.Cin, c.H, c.W)
+    wshape = (c.Cout, c.Cin // c.groups, c.k, c.k)
+    w = (torch.randint(0, 2, wshape, generator=g) * 2 - 1).double()
+    d = density(c)
+    if d < 1.0:
+        w = w * (torch.rand(wshape, generator=g, dtype=torch.float64) < d).double()
+    b = torch.randint(-3, 4, (c.Cout,), generator=g).double() if c.bias else None
+    dy = pm12(c.N, c.Cout, c.H, c.W)
+    return x, w, b, dy
+
+
+def conv_ref(c, x, w, b, dy, want, dtype=torch.float64):
+    """Plain conv2d and its autograd.  want: subset of 'y', 'dx', 'dw', 'db' -> dict of float64 tensors."""
+    x, w, dy = x.to(dtype), w.to(dtype), dy.to(dtype)
+    b = None if b is None else b.to(dtype)
+    xr = x.clone().requires_grad_("dx" in want)
+    wr = w.clone().requires_grad_("dw" in want)
+    y = F.conv2d(xr, wr, b, padding=c.dil * (c.k - 1) // 2, dilation=c.dil, groups=c.groups)
+    out = {}
+    if "y" in want:
+        out["y"] = y.detach().double()
+    ins = [t for t, n in ((xr, "dx"), (wr, "dw")) if n in want]
+    if ins:
+        grads = torch.autograd.grad(y, ins, dy)
+        for t, gr in zip(ins, grads):
+            out["dx" if t is xr else "dw"] = gr.double()
+    if "db" in want:
+        out["db"] = dy.sum((0, 2, 3)).double()
+    return out
+
+
+def _is_int(t):
+    return bool((t == t.round()).all())
+
+
+def check_bounds(c, ref):
+    """Raise unless the reference values are integers inside the representable range (the condition the exactness argument needs)."""
+    for name, t in ref.items():
+        if not _is_int(t):
+            raise ValueError(f"{case_id(c)}: reference {name} is not integral")
+        lim = VALUE_LIMIT if name in ("y", "dx") else SUM_LIMIT - 1
+        m = float(t.abs().max())
+        if m > lim:
+            raise ValueError(f"{case_id(c)}: |{name}| reaches {m:.0f}, beyond {lim}")
+
+
+Built = namedtuple("Built", "case x w b dy ref")
+
+
+@functools.lru_cache(maxsize=2)
+def build(c, want=("y", "dx")):
+    """Operands and reference of a case; raises ValueError when a reference value leaves the representable range."""
+    x, w, b, dy = operands(c)
+    ref = conv_ref(c, x, w, b, dy, want, torch.float32 if c.fast else torch.float64)
+    check_bounds(c, ref)
+    return Built(c, x, w, b, dy, ref)
+
+
+# ---- direct loops over taps in int64 (self-check of the reference) -----------------------------------------------------------
+def loops_int64(c, x, w, b, dy):
+    """y, dx, dw of the convolution by shifting whole maps tap by tap, in numpy int64."""
+    x, w, dy = (np.asarray(t.numpy()).astype(np.int64) for t in (x, w, dy))
+    N, Cin, H, W = x.shape
+    Cout, cg, k = w.shape[0], w.shape[1], c.k
+    og, pad = Cout // c.groups, c.dil * (k - 1) // 2
+    y = np.zeros((N, Cout, H, W), np.int64)
+    dx = np.zeros_like(x)
+    dw = np.zeros_like(w)
+    for co in range(Cout):
+        gi = co // og
+        for cl in range(cg):
+            ci = gi * cg + cl
+            for r in range(k):
+                for s in range(k):
+                    oy, ox = r * c.dil - pad, s * c.dil - pad          # y[h, w] += w * x[h + oy, w + ox]
+                    h0, h1 = max(0, -oy), min(H, H - oy)
+                    w0, w1 = max(0, -ox), min(W, W - ox)
+                    if h0 >= h1 or w0 >= w1:
+                        continue
+                    xs = x[:, ci, h0 + oy:h1 + oy, w0 + ox:w1 + ox]
+                    gs = dy[:, co, h0:h1, w0:w1]
+                    y[:, co, h0:h1, w0:w1] += w[co, cl, r, s] * xs
+                    dx[:, ci, h0 + oy:h1 + oy, w0 + ox:w1 + ox] += w[co, cl, r, s] * gs
+                    dw[co, cl, r, s] = (xs * gs).sum()
+    if b is not None:
+        y += np.asarray(b.numpy()).astype(np.int64)[None, :, None, None]
+    return y, dx, dw
+
+
+# ---- tables ------------------------------------------------------------------------------------------------------------------
+P = "conv_igemm_pipe_kernel"
+T = "conv3x3_tile_kernel"
+
+
+def _c(dtype, shape, fwd, dgrad=None, **kw):
+    N, H, W, Cin, Cout, k, dil = shape
+    return Case(dtype, N, H, W, Cin, Cout, k, dil, fwd=fwd, dgrad=dgrad or fwd, **kw)
+
+
+FWD_CASES = [
+    # the 4-wave pipelined kernel, 3x3: 8-row tiles / 4-row tiles / 16-row tiles / 64-cout tiles; H, W ragged against the tile
+    _c("bf16", (1, 9, 33, 8, 8, 3, 1), P + "<1, 3, 3, 2>"),
+    _c("bf16", (1, 17, 33, 64, 32, 3, 1), P + "<1, 3, 3, 2>", bias=True),
+    _c("bf16", (1, 9, 33, 3, 32, 3, 1), P + "<1, 3, 3, 2>"),                       # Cin = 3 in 8
+    _c("bf16", (1, 13, 65, 8, 8, 3, 1), P + "<1, 3, 3, 2>", bias=True),
+    _c("bf16", (1, 21, 65, 64, 32, 3, 1), P + "<1, 3, 3, 2>"),
+    _c("bf16", (1, 11, 33, 3, 32, 3, 1), P + "<1, 3, 3, 2>", bias=True),
+    _c("bf16", (1, 17, 33, 128, 128, 3, 1), P + "<1, 3, 3, 1>"),
+    _c("bf16", (1, 19, 65, 128, 128, 3, 1), P + "<1, 3, 3, 1>", bias=True),
+    _c("bf16", (4, 120, 250, 32, 24, 3, 1), P + "<1, 3, 3, 4>", bias=True, fast=True),
+    _c("bf16", (4, 121, 225, 16, 24, 3, 1), P + "<1, 3, 3, 4>", fast=True),
+    _c("bf16", (1, 64, 512, 48, 96, 3, 1), P + "<2, 3, 3, 2>", P + "<1, 3, 3, 2>", fast=True),
+    _c("bf16", (1, 65, 513, 48, 96, 3, 1), P + "<2, 3, 3, 2>", P + "<1, 3, 3, 2>", bias=True, fast=True),
+    _c("bf16", (1, 50, 300, 256, 256, 3, 1), P + "<2, 3, 3, 2>", fast=True),
+    # 1x1
+    _c("bf16", (1, 9, 33, 72, 24, 1, 1), P + "<1, 1, 1, 2>", bias=True),
+    _c("bf16", (1, 9, 33, 32, 2, 1, 1), P + "<1, 1, 1, 2>", bias=True),              # Cout = 2 in 8
+    _c("bf16", (1, 13, 65, 72, 24, 1, 1), P + "<1, 1, 1, 2>"),
+    _c("bf16", (2, 61, 513, 16, 64, 1, 1), P + "<2, 1, 1, 2>", "conv_direct_kernel<1, true>", bias=True, fast=True),
+    # 7x7 by kernel rows
+    _c("bf16", (1, 9, 33, 2, 1, 7, 1), P + "<1, 1, 7, 2>"),                          # 2 -> 1 channels in 8 -> 8
+    _c("bf16", (1, 13, 65, 2, 1, 7, 1), P + "<1, 1, 7, 2>", bias=True),
+    _c("bf16", (1, 50, 300, 24, 40, 7, 1), P + "<1, 1, 7, 2>", bias=True, fast=True),
+    _c("bf16", (2, 61, 513, 8, 40, 7, 1), P + "<2, 1, 7, 2>", P + "<1, 1, 7, 2>", fast=True),
+    # the generic LDS-tiled kernel (5x5 in bf16)
+    _c("bf16", (1, 9, 33, 16, 16, 5, 1), "conv_igemm_kernel<bf16_t, 1>", bias=True),
+    _c("bf16", (1, 13, 65, 16, 16, 5, 1), "conv_igemm_kernel<bf16_t, 1>"),
+    _c("bf16", (2, 61, 513, 8, 40, 5, 1), "conv_igemm_kernel<bf16_t, 2>", "conv_igemm_kernel<bf16_t, 1>", fast=True),
+    # the LDS-free kernel: wide-in / narrow-out 1x1, dilated 3x3
+    _c("bf16", (2, 40, 44, 112, 16, 1, 1), "conv_direct_kernel<1, true>", P + "<1, 1, 1, 2>", bias=True),
+    _c("bf16", (1, 13, 65, 112, 16, 1, 1), "conv_direct_kernel<1, true>", P + "<1, 1, 1, 2>"),
+    _c("bf16", (1, 30, 40, 32, 32, 3, 12), "conv_direct_kernel<1, false>"),
+    _c("bf16", (1, 35, 65, 32, 32, 3, 12), "conv_direct_kernel<1, false>", bias=True),
+    _c("bf16", (1, 129, 130, 24, 24, 3, 12), "conv_direct_kernel<1, false>", bias=True),
+    _c("bf16", (1, 30, 40, 64, 64, 3, 12), "conv_direct_kernel<2, false>"),
+    # 16 -> 16 channels with the weights in registers: 7x7, dilated 3x3 (dilation 36 on 40 x 44: most taps fall outside)
+    _c("bf16", (1, 9, 33, 16, 16, 7, 1), "conv7x7_c16_kernel", bias=True),
+    _c("bf16", (1, 13, 65, 16, 16, 7, 1), "conv7x7_c16_kernel"),
+    _c("bf16", (1, 30, 40, 16, 16, 3, 2), "conv3x3d_c16_kernel"),
+    _c("bf16", (1, 30, 40, 16, 16, 3, 12), "conv3x3d_c16_kernel", bias=True),
+    _c("bf16", (1, 35, 65, 16, 16, 3, 12), "conv3x3d_c16_kernel"),
+    _c("bf16", (1, 40, 44, 16, 16, 3, 36), "conv3x3d_c16_kernel"),
+    # the 8-wave LDS-DMA tile kernel: the four tile shapes the planner offers (forward) and what the swapped counts take (data gradient)
+    _c("bf16", (2, 250, 250, 64, 128, 3, 1), T + "<4, 2, 4, 2, 2>", T + "<2, 2, 8, 1, 2>", bias=True, fast=True),
+    _c("bf16", (8, 64, 64, 32, 256, 3, 1), T + "<2, 2, 4, 2, 2>", P + "<1, 3, 3, 2>", fast=True),
+    _c("bf16", (8, 128, 128, 32, 64, 3, 1), T + "<2, 2, 8, 1, 2>", P + "<1, 3, 3, 4>", bias=True, fast=True),
+    _c("bf16", (3, 500, 260, 32, 64, 3, 1), T + "<4, 2, 8, 1, 2>", P + "<1, 3, 3, 4>", fast=True),
+    # the same four with H no multiple of the tile rows and W = 32 m + 1: the last tile column is ONE pixel wide (the edge masks of the
+    # LDS-DMA halo and of the epilogue); each still large enough for the planner's floor of 192 workgroups
+    _c("bf16", (2, 249, 225, 64, 128, 3, 1), T + "<4, 2, 4, 2, 2>", T + "<2, 2, 8, 1, 2>", fast=True),
+    _c("bf16", (6, 57, 33, 32, 256, 3, 1), T + "<2, 2, 4, 2, 2>", P + "<1, 3, 3, 2>", bias=True, fast=True),
+    _c("bf16", (8, 121, 129, 32, 64, 3, 1), T + "<2, 2, 8, 1, 2>", P + "<1, 3, 3, 4>", fast=True),
+    _c("bf16", (3, 499, 257, 32, 64, 3, 1), T + "<4, 2, 8, 1, 2>", P + "<1, 3, 3, 4>", bias=True, fast=True),
+    # its two 32-cout tile shapes, offered under egm_conv_tile_mode(7) only
+    _c("bf16", (3, 250, 250, 32, 32, 3, 1), T + "<4, 1, 8, 1, 2>", mode=7, bias=True, fast=True),
+    _c("bf16", (2, 250, 250, 16, 32, 3, 1), T + "<2, 1, 8, 1, 2>", P + "<1, 3, 3, 4>", mode=7, fast=True),
+    _c("bf16", (3, 249, 225, 32, 32, 3, 1), T + "<4, 1, 8, 1, 2>", mode=7, fast=True),                # ragged, one-pixel last column
+    _c("bf16", (2, 249, 225, 16, 32, 3, 1), T + "<2, 1, 8, 1, 2>", P + "<1, 3, 3, 4>", mode=7, bias=True, fast=True),
+    # the weights-in-registers 3x3 kernel (32 -> 32)
+    _c("bf16", (2, 500, 270, 32, 32, 3, 1), "conv3x3_wreg_kernel<1>", bias=True, fast=True),
+    _c("bf16", (2, 499, 257, 32, 32, 3, 1), "conv3x3_wreg_kernel<1>", fast=True),                     # odd H, one-pixel last column
+    # fp32: the exact parity path
+    _c("f32", (1, 9, 33, 8, 8, 3, 1), "conv_igemm_kernel<float, 1>", bias=True),
+    _c("f32", (1, 13, 65, 8, 8, 3, 1), "conv_igemm_kernel<float, 1>"),
+    _c("f32", (1, 17, 33, 64, 64, 3, 1), "conv_igemm_kernel<float, 1>"),
+    _c("f32", (1, 9, 33, 16, 16, 7, 1), "conv_igemm_kernel<float, 1>", bias=True),
+    _c("f32", (1, 30, 40, 16, 16, 3, 12), "conv_igemm_kernel<float, 1>"),
+    _c("f32", (2, 61, 513, 8, 40, 3, 1), "conv_igemm_kernel<float, 2>", "conv_igemm_kernel<float, 1>", bias=True, fast=True),
+    # grouped: the block-diagonal pack (groups = 2; groups = Cin, 1 -> 2 per group)
+    _c("bf16", (2, 16, 20, 8, 16, 3, 1), P + "<1, 3, 3, 2>", groups=2),
+    _c("bf16", (2, 16, 20, 8, 16, 3, 1), P + "<1, 3, 3, 2>", groups=8, bias=True),
+]
+FWD_CASES = [c._replace(seed=i) for i, c in enumerate(FWD_CASES)]
+
+
+def fwd_case(dtype, shape, mode=5, groups=1):
+    """The table's case of a shape (the act / split tests reuse the operands and the reference of the plain forward case)."""
+    hit = [c for c in FWD_CASES if c.dtype == dtype and (c.N, c.H, c.W, c.Cin, c.Cout, c.k, c.dil) == shape and c.mode == mode and c.groups == groups]
+    assert len(hit) == 1, (dtype, shape, len(hit))
+    return hit[0]
+
+
+RELU_SHAPES = [(1, 17, 33, 64, 32, 3, 1), (8, 64, 64, 32, 256, 3, 1), (2, 500, 270, 32, 32, 3, 1)]     # a pipe, a tile and the weights-in-registers case
+SPLIT_SHAPE, SPLIT_AT = (8, 128, 128, 32, 64, 3, 1), 32
+GROUP_LAUNCH = [_c("bf16", (1, 9, 33, 16, 16, 3, 1), P + "<1, 3, 3, 2>", seed=201), _c("bf16", (1, 17, 35, 16, 16, 3, 1), P + "<1, 3, 3, 2>", bias=True, seed=202),
+                _c("bf16", (1, 12, 70, 16, 16, 3, 1), P + "<1, 3, 3, 2>", seed=203)]
+
+WS = "conv_wgrad_ws_kernel"
+WG = "conv_wgrad_kernel"
+
+
+def _w(dtype, shape, wgrad, **kw):
+    N, H, W, Cin, Cout, k, dil = shape
+    return Case(dtype, N, H, W, Cin, Cout, k, dil, wgrad=wgrad, **kw)
+
+
+WGRAD_CASES = [
+    # pixel tiles (8 x 32) that do NOT divide evenly over the K-splits
+    _w("bf16", (1, 50, 300, 256, 256, 3, 1), WS + "<9, 1>", uneven=True, fast=True),     # 70 tiles over 16 splits
+    _w("bf16", (1, 50, 300, 128, 128, 3, 1), WS + "<9, 1>", uneven=True, fast=True),     # 70 over 64
+    _w("bf16", (3, 100, 300, 32, 32, 3, 1), WS + "<9, 4>", uneven=True, bias=True, fast=True),   # 390 over 256
+    _w("bf16", (1, 50, 300, 32, 32, 5, 1), WS + "<5, 0>", uneven=True, fast=True),       # 70 over 51
+    _w("bf16", (1, 50, 300, 24, 40, 7, 1), WS + "<7, 0>", uneven=True, bias=True, fast=True),    # 70 over 36
+    _w("bf16", (1, 50, 300, 16, 16, 7, 1), "conv7x7_c16_wgrad_kernel", uneven=True, fast=True),  # 70 over 65 (slab count from the query)
+    # one tile per split, tiny, every family
+    _w("bf16", (1, 9, 33, 8, 8, 3, 1), WS + "<9, 4>"),
+    _w("bf16", (1, 9, 33, 3, 32, 3, 1), WS + "<9, 4>", bias=True),                       # CinR = 3 in 8
+    _w("bf16", (1, 9, 33, 3, 2, 3, 1), WS + "<9, 4>", bias=True),                        # CinR = 3 in 8, CoutR = 2 in 8
+    _w("bf16", (1, 9, 33, 16, 40, 3, 1), WS + "<9, 2>"),
+    _w("bf16", (1, 17, 33, 64, 32, 3, 1), WS + "<9, 2>", bias=True),
+    _w("bf16", (2, 17, 35, 64, 64, 3, 1), WS + "<9, 1>"),
+    _w("bf16", (1, 9, 33, 16, 16, 5, 1), WS + "<5, 0>", bias=True),
+    _w("bf16", (1, 9, 33, 2, 1, 7, 1), WS + "<7, 0>"),
+    _w("bf16", (1, 9, 33, 72, 24, 1, 1), WG + "<bf16_t, 1>", bias=True),
+    _w("bf16", (1, 30, 40, 32, 32, 3, 12), WG + "<bf16_t, 1>"),
+    _w("bf16", (1, 129, 130, 32, 32, 3, 12), WG + "<bf16_t, 3>", bias=True),             # row-patch dilated path (H, W >= 128)
+    _w("bf16", (1, 30, 40, 16, 16, 3, 12), "conv3x3d_c16_wgrad_kernel"),
+    _w("bf16", (1, 9, 33, 16, 16, 7, 1), "conv7x7_c16_wgrad_kernel", bias=True),
+    # groups
+    _w("bf16", (2, 16, 20, 8, 16, 3, 1), WS + "<9, 4>", groups=2),
+    _w("bf16", (2, 16, 20, 8, 16, 3, 1), WS + "<9, 4>", groups=8, bias=True),
+    # fp32
+    _w("f32", (1, 9, 33, 8, 8, 3, 1), WG + "<float, 9>"),
+    _w("f32", (1, 9, 33, 3, 2, 3, 1), WG + "<float, 9>", bias=True),
+    _w("f32", (1, 17, 33, 64, 64, 3, 1), WG + "<float, 9>", bias=True),
+    _w("f32", (1, 9, 33, 16, 16, 7, 1), WG + "<float, 7>"),
+    _w("f32", (1, 9, 33, 16, 16, 5, 1), WG + "<float, 5>"),
+    _w("f32", (1, 30, 40, 16, 16, 3, 12), WG + "<float, 1>", bias=True),
+    _w("f32", (1, 129, 130, 16, 16, 3, 12), WG + "<float, 3>"),
+    _w("f32", (2, 16, 20, 8, 16, 3, 1), WG + "<float, 9>", groups=2),
+]
+WGRAD_CASES = [c._replace(seed=100 + i) for i, c in enumerate(WGRAD_CASES)]
+
+# every kernel name the planner queries can return at tile modes 5 and 7 (read from conv_plan / wgrad_plan in csrc/conv_igemm.hip and
+# csrc/conv_wgrad.hip); conv_direct_kernel<2, true> does not exist as a plan (the 1x1 form is taken for Cout <= 16 only)
+ALL_FWD_NAMES = {P + s for s in ("<1, 3, 3, 2>", "<2, 3, 3, 2>", "<1, 3, 3, 1>", "<1, 3, 3, 4>", "<1, 1, 1, 2>", "<2, 1, 1, 2>", "<1, 1, 7, 2>", "<2, 1, 7, 2>")} | {
+    T + s for s in ("<4, 2, 4, 2, 2>", "<2, 2, 4, 2, 2>", "<4, 2, 8, 1, 2>", "<2, 2, 8, 1, 2>", "<4, 1, 8, 1, 2>", "<2, 1, 8, 1, 2>")} | {
+    "conv_igemm_kernel<bf16_t, 1>", "conv_igemm_kernel<bf16_t, 2>", "conv_igemm_kernel<float, 1>", "conv_igemm_kernel<float, 2>",
+    "conv_direct_kernel<1, true>", "conv_direct_kernel<1, false>", "conv_direct_kernel<2, false>", "conv7x7_c16_kernel", "conv3x3d_c16_kernel",
+    "conv3x3_wreg_kernel<1>"}
+ALL_WGRAD_NAMES = {WS + "<9, 1>", WS + "<9, 2>", WS + "<9, 4>", WS + "<7, 0>", WS + "<5, 0>", WG + "<bf16_t, 1>", WG + "<bf16_t, 3>",
+                   "conv7x7_c16_wgrad_kernel", "conv3x3d_c16_wgrad_kernel"} | {WG + f"<float, {t}>" for t in (9, 7, 5, 3, 1)}
+
+DW_SHAPES = [(1, 9, 33, 8), (2, 17, 35, 24)]           # depthwise 3x3: N, H, W, C
+
+
+def dw_operands(shape, seed):
+    N, H, W, C = shape
+    g = torch.Generator().manual_seed(3000 + seed)
+
+    def pm12(*s):
+        return (torch.randint(1, 3, s, generator=g) * (torch.randint(0, 2, s, generator=g) * 2 - 1)).double()
+
+    x, dy = pm12(N, C, H, W), pm12(N, C, H, W)
+    w = (torch.randint(0, 2, (C, 1, 3, 3), generator=g) * 2 - 1).double()
+    b = torch.randint(-3, 4, (C,), generator=g).double()
+    return x, w, b, dy
+
+
+def dw_ref(x, w, b, dy, scale):
+    """y = (depthwise3x3(x, w) + b) * scale and its gradients, float64 autograd."""
+    xr, wr, br = (t.clone().requires_grad_(True) for t in (x, w, b))
+    sr = torch.tensor(float(scale), dtype=torch.float64, requires_grad=True)
+    y = (F.conv2d(xr, wr, br, padding=1, groups=x.shape[1])) * sr
+    dx, dw, db, ds = torch.autograd.grad(y, [xr, wr, br, sr], dy)
+    ref = {"y": y.detach(), "dx": dx, "dw": dw, "db": db, "ds": ds.reshape(1)}
+    for n, t in ref.items():
+        if not _is_int(t) or float(t.abs().max()) > (VALUE_LIMIT if n in ("y", "dx") else SUM_LIMIT - 1):
+            raise ValueError(f"depthwise {tuple(x.shape)} scale {scale}: {n} leaves the exact range")
+    return ref
+
+
+# ---- planner queries (no device needed) -----------------------------------------------------------------------------------------
+def kernel_name(L, fn, c, swap=False):
+    """egm_conv_kernel_name / egm_conv_wgrad_kernel_name of a case (padded counts; swap = the data gradient's call)."""
+    import ctypes
+    ci, co = pad8(c.Cin), pad8(c.Cout)
+    if swap:
+        ci, co = co, ci
+    buf = ctypes.create_string_buffer(96)
+    getattr(L.cdll, fn)(0 if c.dtype == "f32" else 1, c.N, c.H, c.W, ci, co, c.k, c.k, c.dil, ctypes.cast(buf, ctypes.c_void_p), 96)
+    return buf.value.decode()
+
+
+def wgrad_split(L, c):
+    """-> (K-splits = slabs, pixel tiles of 8 x 32) of a weight-gradient case"""
+    slabs = L.query("egm_conv_wgrad_slabs", 0 if c.dtype == "f32" else 1, c.N, c.H, c.W, pad8(c.Cin), pad8(c.Cout), c.k, c.k, c.dil)
+    return slabs, c.N * ((c.H + 7) // 8) * ((c.W + 31) // 32)
+
+
+# ---- what the exact comparison reports ----------------------------------------------------------------------------------------
+def mismatch_report(got_nhwc, want_nhwc, th=8, tw=32):
+    """'' when equal; else the count of wrong elements, the first few (n, h, w, c) with got / want, and whether they sit on the last
+    tile row / column (tiles of th x tw pixels).  NaN in `got` counts as wrong."""
+    got, want = got_nhwc.double(), want_nhwc.double()
+    bad = ~(got == want)
+    n = int(bad.sum())
+    if n == 0:
+        return ""
+    idx = bad.nonzero()
+    H, W = got.shape[1], got.shape[2]
+    last_row = idx[:, 1] >= (H - 1) // th * th
+    last_col = idx[:, 2] >= (W - 1) // tw * tw
+    first = "; ".join(f"{tuple(int(v) for v in i)}: got {float(got[tuple(i)]):g} want {float(want[tuple(i)]):g}" for i in idx[:6])
+    return (f"{n}/{bad.numel()} wrong; first {first}; on the last tile row: {int(last_row.sum())}, on the last tile column: {int(last_col.sum())}, "
+            f"elsewhere: {int((~last_row & ~last_col).sum())}")
