@@ -446,6 +446,121 @@ def contour_f_report(counts):
             "f_images": f_images, "mean_f_images": mean_f_images}
 
 
+SURFACE_BINS = 256                          # bins of ceil(d) in pixels, the last one "255 or more"
+SURFACE_FIELDS = 4 + SURFACE_BINS           # n, sum of floor(256 d), sum of d^2, max d^2, then the bins (csrc/surface.hip)
+_SURFACE_MAX_SIDE = 32767                   # kSurfaceMaxSide: d^2 < 2^31 and a row distance fits 16 bits
+_SURFACE_MAX_TOLERANCE = SURFACE_BINS - 2   # the last bin is open-ended: a cumulative count is exact up to 254
+_surface_workspace_cache = collections.OrderedDict()
+
+
+def surface_workspace(N, H, W, num_classes, device):
+    """boundary_workspace for surface_counts_u8 / surface_dist2_u8 on [N, H, W] images of num_classes classes (1 + 4 C bytes per
+    pixel: the contour byte and a 16-bit row distance per side and class)."""
+    return torch.empty(lib().query("egm_surface_workspace", int(N), int(H), int(W), int(num_classes)), dtype=torch.uint8, device=device)
+
+
+def _surface_call(name, pred_u8, label_u8, num_classes, pred_values, label_values, workspace, counts, want_maps):
+    """The checks and the one call that surface_counts_u8 and surface_dist2_u8 share -> (counts, d2_pred, d2_label)."""
+    require_gpu()
+    p, t = _boundary_images(name, [("pred", pred_u8), ("label", label_u8)])
+    N, H, W = p.shape
+    if H > _SURFACE_MAX_SIDE or W > _SURFACE_MAX_SIDE:
+        raise ValueError(f"{name}: {H} x {W} pixels, at most {_SURFACE_MAX_SIDE} rows and columns are supported")
+    C, dev = int(num_classes), p.device
+    pt, lt = _class_table_dev(pred_values, C, dev), _class_table_dev(label_values, C, dev)
+    if counts is True:
+        counts = torch.zeros((N, C, 2, SURFACE_FIELDS), dtype=torch.int64, device=dev)
+    elif counts is not None and not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int64
+                                     and tuple(counts.shape) == (N, C, 2, SURFACE_FIELDS) and counts.is_contiguous()):
+        raise ValueError(f"{name}: out must be a contiguous int64 CUDA tensor [{N}, {C}, 2, {SURFACE_FIELDS}]")
+    maps = [torch.empty((N, H, W), dtype=torch.int32, device=dev) for _ in range(2)] if want_maps else [None, None]
+    ws = _cached_workspace(_surface_workspace_cache, "egm_surface_workspace", (N, H, W, C), dev, workspace)
+    lib().call("egm_mask_surface_dist_u8", ptr(p), ptr(t), N, H, W, ptr(pt), ptr(lt), C, ptr(ws), ptr(counts), ptr(maps[0]), ptr(maps[1]),
+               stream())
+    return counts, maps[0], maps[1]
+
+
+def surface_counts_u8(pred_u8, label_u8, num_classes=2, pred_values=None, label_values=None, out=None, workspace=None):
+    """The counts behind the surface distances (Hausdorff, HD95, ASSD, surface Dice) of a predicted mask against its ground truth on
+    the device: uint8 CUDA tensors of equal shape ([H, W], or a batch [N, H, W] of independent images) -> int64 [N, C, 2,
+    SURFACE_FIELDS].  K = a side's contour (contour_u8); for p in Kpred_k, d^2(p) = the least |p - q|^2 over q in Klabel_k of the same
+    image, an exact integer, never truncated (csrc/surface.hip).  Direction 0 is pred -> label, direction 1 label ->
+    pred; per image, class and direction: [0] n = |K| of the asking side, [1] the sum of floor(256 d), [2] the sum of d^2, [3] the
+    largest d^2, [4 + t] the pixels with ceil(d) = t for t = 0..255, the last bin holding "255 or more".  Where the other side has no
+    contour of the class in the image only n is counted.  The bins summed up to theta are contour_f_counts_u8(theta)'s mp and mg.
+    pred_values / label_values: see class_table.  out: an int64 [N, C, 2, SURFACE_FIELDS] CUDA tensor to accumulate into (and
+    returned): sums add, field 3 is combined with max.  workspace: a surface_workspace(N, H, W, num_classes, device), see
+    boundary_counts_u8.  H and W are at most 32767 (ValueError above).  Two launches, no host wait.  surface_report turns the counts
+    into the scores."""
+    return _surface_call("surface_counts_u8", pred_u8, label_u8, num_classes, pred_values, label_values, workspace,
+                         True if out is None else out, False)[0]
+
+
+def surface_dist2_u8(pred_u8, label_u8, num_classes=2, pred_values=None, label_values=None, workspace=None):
+    """The distances surface_counts_u8 counts, to look at: -> (d2_pred, d2_label), int32 CUDA tensors of the inputs' shape.  d2_pred
+    holds d^2 to the label's contour of the pixel's own class at the prediction's contour pixels, d2_label the mirror image; -1
+    everywhere else and where the other side has no contour of that class in the image.  Arguments as for surface_counts_u8.  Two
+    launches, no host wait."""
+    _, dp, dl = _surface_call("surface_dist2_u8", pred_u8, label_u8, num_classes, pred_values, label_values, workspace, None, True)
+    return dp.reshape(pred_u8.shape), dl.reshape(label_u8.shape)
+
+
+def surface_report(counts, tolerance=2, spacing=1.0):
+    """The surface distances from surface_counts_u8's counts ([N, C, 2, SURFACE_FIELDS] tensor or array; [C, 2, SURFACE_FIELDS] is one
+    image), in numpy float64 in the style of contour_f_report.  Per image and class, from the two directions 0 and 1:
+      hd    sqrt(max(max_d2_0, max_d2_1)) * spacing: the Hausdorff distance of the two contours
+      assd  (sum_q_0 + sum_q_1) / 256 / (n_0 + n_1) * spacing: the average symmetric surface distance, low by less than 1/256 pixel
+      rmsd  sqrt((sum_d2_0 + sum_d2_1) / (n_0 + n_1)) * spacing
+      hd95  per direction the nearest rank r = (95 n + 99) // 100 and the smallest t whose cumulative bins reach r, i.e. the
+            direction's 95th percentile rounded UP to whole pixels (within one pixel of the interpolated percentile); the larger of
+            the two directions, times spacing.  A rank that lands in the open last bin takes ceil(sqrt(max_d2)) of its direction
+            and sets hd95_capped.  Restated from the definitions, not checked against medpy or MONAI.
+      nsd   (cum_0[tau] + cum_1[tau]) / (n_0 + n_1): the surface Dice at tolerance tau (Nikolov et al. 2018), tau = tolerance in
+            pixels, an int 0..254 or one per image
+    An image and class where either contour is empty is undefined: NaN in every *_images array, counted in undefined [C], and in
+    one_empty [C] too where exactly one side is empty.  hd, hd95, assd, rmsd, nsd [C] are the means over the defined images, NaN for
+    a class defined in no image.  spacing: one isotropic pixel size > 0.  -> dict(hd, hd95, assd, rmsd, nsd [C], hd_images ...
+    nsd_images [N, C], hd95_capped [N, C] bool, undefined, one_empty [C] int64, n_images).  ValueError for a wrong shape, a tolerance
+    outside 0..254 or of the wrong length, or a spacing <= 0."""
+    c = np.asarray(counts.detach().cpu() if isinstance(counts, torch.Tensor) else counts).astype(np.int64)
+    if c.ndim == 3:
+        c = c[None]
+    if c.ndim != 4 or c.shape[2:] != (2, SURFACE_FIELDS):
+        raise ValueError(f"surface_report: counts [N, C, 2, {SURFACE_FIELDS}] expected, got {c.shape}")
+    N, C = c.shape[:2]
+    tau = np.asarray(tolerance)
+    if tau.dtype == np.bool_ or not np.issubdtype(tau.dtype, np.integer) or tau.ndim > 1 or (tau.ndim == 1 and tau.shape[0] != N):
+        raise ValueError(f"surface_report: tolerance must be an int or {N} ints (one per image), got {tolerance!r}")
+    tau = np.broadcast_to(tau.astype(np.int64), (N,))
+    if N and (tau.min() < 0 or tau.max() > _SURFACE_MAX_TOLERANCE):
+        raise ValueError(f"surface_report: tolerance between 0 and {_SURFACE_MAX_TOLERANCE} pixels expected, got {tolerance!r}")
+    if isinstance(spacing, (bool, np.bool_)) or not isinstance(spacing, (int, float, np.integer, np.floating)) or not spacing > 0:
+        raise ValueError(f"surface_report: spacing must be a pixel size > 0, got {spacing!r}")
+    spacing = float(spacing)
+    n, sum_q, sum_d2, max_d2 = (c[..., f] for f in range(4))                  # each [N, C, 2]
+    cum = np.cumsum(c[..., 4:], axis=-1)                                       # [N, C, 2, 256]
+    defined = (n > 0).all(-1)
+    both = np.maximum(n.sum(-1), 1).astype(np.float64)
+    root = np.floor(np.sqrt(max_d2.astype(np.float64))).astype(np.int64)       # exact below 2^52
+    ceil_max = root + (root * root < max_d2)
+    rank = (95 * n + 99) // 100
+    t = (cum < rank[..., None]).sum(-1)                                        # the first bin whose cumulative count reaches the rank
+    capped = (t >= SURFACE_BINS - 1) & defined[..., None]
+    t = np.where(t >= SURFACE_BINS - 1, ceil_max, t)
+    near = np.take_along_axis(cum, np.broadcast_to(tau[:, None, None, None], (N, C, 2, 1)), axis=-1)[..., 0]
+    images = {"hd": np.sqrt(max_d2.max(-1).astype(np.float64)) * spacing, "hd95": t.max(-1).astype(np.float64) * spacing,
+              "assd": sum_q.sum(-1) / 256.0 / both * spacing, "rmsd": np.sqrt(sum_d2.sum(-1) / both) * spacing, "nsd": near.sum(-1) / both}
+    rep = {}
+    for key, v in images.items():
+        rep[key + "_images"] = np.where(defined, v, np.nan)
+        rep[key] = np.where(defined.any(0), np.where(defined, v, 0.0).sum(0) / np.maximum(defined.sum(0), 1), np.nan)
+    rep["hd95_capped"] = capped.any(-1)
+    rep["undefined"] = (~defined).sum(0).astype(np.int64)
+    rep["one_empty"] = ((n > 0).sum(-1) == 1).sum(0).astype(np.int64)
+    rep["n_images"] = N
+    return rep
+
+
 def _label_u8(t, device):
     """A ground-truth mask (numpy or tensor, 0..255) as a contiguous uint8 tensor on the device, [N, Hl, Wl]."""
     t = torch.as_tensor(t)
@@ -788,7 +903,7 @@ class EnsemblePredictor:
         self.alpha = best
         return best, best_miou, m
 
-    def evaluate(self, images, gt_masks, batch_size=None, boundary=None, boundary_metric="box", contour_f=None):
+    def evaluate(self, images, gt_masks, batch_size=None, boundary=None, boundary_metric="box", contour_f=None, surface=None):
         """evaluating_indicator.py's compute_mIoU (:347-417) over this pipeline without the PNGs in between: every photo's mask
         (__call__, or predict_batch over plan_batches with batch_size) is counted against its uint8 ground truth [H0, W0] (0/255 PNG
         bytes, the reference's / 255 rule) on the device, one confusion_u8 call per photo or batch into one matrix, and one copy to the
@@ -801,9 +916,12 @@ class EnsemblePredictor:
         contour, which the region scores hardly see.  boundary_metric: the band's metric, "box" or "euclid" (boundary_counts_u8).
         contour_f (None = off; otherwise the tolerance of contour_f_counts_u8 as a ratio or in pixels): the masks also go through
         contour_f_counts_u8 in the same place, and the report gains "contour_f" = contour_f_report's dict, f_images in input order.
-        Both arguments and the metric are checked against every kept photo's size before any photo is run; all counts travel in the
-        one copy to the host.
-        -> score_report's dict plus "skipped" (plus "boundary", plus "contour_f")."""
+        surface (None = off; otherwise the surface Dice's tolerance, by contour_radius's rules: an int is pixels, a float a ratio of
+        the photo's diagonal): the masks also go through surface_counts_u8 in the same place, and the report gains "surface" =
+        surface_report's dict (hd, hd95, assd, rmsd, nsd) with every photo's own tolerance, the *_images in input order.
+        All three arguments and the metric are checked against every kept photo's size before any photo is run; all counts travel in
+        the one copy to the host.
+        -> score_report's dict plus "skipped" (plus "boundary", plus "contour_f", plus "surface")."""
         images, gt_masks = list(images), list(gt_masks)
         if len(images) != len(gt_masks):
             raise ValueError(f"evaluate: {len(images)} images and {len(gt_masks)} ground-truth masks")
@@ -818,24 +936,28 @@ class EnsemblePredictor:
                 radius_of(*gt_masks[i].shape, boundary)
             if contour_f is not None:
                 contour_radius(*gt_masks[i].shape, contour_f, "contour_f")
-        order, bcounts, fcounts = [], [], []                               # photos in the order scored, their [n, C, 3] and [n, C, 4] counts
+            if surface is not None:
+                contour_radius(*gt_masks[i].shape, surface, "surface")
+        order, bcounts, fcounts, scounts = [], [], [], []                  # photos in the order scored, their [n, C, 3 / 4 / 2 x 260] counts
 
         def score(idx, masks, gts):
             confusion_u8(masks, gts, C, pred_values, None, out=hist)
-            if boundary is not None or contour_f is not None:
+            if boundary is not None or contour_f is not None or surface is not None:
                 order.extend(idx)
             if boundary is not None:
                 bcounts.append(boundary_counts_u8(masks, gts, boundary, C, pred_values, None, metric=boundary_metric))
             if contour_f is not None:
                 fcounts.append(contour_f_counts_u8(masks, gts, contour_f, C, pred_values, None))
+            if surface is not None:
+                scounts.append(surface_counts_u8(masks, gts, C, pred_values, None))
         if batch_size is None:
             for i in keep:
                 score([i], self(images[i]), _label_u8(gt_masks[i], dev)[0])
         else:
             for idx, batch in _padded_batches(images, batch_size, keep):
                 score(idx, self.predict_batch(batch)[:len(idx)], torch.cat([_label_u8(gt_masks[i], dev) for i in idx]))
-        if boundary is not None or contour_f is not None:
-            parts = [hist.reshape(-1)] + [torch.cat(c).reshape(-1) for c in (bcounts, fcounts) if c]
+        if boundary is not None or contour_f is not None or surface is not None:
+            parts = [hist.reshape(-1)] + [torch.cat(c).reshape(-1) for c in (bcounts, fcounts, scounts) if c]
             both = torch.cat(parts).cpu()                                  # the one copy to the host
             hist, rest = both[:C * C].reshape(C, C), both[C * C:].numpy()
             by_input = np.argsort(np.asarray(order, dtype=np.int64), kind="stable")
@@ -846,5 +968,9 @@ class EnsemblePredictor:
             report["boundary"] = boundary_report(rest[:n * C * 3].reshape(n, C, 3)[by_input])
             rest = rest[n * C * 3:]
         if contour_f is not None:
-            report["contour_f"] = contour_f_report(rest.reshape(n, C, 4)[by_input])
+            report["contour_f"] = contour_f_report(rest[:n * C * 4].reshape(n, C, 4)[by_input])
+            rest = rest[n * C * 4:]
+        if surface is not None:
+            taus = [contour_radius(*gt_masks[i].shape, surface, "surface") for i in sorted(order)]
+            report["surface"] = surface_report(rest.reshape(n, C, 2, SURFACE_FIELDS)[by_input], tolerance=taus)
         return report

@@ -785,6 +785,28 @@ int egm_mask_contour_f_u8(const unsigned char* pred, const unsigned char* label,
                           const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
                           unsigned long long* counts, unsigned char* contour_pred, unsigned char* contour_label, egm_stream_t s);
 
+/* ---- Surface distances of uint8 masks at their own size (csrc/surface.hip) ---------------------------------------------
+ * Images, class tables, C, the independence of a batch's images and the contour K_k of a side (4-neighbours inside the image, the
+ * frame makes none, a dropped byte is "not k") as for egm_mask_contour_f_u8.  For a pixel p of Kpred_k, d2(p) = the minimum over q in
+ * Klabel_k of |p - q|^2 in the same image, an exact integer, never truncated: direction 0 is pred -> label, direction 1 label -> pred.
+ * counts [N][C][2][260] uint64, caller-zeroed and accumulated across calls (may be NULL), per image, class and direction:
+ *   [0] n = |K| of the asking side; [1] the sum of q = isqrt(d2 * 2^16) = floor(256 d); [2] the sum of d2; [3] the largest d2 (combined
+ *   with max, not add); [4 + t], t = 0..255: the pixels with ceil(sqrt(d2)) = t in integers, bin 255 = "255 or more".  Where the other
+ *   side's contour of the class is empty in the image the direction has no distances: n is counted, the rest stays as it was.  The
+ *   sum of bins 0..r of direction 0 is egm_mask_contour_f_u8's mp at radius r (r <= 254), of direction 1 its mg.
+ * d2_pred / d2_label int32 [N][H][W] (may be NULL): d2 at the side's contour pixels (for the pixel's own class), -1 everywhere else
+ *   and where the other contour is empty.  Both images are required; at least one of the three outputs must be given.
+ * workspace: egm_surface_workspace(N, H, W, C) bytes of device memory owned by the caller (1 + 4 C bytes per pixel of a padded row:
+ *   the contour byte and a 16-bit row distance per side and class, 0xFFFF = none).
+ * Two launches per call whatever the content, N, C and the distances (rows, then columns); nothing waits for the device, for another
+ * workgroup or for another wave; every device loop has a trip count of at most max(H, the chunks of a row); capturable on one
+ * stream.  H, W <= 32767 (d2 < 2^31, a row distance fits 16 bits), H*W <= 2^30, N*H <= 2^31, any base alignment of the images, the
+ * natural alignment of counts and of the maps; otherwise EGM_ERR_ARG.  Every cell is exact and independent of the order of the adds. */
+long long egm_surface_workspace(int N, int H, int W, int C);
+int egm_mask_surface_dist_u8(const unsigned char* pred, const unsigned char* label, int N, int H, int W,
+                             const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
+                             unsigned long long* counts, int* d2_pred, int* d2_label, egm_stream_t s);
+
 /* ---- batched training data path: B ragged photos with masks -> the batch a train step reads (train.py:14-33, my_dataset.py:118-132)
  * egm_train_batch_u8: for every image b what egm_resample_u8 (axis 1, then axis 0), egm_gather_u8 and egm_augment_u8 compute one
  *   after the other, written into slot b of out_img_bchw fp32 [B][3][slot_h][slot_w] and out_target_bhw int64 [B][slot_h][slot_w]: per
