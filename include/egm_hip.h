@@ -807,6 +807,29 @@ int egm_mask_surface_dist_u8(const unsigned char* pred, const unsigned char* lab
                              const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
                              unsigned long long* counts, int* d2_pred, int* d2_label, egm_stream_t s);
 
+/* ---- Sliding-window inference: overlapping tiles cut and blended on the device (csrc/tiles.hip) -------------------------
+ * A plan cuts every image of an fp32 NCHW batch into ny x nx tiles of h x w pixels: tile t = (n * ny + i) * nx + j covers rows ys[i] ..
+ * ys[i] + h - 1 and columns xs[j] .. xs[j] + w - 1 of image n, T = N * ny * nx tiles.  ys_dev [ny] / xs_dev [nx]: int32 DEVICE tables,
+ * ascending, every tile inside its image, every pixel covered at least once (egm_unet_amd.tiled.TilePlan makes them).
+ * egm_tile_gather_f32: dst fp32 [count][C][h][w], dst[k] = tile min(t0 + k, T - 1) of src: the clamp fills the last chunk of a batched
+ *   loop with copies of the last tile.  0 <= t0 < T, count > 0.  ONE launch whatever count is.
+ * egm_tile_blend_f32: tiles fp32 [T][C][h][w] -> logits_out fp32 NCHW and / or mask_out uint8 [N][H][W] (either may be NULL, not both).
+ *   wy_dev [h] / wx_dev [w]: fp32 DEVICE tables, the two profiles of the separable weight (> 0), made on the host.  A gather: each output
+ *   pixel (y, x) visits the tiles that cover it in ascending t, no atomics, so the result does not depend on scheduling.  The arithmetic
+ *   is fixed so that a float32 restatement gives the same bits: per covering tile wt = wy[y - y0] * wx[x - x0] (one fp32 rounding),
+ *   p = wt * v (one rounding), acc = acc + p and wsum = wsum + wt (one rounding each, never contracted into an FMA), from acc = wsum =
+ *   0; then out = acc / wsum, correctly rounded.  mask = lut[argmax_c out], ties to the lowest class as egm_argmax_u8; lut NULL: the
+ *   index itself.  ONE launch whatever T is; T*C*h*w*4 bytes read, N*C*H*W*4 (+ N*H*W) written.  Offsets into tiles are 64-bit.
+ * Limits: H, W <= 32767, h <= H, w <= W, ny * h >= H and nx * w >= W (fewer tiles cannot cover the image: a stride above the window),
+ *   T < 2^31, C <= 256 when a mask is asked for; any alignment of every buffer (16-byte stores where W % 4 == 0, resp. w % 4 == 0, and
+ *   the output's base is aligned).  Bad scalars and null pointers return EGM_ERR_ARG with a message before any launch.  Nothing waits
+ *   for the device; capturable on one stream. */
+int egm_tile_gather_f32(const float* src, int N, int C, int H, int W, const int* ys_dev, int ny, const int* xs_dev, int nx, int h, int w,
+                        int t0, int count, float* dst, egm_stream_t s);
+int egm_tile_blend_f32(const float* tiles, int N, int C, int H, int W, const int* ys_dev, int ny, const int* xs_dev, int nx, int h, int w,
+                       const float* wy_dev, const float* wx_dev, const unsigned char* lut, float* logits_out, unsigned char* mask_out,
+                       egm_stream_t s);
+
 /* ---- batched training data path: B ragged photos with masks -> the batch a train step reads (train.py:14-33, my_dataset.py:118-132)
  * egm_train_batch_u8: for every image b what egm_resample_u8 (axis 1, then axis 0), egm_gather_u8 and egm_augment_u8 compute one
  *   after the other, written into slot b of out_img_bchw fp32 [B][3][slot_h][slot_w] and out_target_bhw int64 [B][slot_h][slot_w]: per
