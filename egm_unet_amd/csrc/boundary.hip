@@ -18,14 +18,14 @@
 //           most 4 * kBoundaryRows pixels), one shuffle reduction per cell, one 64-bit atomic per wave and cell.
 // When 2 radius + 1 exceeds H or W nothing is eroded: the column pass then ignores the flags and walks its own rows only.
 // No workgroup waits for another and no loop depends on the data.
+// mask_scan.h holds what this file shares with contour.hip and surface.hip: the class tables, the column pass's tile and the host
+// checks.
 #include "common.h"
 #include "mask_scan.h"
 
 namespace {
 
 constexpr int kBoundaryRows = 128;             // column pass: image rows per wave (tests/test_gpu_boundary.py restates it)
-constexpr int kColLanePix = 4;                 //              columns per lane
-constexpr int kColWave = 64 * kColLanePix;     //              and per wave
 constexpr int kColUnroll = 8;                  //              rows loaded before any is used
 
 // One side of the row pass for a lane's 16 pixels [p0, p0 + 16): cls = their classes, prev_cls / carry_start = the class of pixel
@@ -103,13 +103,11 @@ __global__ __launch_bounds__(256) void boundary_cols_kernel(int H, int W, int pi
                                                             const unsigned char* __restrict__ flags, const unsigned char* __restrict__ member,
                                                             int nrc, int ncg, long long items, unsigned long long* __restrict__ counts,
                                                             unsigned char* __restrict__ band_pred, unsigned char* __restrict__ band_label) {
-    const int lane = threadIdx.x & 63;
     const long long item = blockIdx.x * 4LL + (threadIdx.x >> 6);
     if (item >= items) return;                                 // (a whole wave; the kernel has no barrier)
-    const int cg = (int)(item % ncg), rc = (int)((item / ncg) % nrc);
-    const long long n = item / ncg / nrc;
-    const int x0 = cg * kColWave + lane * kColLanePix;
-    const int y0 = rc * kBoundaryRows, yend = min(y0 + kBoundaryRows, H);
+    const ColTile tile(item, ncg, nrc, H, pitch, kBoundaryRows);  // (x0 may lie behind the pitch: load4_row and store4_row bound every access)
+    const long long n = tile.n;
+    const int x0 = tile.x0, y0 = tile.y0, yend = tile.yend;
     const int dv = dead ? 0 : radius, d2 = 2 * radius;         // (radius <= 2^29)
     const int rbeg = max(y0 - dv, 0), rend = yend + dv;        // flag rows walked; row r decides image row r - dv
     const unsigned char* fimg = flags + n * H * pitch;
@@ -165,44 +163,35 @@ __global__ __launch_bounds__(256) void boundary_cols_kernel(int H, int W, int pi
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const unsigned int v = wave_sum_u32(cnt[k][t]);    // at most 64 * 4 * kBoundaryRows
-            if (lane == 0 && v) atomicAdd(&counts[(n * C + k) * 3 + t], (unsigned long long)v);
+            if (tile.lane == 0 && v) atomicAdd(&counts[(n * C + k) * 3 + t], (unsigned long long)v);
         }
 }
 
 }  // namespace
 
 extern "C" long long egm_boundary_workspace(int N, int H, int W) {
-    EGM_REQUIRE(N > 0 && H > 0 && W > 0, "boundary_workspace: bad shape %d x %d x %d", N, H, W);
-    EGM_REQUIRE((long long)H * W <= kBoundaryMaxPix, "boundary_workspace: %d x %d pixels per image, at most 2^30 are supported", H, W);
+    if (mask_shape_check("boundary_workspace", N, H, W, 1) != EGM_OK) return EGM_ERR_ARG;      // (the planes do not depend on C)
     return 2LL * N * H * boundary_pitch(W) + 16;               // (two planes; +16: they start at the first 16-byte boundary)
 }
 
 extern "C" int egm_mask_boundary_u8(const unsigned char* pred, const unsigned char* label, int N, int H, int W, int radius,
                                     const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
                                     unsigned long long* counts, unsigned char* band_pred, unsigned char* band_label, egm_stream_t s) {
-    EGM_REQUIRE(pred && pred_cls && workspace, "mask_boundary_u8: null pointer");
+    MaskGrid g;
+    if (mask_check("mask_boundary_u8", pred, pred_cls, workspace, N, H, W, C, kBoundaryRows, g) != EGM_OK) return EGM_ERR_ARG;
     EGM_REQUIRE(label ? label_cls != nullptr : (!counts && !band_label),
                 "mask_boundary_u8: null pointer (a label needs its class table; without a label there are no counts and no label band)");
     EGM_REQUIRE(counts || band_pred || band_label, "mask_boundary_u8: null pointer (no output: counts, band_pred and band_label are all NULL)");
-    EGM_REQUIRE(C > 0 && C <= kBoundaryMaxC, "mask_boundary_u8: %d classes, between 1 and %d are supported", C, kBoundaryMaxC);
     EGM_REQUIRE(radius >= 1, "mask_boundary_u8: radius %d, at least 1 is required", radius);
-    EGM_REQUIRE(N > 0 && H > 0 && W > 0, "mask_boundary_u8: bad shape %d x %d x %d", N, H, W);
-    EGM_REQUIRE((long long)H * W <= kBoundaryMaxPix, "mask_boundary_u8: %d x %d pixels per image, at most 2^30 are supported", H, W);
-    const long long nrows = (long long)N * H;
-    EGM_REQUIRE(nrows <= (1ll << 31), "mask_boundary_u8: %d images of %d rows in one call, at most 2^31 rows are supported", N, H);
-    const int pitch = boundary_pitch(W);
     const int d = radius < (1 << 29) ? radius : (1 << 29);     // 2 d >= 2^30 >= H, W: as empty an erosion as any larger radius gives
     const int dead = (2LL * d + 1 > H || 2LL * d + 1 > W) ? 1 : 0;
-    unsigned char* flags = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
-    unsigned char* member = flags + nrows * pitch;
-    const int nrc = egm_cdiv(H, kBoundaryRows), ncg = egm_cdiv(W, kColWave);
-    const long long items = (long long)N * nrc * ncg;
-    EGM_REQUIRE(items <= (1ll << 32), "mask_boundary_u8: %lld tiles of %d x %d, at most 2^32 are supported", items, kBoundaryRows, kColWave);
-    hipLaunchKernelGGL(boundary_rows_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)s, pred, label, nrows, W, pitch, 2 * d,
-                       pred_cls, label_cls, C, flags, member);
+    unsigned char* flags = mask_align(workspace);
+    unsigned char* member = flags + g.nrows * g.pitch;
+    hipLaunchKernelGGL(boundary_rows_kernel, g.row_blocks(), dim3(256), 0, (hipStream_t)s, pred, label, g.nrows, W, g.pitch, 2 * d, pred_cls,
+                       label_cls, C, flags, member);
     EGM_CHECK_LAUNCH("mask_boundary_u8 (rows)");
-    hipLaunchKernelGGL(boundary_cols_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)s, H, W, pitch, d, dead, C, flags, member,
-                       nrc, ncg, items, counts, band_pred, band_label);
+    hipLaunchKernelGGL(boundary_cols_kernel, g.col_blocks(), dim3(256), 0, (hipStream_t)s, H, W, g.pitch, d, dead, C, flags, member, g.nrc, g.ncg,
+                       g.items, counts, band_pred, band_label);
     EGM_CHECK_LAUNCH("mask_boundary_u8 (columns)");
     return EGM_OK;
 }

@@ -128,6 +128,12 @@ __device__ __forceinline__ void store8_lds(bf16_t* p, const float (&v)[8]) {
     a.w = (uint32_t)f32_to_bf16(v[6]) | ((uint32_t)f32_to_bf16(v[7]) << 16);
     *reinterpret_cast<uint4*>(p) = a;
 }
+// 16 bytes from any address
+__device__ __forceinline__ uint4 load16_any(const unsigned char* p) {
+    uint4 v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
 __device__ __forceinline__ void zero8(float (&v)[8]) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = 0.f;
@@ -142,6 +148,21 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned int wave_max_u32(unsigned int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned int)__shfl_xor((int)v, o, 64));
     return v;
 }
 // Sum over a whole block (blockDim.x multiple of 64, <= 1024). `red` = 16 floats of LDS. Result valid in every thread.
@@ -190,6 +211,7 @@ __device__ __forceinline__ void egm_pix_nyx(long long p, int H, int W, int& n, i
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // dtype dispatch for host launchers: body sees `T`
 #define EGM_DISPATCH_DTYPE(dtype, ...) \

@@ -25,66 +25,17 @@
 //           Counts stay in 32-bit registers per lane (at most 4 * kContourRows pixels), one shuffle reduction per cell, one 64-bit
 //           atomic per wave and non-zero cell.
 // No workgroup waits for another; a wave never leaves its image: every row index is clamped to [0, H) of image n.
+// mask_scan.h holds what this file shares with boundary.hip and surface.hip: the packed cells and the two scans of the row passes, the
+// F row pass itself (contour_rows_kernel<8>; surface.hip runs it with 16-bit cells), the column passes' tile and the host checks.
 #include "common.h"
 #include "mask_scan.h"
 
 namespace {
 
 constexpr int kContourRows = 16;               // column passes: image rows per wave (tests/test_gpu_contour.py restates it)
-constexpr int kRowGroup = 4;                   //                rows of a tile decided by one walk: they share its loads
 constexpr int kContourMaxRadius = 254;         // a row distance fits a byte, 255 = none
 static_assert(kContourRows % kRowGroup == 0, "a tile is a whole number of row groups");
-constexpr int kColLanePix = 4;                 // column passes: columns per lane
-constexpr int kColWave = 64 * kColLanePix;     //                and per wave
 constexpr unsigned int kOutside = 256u;        // the class of a column outside the row: equal to no class, the dropped one included
-constexpr int kNoMarkLeft = -1024;             // "no marked pixel so far": farther than 255 from every column >= 0
-constexpr int kNoMarkRight = (1 << 30) + 4096; // the same to the right of every column of a padded row (W <= 2^30)
-
-// Distance from each of a lane's 16 pixels [p0, p0 + 16) to the nearest marked pixel at or left of it, plus `add`, capped at 255, as
-// 16 bytes.  marks: bit i = pixel p0 + i is marked.  carry = the last marked column of the chunks before, moved on.
-__device__ __forceinline__ void dist_left(unsigned int marks, int p0, int add, int& carry, unsigned int (&out)[4]) {
-    const int lane = threadIdx.x & 63;
-    int inc = marks ? p0 + 31 - __clz((int)marks) : kNoMarkLeft;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc = max(inc, t);
-    }
-    int cur = __shfl_up(inc, 1, 64);
-    if (lane == 0) cur = kNoMarkLeft;
-    cur = max(cur, carry);
-#pragma unroll
-    for (int i = 0; i < kRowLanePix; ++i) {
-        if ((marks >> i) & 1u) cur = p0 + i;
-        out[i >> 2] |= (unsigned int)min(p0 + i - cur + add, 255) << (8 * (i & 3));
-    }
-    carry = max(carry, __shfl(inc, 63, 64));
-}
-
-// The mirror image: nearest marked pixel at or right of each pixel; io holds dist_left's bytes and leaves the smaller of the two.
-// carry = the first marked column of the chunks to the right.
-__device__ __forceinline__ void dist_right_min(unsigned int marks, int p0, int add, int& carry, unsigned int (&io)[4]) {
-    const int lane = threadIdx.x & 63;
-    int inc = marks ? p0 + __ffs((int)marks) - 1 : kNoMarkRight;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_down(inc, o, 64);
-        if (lane + o < 64) inc = min(inc, t);
-    }
-    int cur = __shfl_down(inc, 1, 64);
-    if (lane == 63) cur = kNoMarkRight;
-    cur = min(cur, carry);
-    unsigned int res[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = kRowLanePix - 1; i >= 0; --i) {
-        if ((marks >> i) & 1u) cur = p0 + i;
-        const int left = (int)((io[i >> 2] >> (8 * (i & 3))) & 255u);
-        res[i >> 2] |= (unsigned int)min(min(cur - (p0 + i) + add, 255), left) << (8 * (i & 3));
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) io[j] = res[j];
-    carry = min(carry, __shfl(inc, 0, 64));
-}
 
 // a lane's 16 classes with kOutside behind the row's end
 __device__ __forceinline__ void row_classes_outside(const unsigned char* row, int p0, int W, const unsigned char* tab,
@@ -95,11 +46,6 @@ __device__ __forceinline__ void row_classes_outside(const unsigned char* row, in
         for (int i = 0; i < kRowLanePix; ++i)
             if (p0 + i >= W) cls[i] = kOutside;
     }
-}
-
-__device__ __forceinline__ uint4 load16(const unsigned char* p) { return *reinterpret_cast<const uint4*>(p); }
-__device__ __forceinline__ void store16(unsigned char* p, const unsigned int (&v)[4]) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(v[0], v[1], v[2], v[3]);
 }
 
 // ---- band, rows: cls[row][p] = pred class | label class << 4 (15 = none, 0xff behind W); gp / gl[row][p] = the distance to the nearest
@@ -123,24 +69,25 @@ __global__ __launch_bounds__(256) void contour_band_rows_kernel(const unsigned c
     int carry[2] = {kNoMarkLeft, kNoMarkLeft};
     for (int base = 0; base < pitch; base += kRowChunk) {      // left to right: run starts
         const int p0 = base + lane * kRowLanePix;
-        unsigned int c[2][kRowLanePix], both[4] = {0u, 0u, 0u, 0u};
+        unsigned int c[2][kRowLanePix];
+        Cells<8> both;
         row_classes_outside(prow, p0, W, pt, c[0]);
         row_classes_outside(lrow, p0, W, lt, c[1]);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            unsigned int q = __shfl_up(c[s][kRowLanePix - 1], 1, 64), marks = 0u, g[4] = {0u, 0u, 0u, 0u};
+            unsigned int q = __shfl_up(c[s][kRowLanePix - 1], 1, 64), marks = 0u;
             if (lane == 0) q = edge_cls[s];
 #pragma unroll
             for (int i = 0; i < kRowLanePix; ++i) {
                 marks |= (c[s][i] != q ? 1u : 0u) << i;
                 q = c[s][i];
-                both[i >> 2] |= (c[s][i] < (unsigned)kBoundaryMaxC ? c[s][i] : 15u) << (8 * (i & 3) + 4 * s);
+                both.put(i, (c[s][i] < (unsigned)kBoundaryMaxC ? c[s][i] : 15u) << (4 * s));
             }
-            dist_left(marks, p0, 1, carry[s], g);
+            const Cells<8> g = dist_left<8>(marks, p0, 1, carry[s]);
             edge_cls[s] = __shfl(c[s][kRowLanePix - 1], 63, 64);
-            if (p0 < pitch) store16(grow[s] + p0, g);
+            if (p0 < pitch) g.store(grow[s] + p0);
         }
-        if (p0 < pitch) store16(crow + p0, both);
+        if (p0 < pitch) both.store(crow + p0);
     }
     edge_cls[0] = edge_cls[1] = kOutside;
     carry[0] = carry[1] = kNoMarkRight;
@@ -151,20 +98,18 @@ __global__ __launch_bounds__(256) void contour_band_rows_kernel(const unsigned c
         row_classes_outside(lrow, p0, W, lt, c[1]);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            unsigned int q = __shfl_down(c[s][0], 1, 64), marks = 0u, g[4] = {0u, 0u, 0u, 0u};
+            unsigned int q = __shfl_down(c[s][0], 1, 64), marks = 0u;
             if (lane == 63) q = edge_cls[s];
 #pragma unroll
             for (int i = kRowLanePix - 1; i >= 0; --i) {
                 marks |= (c[s][i] != q ? 1u : 0u) << i;
                 q = c[s][i];
             }
-            if (p0 < pitch) {
-                const uint4 v = load16(grow[s] + p0);
-                g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
-            }
+            Cells<8> g;
+            if (p0 < pitch) g.load(grow[s] + p0);
             dist_right_min(marks, p0, 1, carry[s], g);
             edge_cls[s] = __shfl(c[s][0], 0, 64);
-            if (p0 < pitch) store16(grow[s] + p0, g);
+            if (p0 < pitch) g.store(grow[s] + p0);
         }
     }
 }
@@ -201,16 +146,12 @@ __global__ __launch_bounds__(256) void contour_band_cols_kernel(int H, int W, in
                                                                 unsigned char* __restrict__ band_label) {
     __shared__ unsigned int kw[256 + kRowGroup];
     disc_table(kw, radius);
-    const int lane = threadIdx.x & 63;
     const long long item = blockIdx.x * 4LL + (threadIdx.x >> 6);
     if (item >= items) return;                                 // (a whole wave, behind the only barrier)
-    const int cg = (int)(item % ncg), rc = (int)((item / ncg) % nrc);
-    const long long n = item / ncg / nrc;
-    const int x0 = cg * kColWave + lane * kColLanePix;
-    const bool live = x0 < pitch;                              // (pitch is a multiple of 16: a word is inside or outside as a whole)
-    const int xl = live ? x0 : 0;
-    const int y0 = rc * kContourRows, yend = min(y0 + kContourRows, H);
-    const long long img = n * H * pitch + xl;
+    const ColTile tile(item, ncg, nrc, H, pitch, kContourRows);
+    const long long n = tile.n, img = tile.img;
+    const int x0 = tile.x0, y0 = tile.y0, yend = tile.yend;
+    const bool live = tile.live;
     unsigned int cnt[kBoundaryMaxC][3];
 #pragma unroll
     for (int k = 0; k < kBoundaryMaxC; ++k) cnt[k][0] = cnt[k][1] = cnt[k][2] = 0u;
@@ -270,93 +211,11 @@ __global__ __launch_bounds__(256) void contour_band_cols_kernel(int H, int W, in
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const unsigned int v = wave_sum_u32(cnt[k][t]);    // at most 64 * 4 * kContourRows
-            if (lane == 0 && v) atomicAdd(&counts[(n * C + k) * 3 + t], (unsigned long long)v);
+            if (tile.lane == 0 && v) atomicAdd(&counts[(n * C + k) * 3 + t], (unsigned long long)v);
         }
 }
 
-// ---- F, rows: contour[row][p] = bit k: p is a contour pixel of pred class k, bit 4 + k: of label class k (0 behind W);
-// g[s * C + k][row][p] = the distance to the nearest contour pixel of side s and class k in the row, 255 = none within 254
-__global__ __launch_bounds__(256) void contour_f_rows_kernel(const unsigned char* __restrict__ pred, const unsigned char* __restrict__ label,
-                                                             long long nrows, int H, int W, int pitch,
-                                                             const unsigned char* __restrict__ pred_cls,
-                                                             const unsigned char* __restrict__ label_cls, int C, int want_g,
-                                                             unsigned char* __restrict__ contour, unsigned char* __restrict__ g_planes) {
-    __shared__ unsigned char pt[256], lt[256];
-    boundary_tables(pt, lt, pred_cls, label_cls, C);
-    const int lane = threadIdx.x & 63;
-    const long long row = blockIdx.x * 4LL + (threadIdx.x >> 6);
-    if (row >= nrows) return;                                  // (a whole wave, behind the only barrier)
-    const int y = (int)(row % H);
-    const bool has_up = y > 0, has_dn = y + 1 < H;             // the neighbours above and below, inside this image only
-    const unsigned char* rows[2] = {pred + row * W, label ? label + row * W : nullptr};
-    const unsigned char* tabs[2] = {pt, lt};
-    unsigned char* krow = contour + row * pitch;
-    const long long plane = nrows * pitch;
-    unsigned char* grow = g_planes + row * pitch;
-    unsigned int left_cls[2] = {kOutside, kOutside};
-    int carry[2 * kBoundaryMaxC];
-#pragma unroll
-    for (int t = 0; t < 2 * kBoundaryMaxC; ++t) carry[t] = kNoMarkLeft;
-    for (int base = 0; base < pitch; base += kRowChunk) {      // left to right
-        const int p0 = base + lane * kRowLanePix;
-        unsigned int kbits[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            unsigned int c[kRowLanePix], up[kRowLanePix], dn[kRowLanePix];
-            row_classes(rows[s], p0, W, tabs[s], c);
-            row_classes(rows[s] && has_up ? rows[s] - W : nullptr, p0, W, tabs[s], up);
-            row_classes(rows[s] && has_dn ? rows[s] + W : nullptr, p0, W, tabs[s], dn);
-            unsigned int before = __shfl_up(c[kRowLanePix - 1], 1, 64), after = __shfl_down(c[0], 1, 64);
-            if (lane == 0) before = left_cls[s];
-            if (lane == 63) after = (rows[s] && p0 + kRowLanePix < W) ? (unsigned int)tabs[s][rows[s][p0 + kRowLanePix]] : kNoClass;
-            left_cls[s] = __shfl(c[kRowLanePix - 1], 63, 64);
-#pragma unroll
-            for (int i = 0; i < kRowLanePix; ++i) {
-                const int p = p0 + i;
-                const unsigned int me = c[i], l = i ? c[i - 1] : before, r = i + 1 < kRowLanePix ? c[i + 1] : after;
-                const bool edge = (p > 0 && l != me) || (p + 1 < W && r != me) || (has_up && up[i] != me) || (has_dn && dn[i] != me);
-                if (me < (unsigned)kBoundaryMaxC && edge) kbits[i >> 2] |= (1u << me) << (8 * (i & 3) + 4 * s);
-            }
-        }
-        if (p0 < pitch) store16(krow + p0, kbits);
-        if (!want_g) continue;
-#pragma unroll
-        for (int t = 0; t < 2 * kBoundaryMaxC; ++t) {          // bit t of the contour byte: side t / 4, class t % 4 -> plane side * C + class
-            if ((t & 3) >= C) continue;
-            unsigned int marks = 0u, g[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int i = 0; i < kRowLanePix; ++i) marks |= ((kbits[i >> 2] >> (8 * (i & 3) + t)) & 1u) << i;
-            dist_left(marks, p0, 0, carry[t], g);
-            if (p0 < pitch) store16(grow + ((t >> 2) * C + (t & 3)) * plane + p0, g);
-        }
-    }
-    if (!want_g) return;
-#pragma unroll
-    for (int t = 0; t < 2 * kBoundaryMaxC; ++t) carry[t] = kNoMarkRight;
-    for (int base = ((pitch - 1) / kRowChunk) * kRowChunk; base >= 0; base -= kRowChunk) {     // right to left
-        const int p0 = base + lane * kRowLanePix;
-        unsigned int kbits[4] = {0u, 0u, 0u, 0u};
-        if (p0 < pitch) {
-            const uint4 v = load16(krow + p0);
-            kbits[0] = v.x; kbits[1] = v.y; kbits[2] = v.z; kbits[3] = v.w;
-        }
-#pragma unroll
-        for (int t = 0; t < 2 * kBoundaryMaxC; ++t) {
-            if ((t & 3) >= C) continue;
-            unsigned char* gt = grow + ((t >> 2) * C + (t & 3)) * plane + p0;
-            unsigned int marks = 0u, g[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int i = 0; i < kRowLanePix; ++i) marks |= ((kbits[i >> 2] >> (8 * (i & 3) + t)) & 1u) << i;
-            if (p0 < pitch) {
-                const uint4 v = load16(gt);
-                g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
-            }
-            dist_right_min(marks, p0, 0, carry[t], g);
-            if (p0 < pitch) store16(gt, g);
-        }
-    }
-}
-
+// ---- F, rows: contour_rows_kernel<8> of mask_scan.h (255 = no contour pixel of the side and class within 254 columns)
 // ---- F, columns: per contour pixel of side s and class k, is a contour pixel of the OTHER side's class k within the tolerance?
 __global__ __launch_bounds__(256) void contour_f_cols_kernel(int H, int W, int pitch, int radius, int C, const unsigned char* __restrict__ contour,
                                                              const unsigned char* __restrict__ g_planes, long long plane, int nrc, int ncg,
@@ -364,16 +223,12 @@ __global__ __launch_bounds__(256) void contour_f_cols_kernel(int H, int W, int p
                                                              unsigned char* __restrict__ contour_pred, unsigned char* __restrict__ contour_label) {
     __shared__ unsigned int kw[256 + kRowGroup];
     disc_table(kw, radius);
-    const int lane = threadIdx.x & 63;
     const long long item = blockIdx.x * 4LL + (threadIdx.x >> 6);
     if (item >= items) return;                                 // (a whole wave, behind the only barrier)
-    const int cg = (int)(item % ncg), rc = (int)((item / ncg) % nrc);
-    const long long n = item / ncg / nrc;
-    const int x0 = cg * kColWave + lane * kColLanePix;
-    const bool live = x0 < pitch;
-    const int xl = live ? x0 : 0;
-    const int y0 = rc * kContourRows, yend = min(y0 + kContourRows, H);
-    const long long img = n * H * pitch + xl;
+    const ColTile tile(item, ncg, nrc, H, pitch, kContourRows);
+    const long long n = tile.n, img = tile.img;
+    const int x0 = tile.x0, y0 = tile.y0, yend = tile.yend;
+    const bool live = tile.live;
     unsigned int cnt[kBoundaryMaxC][4];
 #pragma unroll
     for (int k = 0; k < kBoundaryMaxC; ++k) cnt[k][0] = cnt[k][1] = cnt[k][2] = cnt[k][3] = 0u;
@@ -424,61 +279,46 @@ __global__ __launch_bounds__(256) void contour_f_cols_kernel(int H, int W, int p
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const unsigned int v = wave_sum_u32(cnt[k][t]);    // at most 64 * 4 * kContourRows
-            if (lane == 0 && v) atomicAdd(&counts[(n * C + k) * 4 + t], (unsigned long long)v);
+            if (tile.lane == 0 && v) atomicAdd(&counts[(n * C + k) * 4 + t], (unsigned long long)v);
         }
 }
 
 inline int contour_planes(int C) { return 2 * C + 1 > 3 ? 2 * C + 1 : 3; }      // F: contour + a g plane per side and class; band: 3
 
-// the checks both entry points share; -> EGM_OK or EGM_ERR_ARG with the message set
-int contour_check(const char* name, const void* pred, const void* label, int N, int H, int W, int radius, const void* pred_cls,
-                  const void* label_cls, int C, const void* workspace, const void* counts, const void* out_pred, const void* out_label,
-                  const char* what) {
-    EGM_REQUIRE(pred && pred_cls && workspace, "%s: null pointer", name);
+// mask_check, then the rules of this file's two entry points: one-sided calls and the radius; -> EGM_OK or EGM_ERR_ARG with the message set
+int contour_args(const char* name, const void* pred, const void* label, int N, int H, int W, int radius, const void* pred_cls,
+                 const void* label_cls, int C, const void* workspace, const void* counts, const void* out_pred, const void* out_label,
+                 const char* what, MaskGrid& g) {
+    if (mask_check(name, pred, pred_cls, workspace, N, H, W, C, kContourRows, g) != EGM_OK) return EGM_ERR_ARG;
     EGM_REQUIRE(label ? label_cls != nullptr : (!counts && !out_label),
                 "%s: null pointer (a label needs its class table; without a label there are no counts and no label %s)", name, what);
     EGM_REQUIRE(counts || out_pred || out_label, "%s: null pointer (no output: counts and both %s outputs are NULL)", name, what);
-    EGM_REQUIRE(C > 0 && C <= kBoundaryMaxC, "%s: %d classes, between 1 and %d are supported", name, C, kBoundaryMaxC);
     EGM_REQUIRE(radius >= 1 && radius <= kContourMaxRadius, "%s: radius %d, between 1 and %d are supported", name, radius, kContourMaxRadius);
-    EGM_REQUIRE(N > 0 && H > 0 && W > 0, "%s: bad shape %d x %d x %d", name, N, H, W);
-    EGM_REQUIRE((long long)H * W <= kBoundaryMaxPix, "%s: %d x %d pixels per image, at most 2^30 are supported", name, H, W);
-    EGM_REQUIRE((long long)N * H <= (1ll << 31), "%s: %d images of %d rows in one call, at most 2^31 rows are supported", name, N, H);
-    const long long items = (long long)N * egm_cdiv(H, kContourRows) * egm_cdiv(W, kColWave);
-    EGM_REQUIRE(items <= (1ll << 32), "%s: %lld tiles of %d x %d, at most 2^32 are supported", name, items, kContourRows, kColWave);
     return EGM_OK;
-}
-
-inline unsigned char* contour_align(void* workspace) {
-    return reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
 }
 
 }  // namespace
 
 extern "C" long long egm_contour_workspace(int N, int H, int W, int C) {
-    EGM_REQUIRE(N > 0 && H > 0 && W > 0, "contour_workspace: bad shape %d x %d x %d", N, H, W);
-    EGM_REQUIRE(C > 0 && C <= kBoundaryMaxC, "contour_workspace: %d classes, between 1 and %d are supported", C, kBoundaryMaxC);
-    EGM_REQUIRE((long long)H * W <= kBoundaryMaxPix, "contour_workspace: %d x %d pixels per image, at most 2^30 are supported", H, W);
+    if (mask_shape_check("contour_workspace", N, H, W, C) != EGM_OK) return EGM_ERR_ARG;
     return (long long)contour_planes(C) * N * H * boundary_pitch(W) + 16;      // (+16: the planes start at the first 16-byte boundary)
 }
 
 extern "C" int egm_mask_boundary_euclid_u8(const unsigned char* pred, const unsigned char* label, int N, int H, int W, int radius,
                                            const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
                                            unsigned long long* counts, unsigned char* band_pred, unsigned char* band_label, egm_stream_t s) {
-    const int rc = contour_check("mask_boundary_euclid_u8", pred, label, N, H, W, radius, pred_cls, label_cls, C, workspace, counts, band_pred,
-                                 band_label, "band");
+    MaskGrid g;
+    const int rc = contour_args("mask_boundary_euclid_u8", pred, label, N, H, W, radius, pred_cls, label_cls, C, workspace, counts, band_pred,
+                                band_label, "band", g);
     if (rc != EGM_OK) return rc;
-    const long long nrows = (long long)N * H;
-    const int pitch = boundary_pitch(W);
-    unsigned char* cls_plane = contour_align(workspace);
-    unsigned char* gp_plane = cls_plane + nrows * pitch;
-    unsigned char* gl_plane = gp_plane + nrows * pitch;
-    const int nrc = egm_cdiv(H, kContourRows), ncg = egm_cdiv(W, kColWave);
-    const long long items = (long long)N * nrc * ncg;
-    hipLaunchKernelGGL(contour_band_rows_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)s, pred, label, nrows, W, pitch,
-                       pred_cls, label_cls, C, cls_plane, gp_plane, gl_plane);
+    unsigned char* cls_plane = mask_align(workspace);
+    unsigned char* gp_plane = cls_plane + g.nrows * g.pitch;
+    unsigned char* gl_plane = gp_plane + g.nrows * g.pitch;
+    hipLaunchKernelGGL(contour_band_rows_kernel, g.row_blocks(), dim3(256), 0, (hipStream_t)s, pred, label, g.nrows, W, g.pitch, pred_cls,
+                       label_cls, C, cls_plane, gp_plane, gl_plane);
     EGM_CHECK_LAUNCH("mask_boundary_euclid_u8 (rows)");
-    hipLaunchKernelGGL(contour_band_cols_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)s, H, W, pitch, radius, C, cls_plane,
-                       gp_plane, gl_plane, nrc, ncg, items, counts, band_pred, band_label);
+    hipLaunchKernelGGL(contour_band_cols_kernel, g.col_blocks(), dim3(256), 0, (hipStream_t)s, H, W, g.pitch, radius, C, cls_plane, gp_plane,
+                       gl_plane, g.nrc, g.ncg, g.items, counts, band_pred, band_label);
     EGM_CHECK_LAUNCH("mask_boundary_euclid_u8 (columns)");
     return EGM_OK;
 }
@@ -486,21 +326,18 @@ extern "C" int egm_mask_boundary_euclid_u8(const unsigned char* pred, const unsi
 extern "C" int egm_mask_contour_f_u8(const unsigned char* pred, const unsigned char* label, int N, int H, int W, int radius,
                                      const unsigned char* pred_cls, const unsigned char* label_cls, int C, void* workspace,
                                      unsigned long long* counts, unsigned char* contour_pred, unsigned char* contour_label, egm_stream_t s) {
-    const int rc = contour_check("mask_contour_f_u8", pred, label, N, H, W, radius, pred_cls, label_cls, C, workspace, counts, contour_pred,
-                                 contour_label, "contour");
+    MaskGrid g;
+    const int rc = contour_args("mask_contour_f_u8", pred, label, N, H, W, radius, pred_cls, label_cls, C, workspace, counts, contour_pred,
+                                contour_label, "contour", g);
     if (rc != EGM_OK) return rc;
-    const long long nrows = (long long)N * H;
-    const int pitch = boundary_pitch(W);
-    const long long plane = nrows * pitch;
-    unsigned char* contour = contour_align(workspace);
+    const long long plane = g.nrows * g.pitch;
+    unsigned char* contour = mask_align(workspace);
     unsigned char* g_planes = contour + plane;
-    const int nrc = egm_cdiv(H, kContourRows), ncg = egm_cdiv(W, kColWave);
-    const long long items = (long long)N * nrc * ncg;
-    hipLaunchKernelGGL(contour_f_rows_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)s, pred, label, nrows, H, W, pitch,
-                       pred_cls, label_cls, C, counts ? 1 : 0, contour, g_planes);
+    hipLaunchKernelGGL(contour_rows_kernel<8>, g.row_blocks(), dim3(256), 0, (hipStream_t)s, pred, label, g.nrows, H, W, g.pitch, pred_cls,
+                       label_cls, C, counts ? 1 : 0, contour, g_planes);
     EGM_CHECK_LAUNCH("mask_contour_f_u8 (rows)");
-    hipLaunchKernelGGL(contour_f_cols_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)s, H, W, pitch, radius, C, contour,
-                       g_planes, plane, nrc, ncg, items, counts, contour_pred, contour_label);
+    hipLaunchKernelGGL(contour_f_cols_kernel, g.col_blocks(), dim3(256), 0, (hipStream_t)s, H, W, g.pitch, radius, C, contour, g_planes, plane,
+                       g.nrc, g.ncg, g.items, counts, contour_pred, contour_label);
     EGM_CHECK_LAUNCH("mask_contour_f_u8 (columns)");
     return EGM_OK;
 }

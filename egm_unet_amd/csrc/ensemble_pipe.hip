@@ -29,7 +29,6 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(256) void clip_hfilter_u8_kernel(const unsigned char* __restrict__ img, int H, int W, float* __restrict__ tmp, int Sw,
                                                               const int* __restrict__ bounds, const float* __restrict__ wts, int ksize,

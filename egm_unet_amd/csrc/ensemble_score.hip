@@ -20,17 +20,6 @@ constexpr int kScoreMaxAlphas = 128;
 constexpr int kConfMaxGrid = 2048;             // 8 workgroups of 256 per CU
 constexpr int kConfUnroll = 4;                 // 16-byte chunk pairs in flight per lane
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned int lo = __shfl_xor((unsigned int)v, o, 64), hi = __shfl_xor((unsigned int)(v >> 32), o, 64);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
 // Byte -> cell tables in LDS: lt[b] = label class * C, pt[b] = predicted class, 16 for a dropped byte; a pixel's cell is
 // min(lt[l] + pt[p], 16), and cell 16 is a counter row nobody reads, so a dropped pixel needs no branch.  Every lane owns one 32-bit
 // counter per cell, cnt[cell][lane] (lanes of a wave on different banks: an LDS add without conflicts and without a returned value).
@@ -50,15 +39,10 @@ __device__ __forceinline__ void conf_count16(ConfLds& L, const uint4& p, const u
 #pragma unroll
         for (int b = 0; b < 4; ++b) conf_count(L, (pw[w] >> (b * 8)) & 255u, (lw[w] >> (b * 8)) & 255u);
 }
-// 16 bytes from any address (the label's alignment is whatever it is once the chunks are cut at the prediction's 16-byte boundaries)
-__device__ __forceinline__ uint4 load16_any(const unsigned char* p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
 
 // Pixels [0, head) in front of the prediction's first 16-byte boundary and the tail behind the last whole chunk go byte by byte
-// (workgroup 0); the body is nchunks chunks of 16 pixels, grid-strided, kConfUnroll chunk pairs loaded before any is counted.
+// (workgroup 0); the body is nchunks chunks of 16 pixels, grid-strided, kConfUnroll chunk pairs loaded before any is counted.  The
+// label's alignment is whatever it is once the chunks are cut at the prediction's 16-byte boundaries: load16_any.
 __global__ __launch_bounds__(256) void mask_confusion_u8_kernel(const unsigned char* __restrict__ pred, const unsigned char* __restrict__ label,
                                                                 long long npix, const unsigned char* __restrict__ pred_cls,
                                                                 const unsigned char* __restrict__ label_cls, int C,

@@ -26,8 +26,6 @@ __device__ __forceinline__ int clip8(int v) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // ws[ws_off + (r * nc + xi) * 3 + c] = clip8(2^21 + sum_j img[r0 + r][x0 + j][c] * coefs[xi][j]), (x0, n) = bounds[xi], xi = xx - c0
 __global__ __launch_bounds__(256) void train_hpass_kernel(const egm_train_desc* __restrict__ tab, unsigned char* __restrict__ ws) {
     const egm_train_desc d = tab[blockIdx.y];

@@ -236,8 +236,7 @@ def boundary_radius(H, W, boundary):
 
 
 _BOUNDARY_WORKSPACES = 4                    # shapes whose workspace is kept (3000 x 4000 at N = 8 is 192 MB)
-_boundary_workspace_cache = collections.OrderedDict()
-_contour_workspace_cache = collections.OrderedDict()
+_workspace_caches = {kind: collections.OrderedDict() for kind in ("boundary", "contour", "surface")}     # sized by egm_<kind>_workspace
 _CONTOUR_MAX_RADIUS = 254                   # kContourMaxRadius of csrc/contour.hip: a row distance is kept in a byte, 255 = none
 _BOUNDARY_METRICS = ("box", "euclid")
 
@@ -254,10 +253,12 @@ def contour_workspace(N, H, W, num_classes, device):
     return torch.empty(lib().query("egm_contour_workspace", int(N), int(H), int(W), int(num_classes)), dtype=torch.uint8, device=device)
 
 
-def _cached_workspace(cache, query, shape, device, workspace):
-    """The caller's workspace, checked, or the module's for this shape: the last _BOUNDARY_WORKSPACES shapes used are kept per cache
+def _cached_workspace(kind, shape, device, workspace):
+    """The caller's workspace, checked, or the module's for this shape: the last _BOUNDARY_WORKSPACES shapes used are kept per kind
     (least recently used dropped first), so evaluate()'s loop allocates nothing while a few sizes repeat and memory stays bounded when
-    the sizes never do.  query: the entry point that gives the size in bytes for `shape`."""
+    the sizes never do.  kind: "boundary" with shape (N, H, W), "contour" or "surface" with (N, H, W, C); egm_<kind>_workspace gives
+    the size in bytes."""
+    cache, query = _workspace_caches[kind], f"egm_{kind}_workspace"
     if workspace is not None:
         need = lib().query(query, *shape)
         if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == device and workspace.dtype == torch.uint8
@@ -274,12 +275,14 @@ def _cached_workspace(cache, query, shape, device, workspace):
     return ws
 
 
-def _boundary_workspace(N, H, W, device, workspace):
-    return _cached_workspace(_boundary_workspace_cache, "egm_boundary_workspace", (N, H, W), device, workspace)
-
-
-def _contour_workspace(N, H, W, C, device, workspace):
-    return _cached_workspace(_contour_workspace_cache, "egm_contour_workspace", (N, H, W, C), device, workspace)
+def _counts_out(name, out, shape, device):
+    """The counts tensor of a score call: fresh zeros, or the caller's `out` to accumulate into, checked."""
+    if out is None:
+        return torch.zeros(shape, dtype=torch.int64, device=device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == tuple(shape)
+            and out.is_contiguous()):
+        raise ValueError(f"{name}: out must be a contiguous int64 CUDA tensor {list(shape)}")
+    return out
 
 
 def _boundary_metric(metric):
@@ -332,12 +335,8 @@ def boundary_counts_u8(pred_u8, label_u8, boundary=0.02, num_classes=2, pred_val
     N, H, W = p.shape
     d, C, dev = (contour_radius if euclid else boundary_radius)(H, W, boundary), int(num_classes), p.device
     pt, lt = _class_table_dev(pred_values, C, dev), _class_table_dev(label_values, C, dev)
-    if out is None:
-        out = torch.zeros((N, C, 3), dtype=torch.int64, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (N, C, 3)
-              and out.is_contiguous()):
-        raise ValueError(f"boundary_counts_u8: out must be a contiguous int64 CUDA tensor [{N}, {C}, 3]")
-    ws = _contour_workspace(N, H, W, C, dev, workspace) if euclid else _boundary_workspace(N, H, W, dev, workspace)
+    out = _counts_out("boundary_counts_u8", out, (N, C, 3), dev)
+    ws = _cached_workspace(*(("contour", (N, H, W, C)) if euclid else ("boundary", (N, H, W))), dev, workspace)
     lib().call("egm_mask_boundary_euclid_u8" if euclid else "egm_mask_boundary_u8", ptr(p), ptr(t), N, H, W, d, ptr(pt), ptr(lt), C, ptr(ws),
                ptr(out), None, None, stream())
     return out
@@ -353,7 +352,7 @@ def boundary_band_u8(mask_u8, boundary=0.02, num_classes=2, values=None, workspa
     N, H, W = m.shape
     d, C = (contour_radius if euclid else boundary_radius)(H, W, boundary), int(num_classes)
     band = torch.empty_like(m)
-    ws = _contour_workspace(N, H, W, C, m.device, workspace) if euclid else _boundary_workspace(N, H, W, m.device, workspace)
+    ws = _cached_workspace(*(("contour", (N, H, W, C)) if euclid else ("boundary", (N, H, W))), m.device, workspace)
     lib().call("egm_mask_boundary_euclid_u8" if euclid else "egm_mask_boundary_u8", ptr(m), None, N, H, W, d,
                ptr(_class_table_dev(values, C, m.device)), None, C, ptr(ws), None, ptr(band), None, stream())
     return band.reshape(mask_u8.shape)
@@ -391,7 +390,7 @@ def contour_u8(mask_u8, num_classes=2, values=None, workspace=None):
     C = int(num_classes)
     out = torch.empty_like(m)
     lib().call("egm_mask_contour_f_u8", ptr(m), None, N, H, W, 1, ptr(_class_table_dev(values, C, m.device)), None, C,
-               ptr(_contour_workspace(N, H, W, C, m.device, workspace)), None, ptr(out), None, stream())
+               ptr(_cached_workspace("contour", (N, H, W, C), m.device, workspace)), None, ptr(out), None, stream())
     return out.reshape(mask_u8.shape)
 
 
@@ -411,13 +410,9 @@ def contour_f_counts_u8(pred_u8, label_u8, tolerance=0.008, num_classes=2, pred_
     N, H, W = p.shape
     theta, C, dev = contour_radius(H, W, tolerance, "contour_f"), int(num_classes), p.device
     pt, lt = _class_table_dev(pred_values, C, dev), _class_table_dev(label_values, C, dev)
-    if out is None:
-        out = torch.zeros((N, C, 4), dtype=torch.int64, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (N, C, 4)
-              and out.is_contiguous()):
-        raise ValueError(f"contour_f_counts_u8: out must be a contiguous int64 CUDA tensor [{N}, {C}, 4]")
-    lib().call("egm_mask_contour_f_u8", ptr(p), ptr(t), N, H, W, theta, ptr(pt), ptr(lt), C, ptr(_contour_workspace(N, H, W, C, dev, workspace)),
-               ptr(out), None, None, stream())
+    out = _counts_out("contour_f_counts_u8", out, (N, C, 4), dev)
+    lib().call("egm_mask_contour_f_u8", ptr(p), ptr(t), N, H, W, theta, ptr(pt), ptr(lt), C,
+               ptr(_cached_workspace("contour", (N, H, W, C), dev, workspace)), ptr(out), None, None, stream())
     return out
 
 
@@ -450,7 +445,6 @@ SURFACE_BINS = 256                          # bins of ceil(d) in pixels, the las
 SURFACE_FIELDS = 4 + SURFACE_BINS           # n, sum of floor(256 d), sum of d^2, max d^2, then the bins (csrc/surface.hip)
 _SURFACE_MAX_SIDE = 32767                   # kSurfaceMaxSide: d^2 < 2^31 and a row distance fits 16 bits
 _SURFACE_MAX_TOLERANCE = SURFACE_BINS - 2   # the last bin is open-ended: a cumulative count is exact up to 254
-_surface_workspace_cache = collections.OrderedDict()
 
 
 def surface_workspace(N, H, W, num_classes, device):
@@ -459,8 +453,9 @@ def surface_workspace(N, H, W, num_classes, device):
     return torch.empty(lib().query("egm_surface_workspace", int(N), int(H), int(W), int(num_classes)), dtype=torch.uint8, device=device)
 
 
-def _surface_call(name, pred_u8, label_u8, num_classes, pred_values, label_values, workspace, counts, want_maps):
-    """The checks and the one call that surface_counts_u8 and surface_dist2_u8 share -> (counts, d2_pred, d2_label)."""
+def _surface_call(name, pred_u8, label_u8, num_classes, pred_values, label_values, workspace, out, want_maps):
+    """The checks and the one call that surface_counts_u8 and surface_dist2_u8 share -> (counts, d2_pred, d2_label): the counts (into
+    `out`, if given) or, with want_maps, the two d2 maps."""
     require_gpu()
     p, t = _boundary_images(name, [("pred", pred_u8), ("label", label_u8)])
     N, H, W = p.shape
@@ -468,13 +463,9 @@ def _surface_call(name, pred_u8, label_u8, num_classes, pred_values, label_value
         raise ValueError(f"{name}: {H} x {W} pixels, at most {_SURFACE_MAX_SIDE} rows and columns are supported")
     C, dev = int(num_classes), p.device
     pt, lt = _class_table_dev(pred_values, C, dev), _class_table_dev(label_values, C, dev)
-    if counts is True:
-        counts = torch.zeros((N, C, 2, SURFACE_FIELDS), dtype=torch.int64, device=dev)
-    elif counts is not None and not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int64
-                                     and tuple(counts.shape) == (N, C, 2, SURFACE_FIELDS) and counts.is_contiguous()):
-        raise ValueError(f"{name}: out must be a contiguous int64 CUDA tensor [{N}, {C}, 2, {SURFACE_FIELDS}]")
+    counts = None if want_maps else _counts_out(name, out, (N, C, 2, SURFACE_FIELDS), dev)
     maps = [torch.empty((N, H, W), dtype=torch.int32, device=dev) for _ in range(2)] if want_maps else [None, None]
-    ws = _cached_workspace(_surface_workspace_cache, "egm_surface_workspace", (N, H, W, C), dev, workspace)
+    ws = _cached_workspace("surface", (N, H, W, C), dev, workspace)
     lib().call("egm_mask_surface_dist_u8", ptr(p), ptr(t), N, H, W, ptr(pt), ptr(lt), C, ptr(ws), ptr(counts), ptr(maps[0]), ptr(maps[1]),
                stream())
     return counts, maps[0], maps[1]
@@ -492,8 +483,7 @@ def surface_counts_u8(pred_u8, label_u8, num_classes=2, pred_values=None, label_
     returned): sums add, field 3 is combined with max.  workspace: a surface_workspace(N, H, W, num_classes, device), see
     boundary_counts_u8.  H and W are at most 32767 (ValueError above).  Two launches, no host wait.  surface_report turns the counts
     into the scores."""
-    return _surface_call("surface_counts_u8", pred_u8, label_u8, num_classes, pred_values, label_values, workspace,
-                         True if out is None else out, False)[0]
+    return _surface_call("surface_counts_u8", pred_u8, label_u8, num_classes, pred_values, label_values, workspace, out, False)[0]
 
 
 def surface_dist2_u8(pred_u8, label_u8, num_classes=2, pred_values=None, label_values=None, workspace=None):

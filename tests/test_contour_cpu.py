@@ -100,6 +100,36 @@ def shifted_pair(H=60, W=90, shift=3, seed=17):
     return pred, label
 
 
+def far_pairs():
+    """Pairs whose class-1 contours are more than 254 pixels apart: along a column, along a row and along a diagonal."""
+    a, b = np.zeros((300, 40), dtype=np.uint8), np.zeros((300, 40), dtype=np.uint8)
+    a[2, 5:30] = 255                                                           # ... rows 2 and 290: the walk spans many tiles
+    b[290, 12:20] = 255
+    c, d = np.zeros((5, 1300), dtype=np.uint8), np.zeros((5, 1300), dtype=np.uint8)
+    c[1:4, 3] = 255                                                            # columns 3 and 1290: past a byte and across a 1024 chunk's carry
+    d[2, 1290] = 255
+    e, f = np.zeros((70, 1300), dtype=np.uint8), np.zeros((70, 1300), dtype=np.uint8)
+    e[3:9, 4:12] = 255                                                         # far apart along a diagonal
+    f[60:66, 1270:1290] = 255
+    return {"300x40": (a, b), "5x1300": (c, d), "70x1300": (e, f)}
+
+
+def near_pair_across_chunk():
+    """One marked pixel per side, ten columns apart on either side of column 1024, where the row passes' second chunk begins: the
+    match has to come through the carry from chunk to chunk."""
+    a, b = np.zeros((5, 1300), dtype=np.uint8), np.zeros((5, 1300), dtype=np.uint8)
+    a[2, 1030], b[2, 1020] = 255, 255
+    return a, b
+
+
+def test_near_pair_across_chunk_matches_only_at_a_wide_tolerance():
+    """Otherwise the device case that uses the pair would show nothing: class 1's mp and mg are 1 at theta = 20 and 0 at theta = 1."""
+    a, b = near_pair_across_chunk()
+    pred, label = np.stack([a, b]), np.stack([b, a])
+    wide, narrow = O.f_counts(pred, label, 20, 2)[0], O.f_counts(pred, label, 1, 2)[0]
+    assert wide[:, 1].tolist() == [[1, 1, 1, 1], [1, 1, 1, 1]] and narrow[:, 1].tolist() == [[0, 1, 0, 1], [0, 1, 0, 1]]
+
+
 def test_shifted_contours():
     """A blob image against itself three rows lower: the matches grow with the tolerance, and at 3 every contour pixel that is
     farther than 3 pixels from the frame has its partner."""

@@ -209,15 +209,15 @@ def test_workspace_cache_is_bounded_and_caller_workspace():
         a, b = O.blobs(rng, 20, W, density=0.03, grow=3), O.blobs(rng, 20, W, density=0.03, grow=3)
         want[W] = (a, b, O.counts(a, b, 2, 2)[0])
         assert torch.equal(E.boundary_counts_u8(torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV), 2).cpu(), torch.from_numpy(want[W][2]))
-        assert len(E._boundary_workspace_cache) <= E._BOUNDARY_WORKSPACES
-    assert (1, 20, 30, str(torch.device(DEV, torch.cuda.current_device()))) not in E._boundary_workspace_cache       # the oldest went first
+        assert len(E._workspace_caches["boundary"]) <= E._BOUNDARY_WORKSPACES
+    assert (1, 20, 30, str(torch.device(DEV, torch.cuda.current_device()))) not in E._workspace_caches["boundary"]       # the oldest went first
     a, b, cnt = want[30]
     ta, tb = torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV)
     ws = E.boundary_workspace(1, 20, 30, DEV)
-    n_cached = len(E._boundary_workspace_cache)
+    n_cached = len(E._workspace_caches["boundary"])
     assert torch.equal(E.boundary_counts_u8(ta, tb, 2, workspace=ws).cpu(), torch.from_numpy(cnt))
     assert torch.equal(E.boundary_band_u8(ta, 2, workspace=ws), E.boundary_band_u8(ta, 2))
-    assert len(E._boundary_workspace_cache) <= E._BOUNDARY_WORKSPACES and n_cached <= E._BOUNDARY_WORKSPACES
+    assert len(E._workspace_caches["boundary"]) <= E._BOUNDARY_WORKSPACES and n_cached <= E._BOUNDARY_WORKSPACES
     for bad in (ws[:16], ws.cpu(), ws.to(torch.int8)):
         with pytest.raises(ValueError):
             E.boundary_counts_u8(ta, tb, 2, workspace=bad)

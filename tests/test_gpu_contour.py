@@ -12,7 +12,7 @@ import torch
 
 import boundary_oracle as BO
 import contour_oracle as O
-from test_contour_cpu import shifted_pair
+from test_contour_cpu import far_pairs, near_pair_across_chunk, shifted_pair
 from test_gpu_boundary import _ens, _photos_and_masks, _stack, models  # noqa: F401  (models is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -88,6 +88,17 @@ def test_bands_contours_and_counts(shape, d):
     assert bw[0, 1].tolist() == [0, 0, int((bwl[0] >> 1).sum())]               # an empty prediction
     if H >= 3:                                                                 # the row image: the line is all contour, as are its two neighbours
         assert int((kwp[2] >> 1).sum()) == W and int((kwp[2] & 1).sum()) == 2 * W
+
+
+@pytest.mark.parametrize("pair,d", [("far", 254), ("far", 1), ("near", 20)], ids=["far-r254", "far-r1", "near-r20"])
+def test_rows_wider_than_a_chunk(pair, d):
+    """5 x 1300, the row passes' second chunk in use, against the oracle (the F row pass is also the surface distances', so their
+    agreement with each other in test_gpu_surface.py does not show it right).  far: marks 1287 columns apart, the byte cap reached in
+    both sweeps and carried across the chunk boundary.  near: a match ten columns across column 1024 that a wrong carry would lose."""
+    a, b = far_pairs()["5x1300"] if pair == "far" else near_pair_across_chunk()
+    fw = _check(np.stack([a, b]), np.stack([b, a]), d, 2)[3]
+    assert fw[:, 1, 1].min() > 0 and fw[:, 1, 3].min() > 0                      # both sides have a contour of class 1 ...
+    assert (fw[:, 1, [0, 2]] > 0).all() if pair == "near" else not fw[:, 1, [0, 2]].any()      # ... matched only by the near pair
 
 
 def test_disc_and_box_differ_on_the_device():
@@ -251,26 +262,26 @@ def test_workspace_cache_is_bounded_and_caller_workspace():
     from egm_unet_amd import ensemble as E
     rng = np.random.default_rng(21)
     want = {}
-    n_box = len(E._boundary_workspace_cache)
+    n_box = len(E._workspace_caches["boundary"])
     for W in range(30, 30 + E._BOUNDARY_WORKSPACES + 3):                        # more shapes than the module keeps
         a, b = O.blobs(rng, 20, W, density=0.03, grow=3), O.blobs(rng, 20, W, density=0.03, grow=3)
         want[W] = (a, b, O.band_counts(a, b, 2, 2)[0], O.f_counts(a, b, 2, 2)[0])
         ta, tb = torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV)
         assert torch.equal(E.boundary_counts_u8(ta, tb, 2, metric="euclid").cpu(), torch.from_numpy(want[W][2]))
         assert torch.equal(E.contour_f_counts_u8(ta, tb, 2).cpu(), torch.from_numpy(want[W][3]))
-        assert len(E._contour_workspace_cache) <= E._BOUNDARY_WORKSPACES
+        assert len(E._workspace_caches["contour"]) <= E._BOUNDARY_WORKSPACES
     dev = str(torch.device(DEV, torch.cuda.current_device()))
-    assert (1, 20, 30, 2, dev) not in E._contour_workspace_cache and (1, 20, 36, 2, dev) in E._contour_workspace_cache     # the oldest went first
-    assert len(E._boundary_workspace_cache) == n_box                            # the box metric's cache is its own
+    assert (1, 20, 30, 2, dev) not in E._workspace_caches["contour"] and (1, 20, 36, 2, dev) in E._workspace_caches["contour"]     # the oldest went first
+    assert len(E._workspace_caches["boundary"]) == n_box                            # the box metric's cache is its own
     a, b, cnt, fcnt = want[30]
     ta, tb = torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV)
     ws = E.contour_workspace(1, 20, 30, 2, DEV)
     assert ws.numel() == 5 * 20 * 32 + 16
-    keys = list(E._contour_workspace_cache)
+    keys = list(E._workspace_caches["contour"])
     assert torch.equal(E.boundary_counts_u8(ta, tb, 2, metric="euclid", workspace=ws).cpu(), torch.from_numpy(cnt))
     assert torch.equal(E.contour_f_counts_u8(ta, tb, 2, workspace=ws).cpu(), torch.from_numpy(fcnt))
     assert torch.equal(E.boundary_band_u8(ta, 2, metric="euclid", workspace=ws), E.boundary_band_u8(ta, 2, metric="euclid"))
-    assert list(E._contour_workspace_cache)[:len(keys) - 1] == keys[1:]          # only the call without a workspace touched the cache
+    assert list(E._workspace_caches["contour"])[:len(keys) - 1] == keys[1:]          # only the call without a workspace touched the cache
     assert torch.equal(E.contour_u8(ta, workspace=ws), E.contour_u8(ta))
     for bad in (ws[:16], ws.cpu(), ws.to(torch.int8), E.boundary_workspace(1, 20, 30, DEV)):    # (the box workspace is too small)
         with pytest.raises(ValueError):

@@ -12,7 +12,7 @@ import torch
 
 import contour_oracle as O
 import surface_oracle as S
-from test_contour_cpu import shifted_pair
+from test_contour_cpu import far_pairs, shifted_pair
 from test_gpu_boundary import _ens, _photos_and_masks, _stack, models  # noqa: F401  (models is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -88,24 +88,11 @@ def test_counts_and_maps(shape):
         assert want[2, 1, 0].tolist() == [W] + [0] * (FIELDS - 1) and want[2, 1, 1].sum() == 0
 
 
-def _far_pairs():
-    a, b = np.zeros((300, 40), dtype=np.uint8), np.zeros((300, 40), dtype=np.uint8)
-    a[2, 5:30] = 255                                                           # ... rows 2 and 290: the walk spans many tiles
-    b[290, 12:20] = 255
-    c, d = np.zeros((5, 1300), dtype=np.uint8), np.zeros((5, 1300), dtype=np.uint8)
-    c[1:4, 3] = 255                                                            # columns 3 and 1290: past a byte and across a 1024 chunk's carry
-    d[2, 1290] = 255
-    e, f = np.zeros((70, 1300), dtype=np.uint8), np.zeros((70, 1300), dtype=np.uint8)
-    e[3:9, 4:12] = 255                                                         # far apart along a diagonal
-    f[60:66, 1270:1290] = 255
-    return {"300x40": (a, b), "5x1300": (c, d), "70x1300": (e, f)}
-
-
 @pytest.mark.parametrize("name", ["300x40", "5x1300", "70x1300"])
 def test_distances_beyond_a_byte(name):
     """The 255 cap of the 6.18 kernels would fail all three: every distance of class 1 is above 254."""
     from egm_unet_amd.ensemble import surface_report
-    a, b = _far_pairs()[name]
+    a, b = far_pairs()[name]
     pred, label = np.stack([a, b]), np.stack([b, a])
     want, wp, wl = _check(pred, label, 2)
     assert want[:, 1, :, 3].min() > 254 * 254 and (want[:, 1, :, 4 + 255] == want[:, 1, :, 0]).all() and want[:, 1, :, 0].min() > 0
@@ -292,24 +279,24 @@ def test_workspace_cache_is_bounded_and_caller_workspace():
     from egm_unet_amd import ensemble as E
     rng = np.random.default_rng(21)
     want = {}
-    n_contour = len(E._contour_workspace_cache)
+    n_contour = len(E._workspace_caches["contour"])
     for W in range(30, 30 + E._BOUNDARY_WORKSPACES + 3):                        # more shapes than the module keeps
         a, b = O.blobs(rng, 20, W, density=0.03, grow=3), O.blobs(rng, 20, W, density=0.03, grow=3)
         want[W] = (a, b, S.counts(a, b, 2))
         ta, tb = torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV)
         assert torch.equal(E.surface_counts_u8(ta, tb).cpu(), torch.from_numpy(want[W][2]))
-        assert len(E._surface_workspace_cache) <= E._BOUNDARY_WORKSPACES
+        assert len(E._workspace_caches["surface"]) <= E._BOUNDARY_WORKSPACES
     dev = str(torch.device(DEV, torch.cuda.current_device()))
-    assert (1, 20, 30, 2, dev) not in E._surface_workspace_cache and (1, 20, 36, 2, dev) in E._surface_workspace_cache     # the oldest went first
-    assert len(E._contour_workspace_cache) == n_contour                         # the contour kernels' cache is its own
+    assert (1, 20, 30, 2, dev) not in E._workspace_caches["surface"] and (1, 20, 36, 2, dev) in E._workspace_caches["surface"]     # the oldest went first
+    assert len(E._workspace_caches["contour"]) == n_contour                         # the contour kernels' cache is its own
     a, b, cnt = want[30]
     ta, tb = torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV)
     ws = E.surface_workspace(1, 20, 30, 2, DEV)
     assert ws.numel() == E.lib().query("egm_surface_workspace", 1, 20, 30, 2) and ws.dtype == torch.uint8
-    keys = list(E._surface_workspace_cache)
+    keys = list(E._workspace_caches["surface"])
     assert torch.equal(E.surface_counts_u8(ta, tb, workspace=ws).cpu(), torch.from_numpy(cnt))
     assert torch.equal(E.surface_dist2_u8(ta, tb, workspace=ws)[0], E.surface_dist2_u8(ta, tb)[0])
-    assert list(E._surface_workspace_cache)[:len(keys) - 1] == keys[1:]          # only the call without a workspace touched the cache
+    assert list(E._workspace_caches["surface"])[:len(keys) - 1] == keys[1:]          # only the call without a workspace touched the cache
     for bad in (ws[:16], ws.cpu(), ws.to(torch.int8), E.contour_workspace(1, 20, 30, 2, DEV)):    # (the contour workspace is too small)
         with pytest.raises(ValueError):
             E.surface_counts_u8(ta, tb, workspace=bad)
