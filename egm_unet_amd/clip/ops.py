@@ -1,6 +1,7 @@
 """Inference operators of the CLIP / CLIPSeg path over libegm_hip.so (no autograd: the CLIP backbone is frozen in the
 reference, models/clipseg.py:155-156, and only forward passes are used by predict_CLIPseg.py / eval_CLIPseg.py)."""
 import math
+from types import SimpleNamespace
 
 import torch
 
@@ -185,42 +186,37 @@ def baseline_packed(w_red, w1, w2, wt):
     return out
 
 
+def _baseline_fwd(multi, x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off, u, h, prompts_per_group):
+    """The two forward entries of csrc/clipseg_baseline.hip behind baseline_head (multi = False) and baseline_head_multi."""
+    B, Ltot, _ = x.shape
+    K = mul.shape[0] if multi else 1
+    g = int(math.isqrt(Ltot - tok_off))
+    if g * g != Ltot - tok_off:
+        raise RuntimeError(f"baseline_head{'_multi' if multi else ''}: {Ltot - tok_off} grid tokens do not form a square grid")
+    x = x.contiguous()
+    pk = baseline_packed(w_red, w1, w2, wt)
+    out = torch.empty((B, K, g * BASELINE_PATCH, g * BASELINE_PATCH), dtype=torch.float32, device=x.device)
+    f32 = [t.detach().float().contiguous() for t in (b_red, b1, b2, bt)]
+    mul, add = mul.contiguous(), add.contiguous()
+    tail = (ptr(out), B, K, g, w_red.shape[0], w1.shape[0], BASELINE_PATCH, int(prompts_per_group)) if multi else \
+        (ptr(u), ptr(h), ptr(out), B, g, w_red.shape[0], w1.shape[0], BASELINE_PATCH)
+    lib().call("egm_baseline_fwd_multi" if multi else "egm_baseline_fwd", dtype_code(x.dtype), ptr(x), tok_off, Ltot, ptr(mul), ptr(add), ptr(pk),
+               ptr(f32[0]), ptr(f32[1]), ptr(f32[2]), ptr(f32[3]), *tail, stream())
+    return out
+
+
 def baseline_head(x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off=1, u=None, h=None):
     """CLIPDenseBaseline's head (models/clipseg.py:567-583) as ONE launch: x [B, Ltot, 768] bf16 (tok_off leading tokens skipped),
     mul / add [B, rd] bf16 (film_mul / film_add of the conditional) -> fp32 [B, 1, 16g, 16g].  u [B, g*g, rd] / h [B, g*g, rd2] (bf16,
     both or neither) receive reduce's output and the ReLU output for the training backward."""
-    B, Ltot, _ = x.shape
-    rd, rd2 = w_red.shape[0], w1.shape[0]
-    g = int(math.isqrt(Ltot - tok_off))
-    if g * g != Ltot - tok_off:
-        raise RuntimeError(f"baseline_head: {Ltot - tok_off} grid tokens do not form a square grid")
-    x = x.contiguous()
-    pk = baseline_packed(w_red, w1, w2, wt)
-    out = torch.empty((B, 1, g * BASELINE_PATCH, g * BASELINE_PATCH), dtype=torch.float32, device=x.device)
-    f32 = [t.detach().float().contiguous() for t in (b_red, b1, b2, bt)]
-    mul, add = mul.contiguous(), add.contiguous()
-    lib().call("egm_baseline_fwd", dtype_code(x.dtype), ptr(x), tok_off, Ltot, ptr(mul), ptr(add), ptr(pk),
-               ptr(f32[0]), ptr(f32[1]), ptr(f32[2]), ptr(f32[3]), ptr(u), ptr(h), ptr(out), B, g, rd, rd2, BASELINE_PATCH, stream())
-    return out
+    return _baseline_fwd(False, x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off, u, h, 0)
 
 
 def baseline_head_multi(x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off=1, prompts_per_group=0):
     """baseline_head for K prompts on each of B activations, ONE launch: x [B, Ltot, 768] bf16, mul / add [K, rd] bf16 -> fp32
     [B, K, 16g, 16g] (out[b, k] = baseline_head(x[b:b+1], mul[k:k+1], add[k:k+1])[0, 0], bit for bit).  reduce runs once per token
     tile and prompt group; prompts_per_group <= 0 lets the library choose the groups."""
-    B, Ltot, _ = x.shape
-    K = mul.shape[0]
-    g = int(math.isqrt(Ltot - tok_off))
-    if g * g != Ltot - tok_off:
-        raise RuntimeError(f"baseline_head_multi: {Ltot - tok_off} grid tokens do not form a square grid")
-    x = x.contiguous()
-    pk = baseline_packed(w_red, w1, w2, wt)
-    out = torch.empty((B, K, g * BASELINE_PATCH, g * BASELINE_PATCH), dtype=torch.float32, device=x.device)
-    f32 = [t.detach().float().contiguous() for t in (b_red, b1, b2, bt)]
-    mul, add = mul.contiguous(), add.contiguous()
-    lib().call("egm_baseline_fwd_multi", dtype_code(x.dtype), ptr(x), tok_off, Ltot, ptr(mul), ptr(add), ptr(pk), ptr(f32[0]), ptr(f32[1]),
-               ptr(f32[2]), ptr(f32[3]), ptr(out), B, K, g, w_red.shape[0], w1.shape[0], BASELINE_PATCH, int(prompts_per_group), stream())
-    return out
+    return _baseline_fwd(True, x, mul, add, w_red, b_red, w1, b1, w2, b2, wt, bt, tok_off, None, None, prompts_per_group)
 
 
 def film_fanout(r, mul, add):
@@ -264,3 +260,55 @@ def sigmoid_affine_(x, scale, offset):
         raise RuntimeError("sigmoid_affine_: x must be contiguous fp32 [N, C, H, W] and scale [C]")
     lib().call("egm_sigmoid_affine", ptr(x), ptr(scale.float().contiguous()), float(offset), N, C, H * W, stream())
     return x
+
+
+def trans_conv(a, weight, bias):
+    """ConvTranspose2d(rd -> 1, P, stride P) on a [B, 1 + g*g, rd] (token 0 dropped) as a per-token GEMM + pixel shuffle -> fp32 NCHW."""
+    bs, Ltot, rd = a.shape
+    P, dt, dev = weight.shape[-1], a.dtype, a.device
+    g = int(math.isqrt(Ltot - 1))
+    y = torch.empty((bs * Ltot, P * P), dtype=dt, device=dev)          # per-token rd -> P x P patch (ConvTranspose2d as a GEMM)
+    gemm(a.reshape(-1, rd), rd, cast_weight(weight.reshape(rd, P * P), dt), P * P, False, y, P * P, bs * Ltot, P * P, rd, dt)
+    out = torch.empty((bs, 1, g * P, g * P), dtype=torch.float32, device=dev)
+    lib().call("egm_pixel_shuffle", dtype_code(dt), ptr(y), P * P, 1, Ltot, ptr(bias.detach().float()), ptr(out), bs, g, P, stream())
+    return out
+
+
+# ---- the decoder's operator set, inference form (clip/train_ops.DECODER is the autograd form: same names, same positional parameters;
+# clipseg.py's one decode loop per model class runs on either).  p is the dropout probability: 0 here.
+def _no_dropout(p):
+    if p:
+        raise RuntimeError(f"the inference operators have no dropout (p = {p})")
+
+
+def _self_attention(qkv, n_heads, p_drop):
+    _no_dropout(p_drop)
+    return attention(qkv, n_heads, "full")
+
+
+def _linear_dropout(x, weight, bias, p, act=0, residual=None):
+    """residual + dropout(act(linear(x)), p)"""
+    _no_dropout(p)
+    return linear(x, weight, bias, act=act, residual=residual)
+
+
+def _film_(a, mul, add):
+    """a [B, L, D] <- mul[b] * a + add[b] in place; returns a."""
+    lib().call("egm_film", dtype_code(a.dtype), ptr(a), ptr(mul), ptr(add), a.shape[0], a.shape[1], a.shape[2], stream())
+    return a
+
+
+def _refine_seq(a, seq):
+    """refine_head over the reference's nn.Sequential(Conv2d, ReLU, ConvTranspose2d, ReLU, ConvTranspose2d)."""
+    return refine_head(a, seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias, seq[4].weight, seq[4].bias)
+
+
+def _baseline_fused(x, mul, add, reduce, reduce2, trans_conv, fan):
+    """The fused baseline head over the reference's modules; fan: mul / add hold K prompts for every image (-> [B, K, 16g, 16g])."""
+    return (baseline_head_multi if fan else baseline_head)(x, mul, add, reduce.weight, reduce.bias, reduce2[0].weight, reduce2[0].bias,
+                                                           reduce2[2].weight, reduce2[2].bias, trans_conv.weight, trans_conv.bias)
+
+
+DECODER = SimpleNamespace(training=False, linear=linear, layernorm=layernorm, self_attention=_self_attention, linear_dropout=_linear_dropout,
+                          film=_film_, film_fan=film_fanout, add_fan=bcast_add_, trans_conv=trans_conv, refine=_refine_seq,
+                          baseline_fused=_baseline_fused)

@@ -5,6 +5,7 @@ the saved operands, the row-wise pieces (softmax, LayerNorm, FiLM, ReLU mask, pi
 csrc/train_clip.hip.  Parameter gradients are fp32, activation gradients use the activation dtype.  No torch arithmetic."""
 import ctypes
 import math
+from types import SimpleNamespace
 
 import torch
 from torch.autograd import Function
@@ -304,15 +305,8 @@ class TransConvFn(Function):
 
     @staticmethod
     def forward(ctx, a, weight, bias):
-        B, Ltot, rd = a.shape
-        P, dt, dev = weight.shape[-1], a.dtype, a.device
-        g = int(math.isqrt(Ltot - 1))
-        y = torch.empty((B * Ltot, P * P), dtype=dt, device=dev)
-        O.gemm(a.reshape(-1, rd), rd, O.cast_weight(weight.reshape(rd, P * P), dt), P * P, False, y, P * P, B * Ltot, P * P, rd, dt)
-        out = torch.empty((B, 1, g * P, g * P), dtype=torch.float32, device=dev)
-        lib().call("egm_pixel_shuffle", dtype_code(dt), ptr(y), P * P, 1, Ltot, ptr(bias.detach()), ptr(out), B, g, P, stream())
         ctx.save_for_backward(a, weight)
-        return out
+        return O.trans_conv(a, weight, bias)
 
     @staticmethod
     def backward(ctx, gout):
@@ -438,6 +432,41 @@ def baseline_head(x, mul, add, reduce, reduce2, trans_conv):
     """BaselineHeadFn over the reference's modules: reduce (Linear), reduce2 (Sequential(Linear, ReLU, Linear)), trans_conv."""
     return BaselineHeadFn.apply(x, mul, add, reduce.weight, reduce.bias, reduce2[0].weight, reduce2[0].bias, reduce2[2].weight,
                                 reduce2[2].bias, trans_conv.weight, trans_conv.bias)
+
+
+# ---- the decoder's operator set, autograd form (clip/ops.DECODER is the inference form: same names, same positional parameters)
+def _linear_dropout(x, weight, bias, p, act=0, residual=None):
+    """residual + dropout(act(linear(x)), p); p == 0: no dropout kernel, the residual rides in the linear's epilogue."""
+    if p == 0.0:
+        return LinearFn.apply(x, weight, bias, act, residual)
+    return DropoutFn.apply(LinearFn.apply(x, weight, bias, act, None), p, residual)
+
+
+def _film(a, mul, add):
+    return FilmFn.apply(a, mul, add)
+
+
+def _film_fan(r, mul, add):
+    return FilmFanoutFn.apply(r, mul, add)
+
+
+def _add_fan(a, r):
+    return BcastAddFn.apply(a, r)
+
+
+def _trans_conv(a, weight, bias):
+    return TransConvFn.apply(a, weight, bias)
+
+
+def _baseline_fused(x, mul, add, reduce, reduce2, trans_conv, fan):
+    if fan:
+        raise NotImplementedError("BaselineHeadFn takes one prompt per image; the K-prompt training head runs on the composed operators")
+    return baseline_head(x, mul, add, reduce, reduce2, trans_conv)
+
+
+DECODER = SimpleNamespace(training=True, linear=linear, layernorm=layernorm, self_attention=attention, linear_dropout=_linear_dropout,
+                          film=_film, film_fan=_film_fan, add_fan=_add_fan, trans_conv=_trans_conv, refine=refine,
+                          baseline_fused=_baseline_fused)
 
 
 class BCEWithLogitsFn(Function):

@@ -5,7 +5,6 @@
     model.load_state_dict(torch.load('weights/rd64-uni.pth'), strict=False)
     mask_logits = model(images, prompts)[0]                          # [B, 1, H, W] fp32
 """
-import math
 import os
 
 import torch
@@ -146,7 +145,8 @@ class CLIPDenseBase(nn.Module):
         with torch.no_grad():
             cond = self._multi_cond(conditionals)
             condT = self._cond_in_dtype(cond)
-        out = self._decode_multi_train(x_inp, condT)
+        from .clip.train_ops import DECODER as T
+        out = self._decode_multi(x_inp, condT, T)
         B, K = x_inp.shape[0], cond.shape[0]
         return out.view(B, K, out.shape[-2], out.shape[-1])
 
@@ -179,18 +179,15 @@ class CLIPDenseBase(nn.Module):
         lib().call("egm_cast_f32", dtype_code(self.compute_dtype), ptr(cond.float().contiguous()), ptr(condT), cond.numel(), stream())
         return condT
 
-    def _trans_conv_eval(self, a):
-        """ConvTranspose2d(rd -> 1, P, stride P) on a [B, 1 + g*g, rd] (token 0 dropped) as a per-token GEMM + pixel shuffle -> fp32 NCHW."""
-        bs, Ltot, rd = a.shape
-        dt, dev = a.dtype, a.device
-        g = int(math.isqrt(Ltot - 1))
-        P = self.trans_conv.kernel_size[0]
-        y = torch.empty((bs * Ltot, P * P), dtype=dt, device=dev)      # per-token 64 -> 16x16 patch (ConvTranspose2d as a GEMM)
-        O.gemm(a.reshape(-1, rd), rd, O.cast_weight(self.trans_conv.weight.reshape(rd, P * P), dt), P * P, False, y, P * P, bs * Ltot, P * P, rd, dt)
-        out = torch.empty((bs, 1, g * P, g * P), dtype=torch.float32, device=dev)
-        lib().call("egm_pixel_shuffle", dtype_code(dt), ptr(y), P * P, 1, Ltot, ptr(self.trans_conv.bias.detach().float()), ptr(out), bs, g, P,
-                   stream())
-        return out
+    def _film_vecs(self, ops, condT):
+        """(mul, add) = (film_mul, film_add) of the conditional vectors [N, 512] -> [N, rd] each."""
+        return ops.linear(condT, self.film_mul.weight, self.film_mul.bias), ops.linear(condT, self.film_add.weight, self.film_add.bias)
+
+    def _features(self, out, q_raw, cond, acts, return_features):
+        """forward()'s result: (logits,) or, with return_features, the reference's (logits, visual_q, cond, fp32 [L, B, 768] activations)."""
+        if return_features:
+            return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts]
+        return out,
 
 
 class CLIPDensePredT(CLIPDenseBase):
@@ -231,13 +228,14 @@ class CLIPDensePredT(CLIPDenseBase):
         self.n_heads = n_heads
         self.decoder_dropout = None          # None: the encoder layers' own p (0.1, as in the reference's train mode); 0.0 disables it
 
-    def _encoder_layer(self, blk, a):
-        """nn.TransformerEncoderLayer defaults in eval mode: post-norm, ReLU feed-forward, no dropout."""
-        qkv = O.linear(a, blk.self_attn.in_proj_weight, blk.self_attn.in_proj_bias)
-        att = O.attention(qkv, self.n_heads, "full")
-        a = O.layernorm(O.linear(att, blk.self_attn.out_proj.weight, blk.self_attn.out_proj.bias, residual=a), blk.norm1)
-        h = O.linear(a, blk.linear1.weight, blk.linear1.bias, act=1)
-        return O.layernorm(O.linear(h, blk.linear2.weight, blk.linear2.bias, residual=a), blk.norm2)
+    def _encoder_layer(self, ops, blk, a, p):
+        """nn.TransformerEncoderLayer defaults (post-norm, ReLU feed-forward) with dropout p on the attention weights, behind the attention
+        output projection, behind the ReLU and behind the second feed-forward linear (models/clipseg.py:421-422); p = 0: eval mode."""
+        at = blk.self_attn
+        att = ops.self_attention(ops.linear(a, at.in_proj_weight, at.in_proj_bias), self.n_heads, p)
+        a = ops.layernorm(ops.linear_dropout(att, at.out_proj.weight, at.out_proj.bias, p, 0, a), blk.norm1)
+        h = ops.linear_dropout(a, blk.linear1.weight, blk.linear1.bias, p, 1)
+        return ops.layernorm(ops.linear_dropout(h, blk.linear2.weight, blk.linear2.bias, p, 0, a), blk.norm2)
 
     def forward(self, inp_image, conditional=None, return_features=False, mask=None):
         """models/clipseg.py:436-496.  eval(): inference path, no autograd.  train(): the decoder (reduces, FiLM, blocks, trans_conv)
@@ -246,139 +244,49 @@ class CLIPDensePredT(CLIPDenseBase):
         assert type(return_features) == bool
         if mask is not None:
             raise ValueError("mask not supported")                  # as the reference (models/clipseg.py:442-443)
-        if self.training and torch.is_grad_enabled():
-            return self._forward_train(inp_image, conditional, return_features)
+        train = self.training and torch.is_grad_enabled()
         with torch.no_grad():
-            return self._forward_eval(inp_image, conditional, return_features)
-
-    def _encoder_layer_train(self, blk, a):
-        """nn.TransformerEncoderLayer in train mode (post-norm, ReLU): dropout p on the attention weights, behind the attention output
-        projection, behind the ReLU and behind the second feed-forward linear (models/clipseg.py:421-422, p = 0.1 by default)."""
-        from .clip import train_ops as T
-        p = self.decoder_dropout if self.decoder_dropout is not None else float(blk.dropout.p)
-        qkv = T.linear(a, blk.self_attn.in_proj_weight, blk.self_attn.in_proj_bias)
-        att = T.attention(qkv, self.n_heads, p)
-        if p == 0.0:
-            a = T.layernorm(T.linear(att, blk.self_attn.out_proj.weight, blk.self_attn.out_proj.bias, residual=a), blk.norm1)
-            h = T.linear(a, blk.linear1.weight, blk.linear1.bias, act=1)
-            return T.layernorm(T.linear(h, blk.linear2.weight, blk.linear2.bias, residual=a), blk.norm2)
-        a = T.layernorm(T.dropout(T.linear(att, blk.self_attn.out_proj.weight, blk.self_attn.out_proj.bias), p, residual=a), blk.norm1)
-        h = T.dropout(T.linear(a, blk.linear1.weight, blk.linear1.bias, act=1), p)
-        return T.layernorm(T.dropout(T.linear(h, blk.linear2.weight, blk.linear2.bias), p, residual=a), blk.norm2)
-
-    def _forward_train(self, inp_image, conditional, return_features):
-        from .clip import train_ops as T
-        dev = self.model.positional_embedding.device
-        x_inp = inp_image.to(dev)
-        bs = x_inp.shape[0]
-        with torch.no_grad():
-            cond = self.get_cond_vec(conditional, bs)
+            x_inp = inp_image.to(self.model.positional_embedding.device)
+            cond = self.get_cond_vec(conditional, x_inp.shape[0])
             q_raw, acts_all = self._visual_run(x_inp, extract_layers=[0] + list(self.extract_layers))
-        dt, code = self.compute_dtype, dtype_code(self.compute_dtype)
-        acts = acts_all[1:]
-        acts = acts[::-1] if not self.rev_activations else acts
-        condT = torch.empty(cond.shape, dtype=dt, device=dev)
-        lib().call("egm_cast_f32", code, ptr(cond.float().contiguous()), ptr(condT), cond.numel(), stream())
-        a = None
-        for i, (act, blk, red) in enumerate(zip(acts, self.blocks, self.reduces)):
-            a = T.linear(act.detach(), red.weight, red.bias, residual=a)
-            if i == self.cond_layer:
-                a = T.FilmFn.apply(a, T.linear(condT, self.film_mul.weight, self.film_mul.bias),
-                                   T.linear(condT, self.film_add.weight, self.film_add.bias))
-            a = self._encoder_layer_train(blk, a)
-        if self.complex_trans_conv:
-            out = T.refine(a, self.trans_conv)
-        else:
-            out = T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
-        if return_features:
-            return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts_all]
-        return out,
+            condT = self._cond_in_dtype(cond)
+            if not train:
+                out = self._decode(O.DECODER, acts_all[1:], condT, False)
+        if train:
+            from .clip.train_ops import DECODER as T
+            out = self._decode(T, [t.detach() for t in acts_all[1:]], condT, False)
+        return self._features(out, q_raw, cond, acts_all, return_features)
 
-    def _forward_eval(self, inp_image, conditional=None, return_features=False):
-        dev = self.model.positional_embedding.device
-        x_inp = inp_image.to(dev)
-        bs = x_inp.shape[0]
-        cond = self.get_cond_vec(conditional, bs)
-        q_raw, acts_all = self._visual_run(x_inp, extract_layers=[0] + list(self.extract_layers))
-        dt, code, L_ = self.compute_dtype, dtype_code(self.compute_dtype), lib()
-        acts = acts_all[1:]
-        acts = acts[::-1] if not self.rev_activations else acts
-        condT = torch.empty(cond.shape, dtype=dt, device=dev)
-        L_.call("egm_cast_f32", code, ptr(cond.float().contiguous()), ptr(condT), cond.numel(), stream())
-        a = None
+    def _decode(self, ops, acts, condT, fan):
+        """The decoder on the operator set ops (clip/ops.DECODER or clip/train_ops.DECODER): per extracted layer reduce_i(act_i) + the
+        running a, FiLM at cond_layer, an encoder layer; then trans_conv or the refined head -> fp32 [N, 1, H', W'].
+        fan = False: condT [B, 512], one conditional per image, N = B.
+        fan = True: condT [K, 512], every image with every prompt, N = B*K.  The layers before cond_layer run on the B sequences; at
+        cond_layer one fan-out kernel writes a[b*K + k] = mul[k] * r[b] + add[k]; behind it reduce_i(act_i) stays a product over B*L
+        rows whose result is broadcast-added into the B*K sequences (so are its gradients: summed over the prompts)."""
+        acts = acts if self.rev_activations else acts[::-1]
+        a, fanned = None, False
         for i, (act, blk, red) in enumerate(zip(acts, self.blocks, self.reduces)):
-            a = O.linear(act, red.weight, red.bias, residual=a)
-            if i == self.cond_layer:
-                mul, add = O.linear(condT, self.film_mul.weight, self.film_mul.bias), O.linear(condT, self.film_add.weight, self.film_add.bias)
-                L_.call("egm_film", code, ptr(a), ptr(mul), ptr(add), bs, a.shape[1], a.shape[2], stream())
-            a = self._encoder_layer(blk, a)
+            if fanned:
+                a = ops.add_fan(a, ops.linear(act, red.weight, red.bias))
+            else:
+                a = ops.linear(act, red.weight, red.bias, residual=a)
+                if i == self.cond_layer:
+                    a = (ops.film_fan if fan else ops.film)(a, *self._film_vecs(ops, condT))
+                    fanned = fan
+            p = 0.0 if not ops.training else self.decoder_dropout if self.decoder_dropout is not None else float(blk.dropout.p)
+            a = self._encoder_layer(ops, blk, a, p)
+        if fan and not fanned:                                       # cond_layer behind the last layer: no FiLM, every prompt alike
+            one = torch.ones((condT.shape[0], a.shape[-1]), dtype=a.dtype, device=a.device)
+            a = ops.film_fan(a, one, torch.zeros_like(one))
         if self.complex_trans_conv:
-            tc = self.trans_conv
-            out = O.refine_head(a, tc[0].weight, tc[0].bias, tc[2].weight, tc[2].bias, tc[4].weight, tc[4].bias)
-            if return_features:
-                return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts_all]
-            return out,
-        out = self._trans_conv_eval(a)
-        if return_features:
-            return out, q_raw.float(), cond, [t.float().permute(1, 0, 2) for t in acts_all]
-        return out,
+            return ops.refine(a, self.trans_conv)
+        return ops.trans_conv(a, self.trans_conv.weight, self.trans_conv.bias)
 
-    def _decode_multi(self, x_inp, condT):
-        """forward_multi's decoder: layers before cond_layer on the B sequences; at cond_layer reduce (+ the running a) on B*L rows, then
-        one fan-out kernel writes a[b*K + k] = mul[k] * r[b] + add[k]; behind it reduce_i(act_i) stays a GEMM over B*L rows whose result
-        is broadcast-added into the B*K sequences.  Encoder layers and heads then run on B*K sequences -> fp32 [B*K, 1, H', W']."""
-        B, K = x_inp.shape[0], condT.shape[0]
+    def _decode_multi(self, x_inp, condT, ops=O.DECODER):
+        """forward_multi's (ops = clip/train_ops.DECODER: forward_multi_train's) backbone pass and decoder -> fp32 [B*K, 1, H', W']."""
         _, acts_all = self._visual_run(x_inp, extract_layers=[0] + list(self.extract_layers), stop_after=max(self.extract_layers))
-        acts = acts_all[1:]
-        acts = acts[::-1] if not self.rev_activations else acts
-        a, fanned = None, False
-        for i, (act, blk, red) in enumerate(zip(acts, self.blocks, self.reduces)):
-            if not fanned:
-                a = O.linear(act, red.weight, red.bias, residual=a)
-                if i == self.cond_layer:
-                    mul = O.linear(condT, self.film_mul.weight, self.film_mul.bias)
-                    add = O.linear(condT, self.film_add.weight, self.film_add.bias)
-                    a = O.film_fanout(a, mul, add)
-                    fanned = True
-            else:
-                O.bcast_add_(a, O.linear(act, red.weight, red.bias))
-            a = self._encoder_layer(blk, a)
-        if not fanned:                                               # cond_layer behind the last layer: no FiLM, every prompt alike
-            rd = a.shape[-1]
-            one = torch.ones((K, rd), dtype=a.dtype, device=a.device)
-            a = O.film_fanout(a, one, torch.zeros_like(one))
-        if self.complex_trans_conv:
-            tc = self.trans_conv
-            return O.refine_head(a, tc[0].weight, tc[0].bias, tc[2].weight, tc[2].bias, tc[4].weight, tc[4].bias)
-        return self._trans_conv_eval(a)
-
-
-    def _decode_multi_train(self, x_inp, condT):
-        """_decode_multi on the autograd operators of clip/train_ops.py: the reduces stay products over B*L rows in both directions
-        (FilmFanoutFn / BcastAddFn hand them the gradients summed over the prompts), encoder layers and heads run on B*K sequences."""
-        from .clip import train_ops as T
-        K = condT.shape[0]
-        with torch.no_grad():
-            _, acts_all = self._visual_run(x_inp, extract_layers=[0] + list(self.extract_layers), stop_after=max(self.extract_layers))
-        acts = acts_all[1:]
-        acts = acts[::-1] if not self.rev_activations else acts
-        a, fanned = None, False
-        for i, (act, blk, red) in enumerate(zip(acts, self.blocks, self.reduces)):
-            if not fanned:
-                a = T.linear(act.detach(), red.weight, red.bias, residual=a)
-                if i == self.cond_layer:
-                    a = T.FilmFanoutFn.apply(a, T.linear(condT, self.film_mul.weight, self.film_mul.bias),
-                                             T.linear(condT, self.film_add.weight, self.film_add.bias))
-                    fanned = True
-            else:
-                a = T.BcastAddFn.apply(a, T.linear(act.detach(), red.weight, red.bias))
-            a = self._encoder_layer_train(blk, a)
-        if not fanned:                                               # cond_layer behind the last layer: no FiLM, every prompt alike
-            one = torch.ones((K, a.shape[-1]), dtype=a.dtype, device=a.device)
-            a = T.FilmFanoutFn.apply(a, one, torch.zeros_like(one))
-        if self.complex_trans_conv:
-            return T.refine(a, self.trans_conv)
-        return T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
+        return self._decode(ops, [t.detach() for t in acts_all[1:]] if ops.training else acts_all[1:], condT, True)
 
 
 class CLIPDensePredTMasked(CLIPDensePredT):
@@ -438,76 +346,35 @@ class CLIPDenseBaseline(CLIPDenseBase):
         """models/clipseg.py:556-590.  eval(): inference, no autograd.  train(): film_mul / film_add / reduce / reduce2 / trans_conv are
         differentiable through the HIP operators of clip/train_ops.py; the CLIP backbone stays frozen."""
         assert type(return_features) == bool
-        dev = self.model.positional_embedding.device
-        x_inp = inp_image.to(dev)
-        bs = x_inp.shape[0]
+        x_inp = inp_image.to(self.model.positional_embedding.device)
         train = self.training and torch.is_grad_enabled()
         with torch.no_grad():
-            cond = self.get_cond_vec(conditional, bs)
+            cond = self.get_cond_vec(conditional, x_inp.shape[0])
             q_raw, acts = self._visual_run(x_inp, [self.extract_layer], stop_after=None if return_features else self.extract_layer)
             condT = self._cond_in_dtype(cond)
-        act = acts[0]
+            if not train:
+                out = self._head(O.DECODER, acts[0], *self._film_vecs(O.DECODER, condT), False)
         if train:
-            out = self._head_train(act.detach(), condT)
-        else:
-            with torch.no_grad():
-                out = self._head_eval(act, condT)
-        if return_features:
-            return out, q_raw.float(), cond, [act.float().permute(1, 0, 2)]
-        return out,
+            from .clip.train_ops import DECODER as T
+            out = self._head(T, acts[0].detach(), *self._film_vecs(T, condT), False)
+        return self._features(out, q_raw, cond, acts, return_features)
 
-    def _head_eval(self, act, condT):
-        mul = O.linear(condT, self.film_mul.weight, self.film_mul.bias)
-        add = O.linear(condT, self.film_add.weight, self.film_add.bias)
-        if self._fused():
-            r2 = self.reduce2
-            return O.baseline_head(act, mul, add, self.reduce.weight, self.reduce.bias, r2[0].weight, r2[0].bias, r2[2].weight, r2[2].bias,
-                                   self.trans_conv.weight, self.trans_conv.bias)
-        a = O.linear(act, self.reduce.weight, self.reduce.bias)
-        lib().call("egm_film", dtype_code(a.dtype), ptr(a), ptr(mul), ptr(add), a.shape[0], a.shape[1], a.shape[2], stream())
-        a = O.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
-        a = O.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
-        return self._trans_conv_eval(a)
+    def _head(self, ops, act, mul, add, fan):
+        """reduce -> FiLM -> reduce2 -> trans_conv on the operator set ops: the fused launch where it exists, else composed.
+        fan = False: mul / add [B, rd], one conditional per image -> fp32 [B, 1, H', W'].
+        fan = True: mul / add [K, rd], every image with every prompt; fused (inference only: reduce once per token tile) -> [B, K, H', W'],
+        composed (reduce on B*L rows, the FiLM fan-out, reduce2 / trans_conv on B*K sequences) -> [B*K, 1, H', W']."""
+        if self._fused() and not (fan and ops.training):
+            return ops.baseline_fused(act, mul, add, self.reduce, self.reduce2, self.trans_conv, fan)
+        a = (ops.film_fan if fan else ops.film)(ops.linear(act, self.reduce.weight, self.reduce.bias), mul, add)
+        a = ops.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
+        a = ops.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
+        return ops.trans_conv(a, self.trans_conv.weight, self.trans_conv.bias)
 
-    def _decode_multi(self, x_inp, condT):
-        """forward_multi's head: the backbone once (stopping after extract_layer), then the fused multi-prompt launch (reduce once per
-        token tile) or, composed, reduce on B*L rows + the FiLM fan-out + reduce2 / trans_conv on B*K sequences."""
+    def _decode_multi(self, x_inp, condT, ops=O.DECODER):
+        """forward_multi's (ops = clip/train_ops.DECODER: forward_multi_train's) head: the backbone once, stopping after extract_layer."""
         _, acts = self._visual_run(x_inp, [self.extract_layer], stop_after=self.extract_layer)
-        act = acts[0]
-        mul = O.linear(condT, self.film_mul.weight, self.film_mul.bias)
-        add = O.linear(condT, self.film_add.weight, self.film_add.bias)
-        if self._fused():
-            r2 = self.reduce2
-            return O.baseline_head_multi(act, mul, add, self.reduce.weight, self.reduce.bias, r2[0].weight, r2[0].bias, r2[2].weight,
-                                         r2[2].bias, self.trans_conv.weight, self.trans_conv.bias)
-        a = O.film_fanout(O.linear(act, self.reduce.weight, self.reduce.bias), mul, add)
-        a = O.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
-        a = O.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
-        return self._trans_conv_eval(a)
-
-    def _decode_multi_train(self, x_inp, condT):
-        """forward_multi_train's head on the composed autograd operators (either dtype): reduce on B*L rows, the FiLM fan-out, then
-        reduce2 / trans_conv on B*K sequences."""
-        from .clip import train_ops as T
-        with torch.no_grad():
-            _, acts = self._visual_run(x_inp, [self.extract_layer], stop_after=self.extract_layer)
-        mul = T.linear(condT, self.film_mul.weight, self.film_mul.bias)
-        add = T.linear(condT, self.film_add.weight, self.film_add.bias)
-        a = T.FilmFanoutFn.apply(T.linear(acts[0].detach(), self.reduce.weight, self.reduce.bias), mul, add)
-        a = T.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
-        a = T.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
-        return T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
-
-    def _head_train(self, act, condT):
-        from .clip import train_ops as T
-        mul = T.linear(condT, self.film_mul.weight, self.film_mul.bias)
-        add = T.linear(condT, self.film_add.weight, self.film_add.bias)
-        if self._fused():
-            return T.baseline_head(act, mul, add, self.reduce, self.reduce2, self.trans_conv)
-        a = T.FilmFn.apply(T.linear(act, self.reduce.weight, self.reduce.bias), mul, add)
-        a = T.linear(a, self.reduce2[0].weight, self.reduce2[0].bias, act=1)
-        a = T.linear(a, self.reduce2[2].weight, self.reduce2[2].bias)
-        return T.TransConvFn.apply(a, self.trans_conv.weight, self.trans_conv.bias)
+        return self._head(ops, acts[0].detach() if ops.training else acts[0], *self._film_vecs(ops, condT), True)
 
 
 # 'background' + datasets/pascal_classes.json in id order (the reference's third_party.JoEm VOC list, which its tree does not ship)

@@ -106,23 +106,19 @@ __device__ __forceinline__ void stage(bf16_t* dst, const bf16_t* src, int n16) {
     for (int i = threadIdx.x; i < n16; i += NT) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
 }
 
-// ---- forward ---------------------------------------------------------------------------------------------------------------
+// What both forward kernels start with: the wave's token tile (image b, token t of lane column col, tv: the token exists), W1 / W2 / Wt
+// staged into s_res, and acc = x W_red^T, the 768-deep product, with W_red streaming through s_wr in 64-feature chunks.
 template <int NP>
-__global__ __launch_bounds__(NT) void baseline_fwd_kernel(const bf16_t* __restrict__ x, int tok_off, int Ltot, const bf16_t* __restrict__ mul,
-                                                          const bf16_t* __restrict__ add, const bf16_t* __restrict__ pk,
-                                                          const float* __restrict__ b_red, const float* __restrict__ b1,
-                                                          const float* __restrict__ b2, const float* __restrict__ bt,
-                                                          bf16_t* __restrict__ u_out, bf16_t* __restrict__ h_out, float* __restrict__ out,
-                                                          int g, int rd, int rd2, long long nwt, long long ntpi) {
-    constexpr int MT = NP / 16, KS = NP / 32;
-    __shared__ __align__(16) bf16_t s_wr[64 * NP];                   // one 64-feature chunk of W_red
-    __shared__ __align__(16) bf16_t s_res[2 * NP * NP + PP * NP];    // W1 fwd | W2 fwd | Wt fwd
+__device__ __forceinline__ void reduce_product(const bf16_t* __restrict__ x, int tok_off, int Ltot, const bf16_t* __restrict__ pk, int g,
+                                               long long nwt, long long ntpi, bf16_t* s_wr, bf16_t* s_res, int& b, int& t, bool& tv,
+                                               f32x4_t (&acc)[NP / 16]) {
+    constexpr int MT = NP / 16;
     const int tid = threadIdx.x, lane = tid & 63, q = lane >> 4, col = lane & 15;
     const long long wt = (long long)blockIdx.x * WT + (tid >> 6);
     const bool has = wt < nwt;
-    const int b = has ? (int)(wt / ntpi) : 0;
-    const int t = has ? (int)(wt % ntpi) * TT + col : 0;
-    const bool tv = has && t < g * g;
+    b = has ? (int)(wt / ntpi) : 0;
+    t = has ? (int)(wt % ntpi) * TT + col : 0;
+    tv = has && t < g * g;
     // the token's 768 activations as B fragments: chunk c, step s -> features 64c + 16q + 8s .. +7
     bf16x8_t xf[24];
     {
@@ -133,7 +129,6 @@ __global__ __launch_bounds__(NT) void baseline_fwd_kernel(const bf16_t* __restri
             for (int s = 0; s < 2; ++s) xf[2 * c + s] = tv ? frag(xr + 64 * c + 8 * s) : zero8();
     }
     stage(s_res, pk + off_w1f(NP), (2 * NP * NP + PP * NP) / 8);
-    f32x4_t acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     for (int c = 0; c < 12; ++c) {
@@ -145,6 +140,24 @@ __global__ __launch_bounds__(NT) void baseline_fwd_kernel(const bf16_t* __restri
             for (int m = 0; m < MT; ++m) acc[m] = mfma(frag(s_wr + ((m * 2 + s) * 64 + lane) * 8), xf[2 * c + s], acc[m]);
         __syncthreads();
     }
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------
+template <int NP>
+__global__ __launch_bounds__(NT) void baseline_fwd_kernel(const bf16_t* __restrict__ x, int tok_off, int Ltot, const bf16_t* __restrict__ mul,
+                                                          const bf16_t* __restrict__ add, const bf16_t* __restrict__ pk,
+                                                          const float* __restrict__ b_red, const float* __restrict__ b1,
+                                                          const float* __restrict__ b2, const float* __restrict__ bt,
+                                                          bf16_t* __restrict__ u_out, bf16_t* __restrict__ h_out, float* __restrict__ out,
+                                                          int g, int rd, int rd2, long long nwt, long long ntpi) {
+    constexpr int MT = NP / 16, KS = NP / 32;
+    __shared__ __align__(16) bf16_t s_wr[64 * NP];                   // one 64-feature chunk of W_red
+    __shared__ __align__(16) bf16_t s_res[2 * NP * NP + PP * NP];    // W1 fwd | W2 fwd | Wt fwd
+    const int lane = threadIdx.x & 63, q = lane >> 4;
+    int b, t;
+    bool tv;
+    f32x4_t acc[MT];
+    reduce_product<NP>(x, tok_off, Ltot, pk, g, nwt, ntpi, s_wr, s_res, b, t, tv, acc);
     // u (rounded, saved) -> f
     const long long trow = (long long)b * g * g + t;
     bf16x8_t fb[KS];
@@ -217,35 +230,13 @@ __global__ __launch_bounds__(NT) void baseline_fwd_multi_kernel(const bf16_t* __
                                                                 const float* __restrict__ b2, const float* __restrict__ bt, float* __restrict__ out,
                                                                 int g, int rd, int rd2, long long nwt, long long ntpi, int K, int kpg) {
     constexpr int MT = NP / 16, KS = NP / 32;
-    __shared__ __align__(16) bf16_t s_wr[64 * NP];
-    __shared__ __align__(16) bf16_t s_res[2 * NP * NP + PP * NP];
-    const int tid = threadIdx.x, lane = tid & 63, q = lane >> 4, col = lane & 15;
-    const long long wt = (long long)blockIdx.x * WT + (tid >> 6);
-    const bool has = wt < nwt;
-    const int b = has ? (int)(wt / ntpi) : 0;
-    const int t = has ? (int)(wt % ntpi) * TT + col : 0;
-    const bool tv = has && t < g * g;
-    bf16x8_t xf[24];
-    {
-        const bf16_t* xr = x + ((long long)b * Ltot + tok_off + (tv ? t : 0)) * DX + 16 * q;
-#pragma unroll
-        for (int c = 0; c < 12; ++c)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) xf[2 * c + s] = tv ? frag(xr + 64 * c + 8 * s) : zero8();
-    }
-    stage(s_res, pk + off_w1f(NP), (2 * NP * NP + PP * NP) / 8);
+    __shared__ __align__(16) bf16_t s_wr[64 * NP];                   // one 64-feature chunk of W_red
+    __shared__ __align__(16) bf16_t s_res[2 * NP * NP + PP * NP];    // W1 fwd | W2 fwd | Wt fwd
+    const int lane = threadIdx.x & 63, q = lane >> 4;
+    int b, t;
+    bool tv;
     f32x4_t acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < 12; ++c) {
-        stage(s_wr, pk + off_wr(NP) + 64LL * NP * c, 64 * NP / 8);
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = mfma(frag(s_wr + ((m * 2 + s) * 64 + lane) * 8), xf[2 * c + s], acc[m]);
-        __syncthreads();
-    }
+    reduce_product<NP>(x, tok_off, Ltot, pk, g, nwt, ntpi, s_wr, s_res, b, t, tv, acc);
     f32x4_t u[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) {

@@ -65,3 +65,22 @@ def test_dense_pred_t_unchanged():
     want = json.load(open(os.path.join(GOLDEN, "clipseg_manifest.json")))
     assert list(m.state_dict()) == list(want)
     assert {k: list(v.shape) for k, v in m.state_dict().items()} == want
+
+
+def test_decoder_operator_sets_share_one_interface():
+    """clipseg.py's one decode loop per model class runs on clip/ops.DECODER (inference) or clip/train_ops.DECODER (autograd): the two
+    sets expose the same names and, name for name, the same positional parameters."""
+    import inspect
+    from egm_unet_amd.clip import ops as O, train_ops as T
+    inf, trn = vars(O.DECODER), vars(T.DECODER)
+    assert sorted(inf) == sorted(trn)
+    assert inf["training"] is False and trn["training"] is True
+    positional = (inspect.Parameter.POSITIONAL_ONLY, inspect.Parameter.POSITIONAL_OR_KEYWORD)
+    for name in inf:
+        if name == "training":
+            continue
+        assert callable(inf[name]) and callable(trn[name]), name
+        sig = [[p.name for p in inspect.signature(f).parameters.values() if p.kind in positional] for f in (inf[name], trn[name])]
+        assert sig[0] == sig[1] and sig[0], (name, sig)
+        kinds = {p.kind for f in (inf[name], trn[name]) for p in inspect.signature(f).parameters.values()}
+        assert kinds <= set(positional), (name, kinds)                   # no *args / **kwargs hiding a different list

@@ -79,6 +79,20 @@ def test_baseline_op_vs_float64(B, g, rd, rd2):
         assert torch.equal(g0, g1), name
 
 
+@pytest.mark.parametrize("rd,rd2", [(64, 128), (128, 64)])
+def test_baseline_op_output_does_not_depend_on_saving_u_h(rd, rd2):
+    """B = 3, g = 3: 9 tokens in a 16-token wave tile, a ragged last workgroup, zero pad rows between rd / rd2 and NP = 128."""
+    from egm_unet_amd.clip import ops as O
+    B, g = 3, 3
+    gen = torch.Generator().manual_seed(rd + 2 * rd2)
+    x = torch.randn(B, 1 + g * g, 768, generator=gen).to(DEV).bfloat16()
+    mul, add = (1.0 + 0.3 * torch.randn(B, rd, generator=gen)).to(DEV).bfloat16(), (0.2 * torch.randn(B, rd, generator=gen)).to(DEV).bfloat16()
+    ps = [p.to(DEV) for p in head_params(rd, rd2, 11)]
+    u = torch.empty(B, g * g, rd, device=DEV, dtype=torch.bfloat16)
+    h = torch.empty(B, g * g, rd2, device=DEV, dtype=torch.bfloat16)
+    assert torch.equal(O.baseline_head(x, mul, add, *ps, u=u, h=h), O.baseline_head(x, mul, add, *ps))
+
+
 def test_baseline_bwd_du_class_token_row_is_zero():
     from egm_unet_amd._lib import dtype_code, lib, ptr, stream
     from egm_unet_amd.clip import ops as O

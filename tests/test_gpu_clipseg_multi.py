@@ -108,6 +108,22 @@ def test_baseline_multi_op_vs_float64_and_single(B, K, g, rd, rd2):
         assert torch.equal(O.baseline_head_multi(xg, mg, ag, *pg, prompts_per_group=kpg), y), kpg
 
 
+@pytest.mark.parametrize("K,kpg", [(5, 2), (1, 0)])                  # a ragged last prompt group; one prompt
+def test_baseline_multi_op_equals_single_per_prompt(K, kpg):
+    """The two forward kernels share their reduce product and repeat one chain: at B = 1 every prompt's mask is the single-prompt
+    launch's, bit for bit."""
+    from egm_unet_amd.clip import ops as O
+    g, rd, rd2 = 3, 64, 128
+    gen = torch.Generator().manual_seed(7 + K)
+    xg = torch.randn(1, 1 + g * g, 768, generator=gen).to(DEV).bfloat16()
+    mg, ag = (1.0 + 0.3 * torch.randn(K, rd, generator=gen)).to(DEV).bfloat16(), (0.2 * torch.randn(K, rd, generator=gen)).to(DEV).bfloat16()
+    pg = [p.to(DEV) for p in head_params(rd, rd2, 5)]
+    y = O.baseline_head_multi(xg, mg, ag, *pg, prompts_per_group=kpg)
+    assert y.shape == (1, K, 16 * g, 16 * g)
+    for k in range(K):
+        assert torch.equal(y[:, k:k + 1], O.baseline_head(xg, mg[k:k + 1], ag[k:k + 1], *pg)), k
+
+
 # ---- models ---------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def base():
