@@ -830,6 +830,44 @@ int egm_tile_blend_f32(const float* tiles, int N, int C, int H, int W, const int
                        const float* wy_dev, const float* wx_dev, const unsigned char* lut, float* logits_out, unsigned char* mask_out,
                        egm_stream_t s);
 
+/* ---- Test-time augmentation: flip and multi-scale views made and merged on the device (csrc/tta.hip) -------------------
+ * An axis resized from n_in to n_out pixels (bilinear, align_corners=False, no antialias) is two DEVICE tables made on the host in
+ * integers (egm_unet_amd.tta.resize_axis): idx int32 [n_out][2] = the two source pixels (i0, i1) of output pixel d, and l1 fp32 [n_out],
+ * the weight of i1; the weight of i0 is l0 = 1 - l1 (one fp32 subtraction on the device).  The device never computes a coordinate.
+ * With a = A[r(iy0)][c(ix0)], b = A[r(iy0)][c(ix1)], c = A[r(iy1)][c(ix0)], d = A[r(iy1)][c(ix1)] the sample is
+ *     top = lx0 * a + lx1 * b,  bot = lx0 * c + lx1 * d,  val = ly0 * top + ly1 * bot,
+ * every multiply, add and subtract one fp32 rounding, none contracted into an FMA, so a float32 restatement gives the same bits.
+ * A flip code's bit 0 mirrors the columns, bit 1 the rows.
+ * egm_tta_views_f32: src fp32 [N][C][H][W] -> dst fp32 [F*N][C][h][w], the F flipped views of ONE scale; view f of image n at batch
+ *   index f*N + n.  dst[f*N + n][c][y][x] = the sample of src[n][c] at row ry = (flips[f] & 2 ? h-1-y : y) of yi_dev [h][2] / yl_dev [h]
+ *   and column cx = (flips[f] & 1 ? w-1-x : x) of xi_dev [w][2] / xl_dev [w] (here r and c are the identity: the mirror is in which
+ *   table row a pixel reads).  flips_dev: int32 [F].  ONE launch whatever N and F are; the taps are gathers (dword loads).
+ * egm_tta_merge_f32: views_dev: DEVICE table of V egm_tta_view, each a view's fp32 [N][C][h][w] tensor, its size, its flip code and the
+ *   four tables from (h, w) to (H, W): yi [H][2], yl [H], xi [W][2], xl [W]; r(k) = h-1-k for a rows flip, c(k) = w-1-k for a columns
+ *   flip.  -> logits_out fp32 [N][C][H][W] and / or mask_out uint8 [N][H][W] (either may be NULL, not both).
+ *   mode 0 (mean): acc = 0; acc = acc + sample_v for v ascending; out = acc / (float)V, correctly rounded.  Bit-reproducible.
+ *   mode 1 (prob): per view and pixel m = max_c sample_c, e_c = expf(sample_c - m) (the accurate expf), z = the sum of e_c in ascending
+ *     c, acc_c = acc_c + e_c / z; out_c = acc_c / (float)V.  The samples of every class stay in registers: C <= 8.
+ *   mask = lut[argmax_c out], ties to the lowest class as egm_argmax_u8; lut NULL: the index itself.  ONE launch whatever N and V are,
+ *   no atomics; the mask needs no merged tensor in memory.
+ * Every index read from a table is clamped into its tensor before it addresses memory, and a flip code is read & 3, so a wrong table
+ *   gives wrong pixels, never an access outside [N][C][h][w] as the call (the descriptor) states it.
+ * Limits: H, W, h, w <= 32767, V <= 4096, C <= 256 when a mask is asked for, C <= 8 in mode 1; any alignment of every buffer (16-byte
+ *   stores where the row length is a multiple of 4 and the output's base is aligned; tables int32 / fp32 aligned).  Bad scalars and
+ *   null pointers return EGM_ERR_ARG with a message before any launch.  Nothing waits for the device; capturable on one stream. */
+typedef struct egm_tta_view {
+    const float* logits;        /* fp32 [N][C][h][w] */
+    const int* yi;              /* int32 [H][2] */
+    const float* yl;            /* fp32 [H] */
+    const int* xi;              /* int32 [W][2] */
+    const float* xl;            /* fp32 [W] */
+    int h, w, flip, pad;
+} egm_tta_view;                 /* 56 bytes */
+int egm_tta_views_f32(const float* src, int N, int C, int H, int W, int h, int w, const int* yi_dev, const float* yl_dev,
+                      const int* xi_dev, const float* xl_dev, const int* flips_dev, int F, float* dst, egm_stream_t s);
+int egm_tta_merge_f32(const egm_tta_view* views_dev, int V, int N, int C, int H, int W, int mode, const unsigned char* lut,
+                      float* logits_out, unsigned char* mask_out, egm_stream_t s);
+
 /* ---- batched training data path: B ragged photos with masks -> the batch a train step reads (train.py:14-33, my_dataset.py:118-132)
  * egm_train_batch_u8: for every image b what egm_resample_u8 (axis 1, then axis 0), egm_gather_u8 and egm_augment_u8 compute one
  *   after the other, written into slot b of out_img_bchw fp32 [B][3][slot_h][slot_w] and out_target_bhw int64 [B][slot_h][slot_w]: per
