@@ -167,6 +167,10 @@ __global__ void mca_gates_fwd_kernel(const float* __restrict__ sums, GateParams 
     }
 }
 // dG [N][L][2] (slot 0 = sum over the slice of dx_out*x) -> coef [N][L][2] (A, B), dwts [3][2], dks [3][8]; dz scratch [N][L]
+// sd == 0 (a dead channel behind a ReLU; any slice whose variance cancels exactly or is clamped from below zero): B = 0, the gradient
+// through the standard deviation is dropped instead of the 0 / 0 = NaN of (x - mean) / ((cnt - 1) sd) -- the value torch's std backward
+// masks to as well.  A constant non-zero slice may instead come out with sd = rounding noise (~ |x| sqrt(2^-24)); B then stays O(1) and
+// A + B x equals the sd == 0 limit to ~1e-7 of dx, so there is no second guard (tests/mca_oracle.py: gates_bwd, tests/test_gpu_mca.py).
 // LDS_IN: dz, o and the (mean, std) pairs of all entries are staged in LDS (dynamic, 4 * total floats) -- the loop below reads up to
 // 7 + 7 + 2 of them per entry, and from global memory each is an exposed round trip in this one-workgroup kernel (25 us per launch).
 template <bool LDS_IN>
@@ -239,6 +243,19 @@ __global__ void mca_gates_bwd_kernel(const float* __restrict__ dG, const float* 
 }
 
 // ---- x_out = x * (g_h + g_w + g_c)/3 -------------------------------------------------------------------------------
+// One element of x_out.  bf16 storage: the float32 product x * ((g_h + g_w + g_c) * inv); its three float32 roundings are 2^-16 of the
+// bf16 ulp the store rounds to.  float32 storage (the parity path): those three roundings in front of the final one put the result up
+// to 3.7 float32 ulps from the exact product (measured 2.9), so there the factor is formed in double and rounded ONCE: within half a
+// float32 ulp of x (g_h + g_w + g_c) / n.  inv is 1 / (number of gates), 1/3.f or 0.5f; its exact value is recovered from the count.
+template <typename T>
+__device__ __forceinline__ float mca_xout_elem(float x, float gh, float gw, float gc, float inv) {
+    if constexpr (sizeof(T) == 4) {
+        const double n = rint(1.0 / (double)inv);
+        return (float)((double)x * (((double)gh + (double)gw + (double)gc) / n));
+    } else {
+        return x * (((gh + gw) + gc) * inv);
+    }
+}
 template <typename T>
 __global__ void mca_xout_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gates, T* __restrict__ xo, int ldo, int N, int H,
                                 int W, int C, float inv) {
@@ -248,11 +265,11 @@ __global__ void mca_xout_kernel(const T* __restrict__ x, int ldx, const float* _
         long long p; int cv; egm_divmod(i, ncv, p, cv);
         int w, h, n; egm_pix_nyx(p, H, W, n, h, w);
         const float* g = gates + (long long)n * L;
-        const float ghw = g[h] + g[H + w];
+        const float gh = g[h], gw = g[H + w];
         float v[8];
         load8(x + p * ldx + cv * 8, v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= (ghw + g[H + W + cv * 8 + j]) * inv;
+        for (int j = 0; j < 8; ++j) v[j] = mca_xout_elem<T>(v[j], gh, gw, g[H + W + cv * 8 + j], inv);
         store8(xo + p * ldo + cv * 8, v);
     }
 }
@@ -420,9 +437,9 @@ __global__ __launch_bounds__(256) void mca_fused_fwd_kernel(const T* __restrict_
             const long long p = img + (long long)gy * W + gx;
             if (sizeof(T) == 2) load8(reinterpret_cast<const T*>(&raw[k]), val);
             else load8(x + p * ldx + c0 + v * 8, val);
-            const float ghw = sgh[py] + sgw[px];
+            const float gh = sgh[py], gw = sgw[px];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) val[j] = to_f32(from_f32<T>(val[j] * ((ghw + gc8[j]) * inv)));
+            for (int j = 0; j < 8; ++j) val[j] = to_f32(from_f32<T>(mca_xout_elem<T>(val[j], gh, gw, gc8[j], inv)));
             if (xo != nullptr && py >= 2 && py < MF_TY + 2 && px >= 2 && px < MF_TX + 2) store8(xo + p * ldxo + c0 + v * 8, val);
         }
         store8_lds(sxo + pix * MF_CB + v * 8, val);
@@ -484,11 +501,11 @@ __global__ __launch_bounds__(256) void mca_fused_fwd_kernel(const T* __restrict_
                     if (t[j] < mn[j]) { mn[j] = t[j]; amn[j] = (r + 1) * 3 + (q + 1); }
                 }
             }
-        const float ghw = sgh[ly + 2] + sgw[lx + 2];
+        const float gh = sgh[ly + 2], gw = sgw[lx + 2];
         float o[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float sh = to_f32(from_f32<T>(to_f32(shv[k][j]) * ((ghw + gs8[j]) * inv)));
+            const float sh = to_f32(from_f32<T>(mca_xout_elem<T>(to_f32(shv[k][j]), gh, gw, gs8[j], inv)));
             const float o1 = to_f32(from_f32<T>(0.51f * c[j] + 0.2f * (mx[j] - mn[j]) + 0.1f * sh));
             o[j] = o1 + 0.2f * s2[j] * (1.f / 9.f);
         }
