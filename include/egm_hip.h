@@ -715,6 +715,28 @@ int egm_ensemble_alpha_hist_u8(const float* clip_logits, const float* unet_logit
                                const unsigned char* label_cls, const float* alphas, int na, int N, int C, int hc, int wc, int H, int W,
                                int Hl, int Wl, const int* ybeg, const int* xbeg, unsigned long long* hist, egm_stream_t s);
 
+/* ---- threshold-swept scores of binary logits (csrc/sweep.hip) ---------------------------------------------------------
+ * scores: fp32.  C == 1: one map per sample, [N][HW] (c_pos, c_neg ignored).  C >= 2: an NCHW tensor [N][C][HW]; a pixel's score is
+ * the fp32 difference x[n][c_pos] - x[n][c_neg] (0 <= c_pos != c_neg < C).  Samples are independent and may start at any 4-byte offset
+ * (odd HW); 1 <= N <= 65535 (the grid's y), 1 <= HW <= 2^40, otherwise EGM_ERR_ARG.
+ * egm_sweep_hist: hist[n][g][b] += 1 for every kept pixel, b = #{i : score > cuts[i]} by fp32 comparison alone (NaN: bin 0), g its truth.
+ *   cuts: T floats, strictly ascending, no NaN, the last one +inf (so b <= T - 1), 2 <= T <= 256.  They are given twice: cuts_host in
+ *   HOST memory is what the launcher checks before the launch, cuts_dev in DEVICE memory holds the same T floats and is what the kernel
+ *   reads (once per workgroup, into LDS), so a captured launch carries no table in its arguments.
+ *   target: target_f32 == 0: uint8 [N][HW] through target_cls (256 bytes of DEVICE memory: 0 = negative, 1 = positive, anything else
+ *   drops the pixel); target_f32 != 0: fp32 [N][HW], > 0.5 is positive, anything else (NaN included) negative, target_cls may be NULL.
+ *   hist: uint64 [N][2][T], caller-zeroed, accumulated across calls.  One launch, one workgroup per egm_sweep_chunk() pixels of a
+ *   sample; 32-bit partial counts on chip are bounded by that chunk, so no size can wrap them; at most one 64-bit atomic per non-zero
+ *   cell and workgroup.  Integer adds: the result does not depend on scheduling.
+ * egm_score_mask_u8: out[n][i] = score > cut ? v_fg : v_bg (uint8 [N][HW], any alignment); cut may be +-inf, not NaN; v_* in 0..255.
+ * Both launch on s, allocate nothing, wait for nothing (capturable), and check their arguments before the launch. */
+long long egm_sweep_chunk(void);
+int egm_sweep_hist(const float* scores, int N, int C, int c_pos, int c_neg, long long HW, const void* target, int target_f32,
+                   const unsigned char* target_cls, const float* cuts_host, const float* cuts_dev, int T, unsigned long long* hist,
+                   egm_stream_t s);
+int egm_score_mask_u8(const float* scores, int N, int C, int c_pos, int c_neg, long long HW, float cut, int v_bg, int v_fg,
+                      unsigned char* out, egm_stream_t s);
+
 /* ---- connected components of uint8 class maps and the mask clean-up on them (csrc/ccl.hip) -------------------------
  * cls: uint8 [N][H][W], 0 = background; images are independent.  Two pixels are joined when they hold the same byte and are neighbours:
  * `connectivity` (8 or 4) for foreground bytes, the dual (4 or 8) for background.  Any H, W >= 1 and any alignment; H*W <= 2^30,
