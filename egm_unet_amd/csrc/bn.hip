@@ -553,14 +553,16 @@ extern "C" int egm_bn_multi(int dtype, int which, const egm_bn_desc* descs, int 
     BnMulti m;
     const int grid = multi_build(descs, n, which, &m);
     EGM_REQUIRE(grid > 0, "bn_multi: bad descriptors (n=%d, 1..%d tensors, C %% 8 == 0, C <= 1024)", n, EGM_BN_MULTI_MAX);
+    // every activation tensor a pass reads or writes: what EGM_REQ_VEC asks of the single-tensor entry points (16-byte vectors)
+    auto vec = [](const void* p, int ld, int C) { return p != nullptr && egm_aligned16(p) && ld >= C && ld % 8 == 0; };
     for (int i = 0; i < n; ++i) {
         const egm_bn_desc& d = descs[i];
         switch (which) {
             case EGM_BN_MULTI_FINALIZE: EGM_REQUIRE(d.stats && d.ntiles > 0 && d.C_real > 0 && d.C_real <= d.C, "bn_multi finalize: bad entry %d", i); break;
-            case EGM_BN_MULTI_FWD: EGM_REQUIRE(d.y && d.z && egm_aligned16(d.y) && egm_aligned16(d.z) && d.ldy >= d.C && d.ldz >= d.C, "bn_multi fwd: bad entry %d", i); break;
-            case EGM_BN_MULTI_BWD_REDUCE: EGM_REQUIRE(d.dz && d.y && d.partials && egm_aligned16(d.dz) && d.lddz >= d.C && d.ldy >= d.C, "bn_multi bwd reduce: bad entry %d", i); break;
+            case EGM_BN_MULTI_FWD: EGM_REQUIRE(vec(d.y, d.ldy, d.C) && vec(d.z, d.ldz, d.C), "bn_multi fwd: bad entry %d", i); break;
+            case EGM_BN_MULTI_BWD_REDUCE: EGM_REQUIRE(vec(d.dz, d.lddz, d.C) && vec(d.y, d.ldy, d.C) && d.partials, "bn_multi bwd reduce: bad entry %d", i); break;
             case EGM_BN_MULTI_BWD_COEFS: EGM_REQUIRE(d.partials && d.nblocks > 0 && d.sums && d.cf4, "bn_multi bwd coefs: bad entry %d", i); break;
-            case EGM_BN_MULTI_BWD_APPLY: EGM_REQUIRE(d.dz && d.y && d.dy && d.sums && egm_aligned16(d.dy) && d.lddy >= d.C, "bn_multi bwd apply: bad entry %d", i); break;
+            case EGM_BN_MULTI_BWD_APPLY: EGM_REQUIRE(vec(d.dz, d.lddz, d.C) && vec(d.y, d.ldy, d.C) && vec(d.dy, d.lddy, d.C) && d.sums, "bn_multi bwd apply: bad entry %d", i); break;
             default: EGM_FAIL(EGM_ERR_ARG, "bn_multi: unknown pass %d", which);
         }
     }
