@@ -2,5 +2,6 @@
 nn.Module / train_utils interface.  All arithmetic runs in libegm_hip.so (include/egm_hip.h); there is no CPU path."""
 from .unet import UNet  # noqa: F401
 from .egm_unet import GRFBUNet  # noqa: F401
+from . import prompts  # noqa: F401
 
-__all__ = ["UNet", "GRFBUNet"]
+__all__ = ["UNet", "GRFBUNet", "prompts"]

@@ -1037,6 +1037,30 @@ long long egm_film_fanout_bwd_workspace(int dtype, int B, int K, int L, int D);
 int egm_film_fanout_bwd(int dtype, const void* g, const void* r, const void* mul, void* dr, void* dmul, void* dadd, void* ws, int B, int K,
                         int L, int D, egm_stream_t s);
 
+/* ---- CLIPSeg visual prompts (csrc/vprompt.hip, egm_unet_amd/prompts.py) ------------------------------------------------
+ * The support image of a one-shot query from a decoded photo and its mask.  fp32, a fixed evaluation order with one rounding per
+ * operation (tests/vprompt_oracle.py restates it); no allocation, no synchronisation with the host; K images per launch; S in 8 .. 8192.
+ * egm_vprompt_mask_f32: uint8 masks [K][H][W] -> coverage m [K][S][S] in [0, 1], the separable filter of data.float_filter_tables
+ *   (bounds int32 [S][2], weights fp32 [S][ksize] per axis, at most 64 taps) on the 0/1 indicator, columns first; value v is object when
+ *   bit v of the 256-bit set lut8_host (8 words, host memory) is set.  tmp_khs: fp32 [K][H][S].  Two launches; the second also resets the
+ *   K box records box_k4 (int32 [K][4] = y0, y1, x0, x1 with exclusive ends) to the empty box {S, 0, S, 0}.
+ * egm_vprompt_blend_f32: x [K][3][S][S], m -> out [K][3][S][S] by mode 0 overlay, 1 highlight, 2 highlight2, 3 shape, 4 image_only,
+ *   5 image_black, 6 x*m + bg_fac * blur(x) * (1 - m) - sub; blur: the separable 15-tap filter taps15_host (host memory), rows first,
+ *   reflect-101 borders (blur == 0: blur(x) = x).  The same launch grows box_k4[k] to the extents of m > 0 with vector atomics, so
+ *   egm_vprompt_mask_f32 has to run before it on the stream.  One launch.
+ * egm_vprompt_crop_f32: the square window around box_k4[k] widened by cnum / 1024 of its side per side (the whole image for an empty
+ *   box), resampled to S x S bilinearly from integer taps; pixels outside the image read 0.  Not in place.  One launch.
+ * egm_cond_mix_f32: out[g][:] = w * text[g][:] + (1 - w) * mean(vis[group_off[g] .. group_off[g + 1]][:]), the mean a left-to-right sum
+ *   divided once; text_gd == NULL: the mean alone.  vis [K][D], group_off int32 [G + 1] on the device, ascending from 0 to K. */
+int egm_vprompt_mask_f32(const void* masks_khw, int K, int H, int W, float* m_kss, int S, const int* xbounds, const float* xweights,
+                         int xksize, const int* ybounds, const float* yweights, int yksize, const unsigned int* lut8_host, float* tmp_khs,
+                         int* box_k4, egm_stream_t s);
+int egm_vprompt_blend_f32(const float* x_k3ss, const float* m_kss, float* out_k3ss, int* box_k4, int K, int S, int mode,
+                          const float* taps15_host, int blur, float bg_fac, float sub, egm_stream_t s);
+int egm_vprompt_crop_f32(const float* src_k3ss, const int* box_k4, float* out_k3ss, int K, int S, int cnum, egm_stream_t s);
+int egm_cond_mix_f32(float* out_gd, const float* vis_kd, const int* group_off, const float* text_gd, float w, int G, int K, int D,
+                     egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
