@@ -7,9 +7,9 @@
 // coordinate.  The arithmetic of a sample is fixed so that a numpy float32 restatement gives the same bits (tests/tta_oracle.py):
 //   l0 = 1 - l1,  top = lx0 * a + lx1 * b,  bot = lx0 * c + lx1 * d,  val = ly0 * top + ly1 * bot
 // one rounding per operation, no contraction into an FMA; the mean is acc = acc + val in ascending v and one correctly rounded division.
-//   shape   a lane owns kLanePix consecutive output pixels of one row, a wave kCols columns of ONE row, a workgroup kRows rows: the row
-//           taps (and the view descriptor) are wave-uniform, the column taps differ per lane.  Both kernels are gathers: no atomics,
-//           no lane depends on another.  In the merge's mean mode the classes are the outermost loop with a running best, so C costs
+//   shape   a lane owns kStripLanePix consecutive output pixels of one row, a wave kStripCols columns of ONE row, a workgroup kStripRows
+//           rows: the row taps (and the view descriptor) are wave-uniform, the column taps differ per lane.  Both kernels are gathers: no
+//           atomics, no lane depends on another.  In the merge's mean mode the classes are the outermost loop with a running best, so C costs
 //           no registers; in prob mode a view's samples of every class stay in registers (kProbMaxC).
 //   memory  taps are gathers (dword loads; at scale 1 consecutive lanes read consecutive addresses); the outputs leave as 16-byte
 //           non-temporal stores where the row length is a multiple of 4 and the base is aligned (common.h, EGM_STORE_MODE), else as
@@ -17,21 +17,18 @@
 // Every index read from a table is clamped into [0, side - 1] of the tensor it addresses and a flip code is read & 3, so the reads
 // stay inside [N][C][h][w] (as the call or the descriptor states it) whatever the tables hold.
 #include <math.h>
-#include "common.h"
+#include "strip_out.h"
 
 // No multiply of this file may be fused with the add behind it (as csrc/tiles.hip: the pragma governs the operators written below
-// it; the __fmul_rn / __fadd_rn wrappers are plain operators inside a header compiled under the default mode, and were fused).
+// it; the __fmul_rn / __fadd_rn wrappers are plain operators inside a header compiled under the default mode, and were fused).  So
+// strip_out.h, the frame shared with tiles.hip (the lane's pixels, the running argmax, the stores, the entry points' geometry), holds
+// no arithmetic on samples: the taps, acc + val, the softmax and acc / fV stay here, below the pragma.
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kRows = 4;                               // rows per workgroup, one per wave (tests/test_gpu_tta.py restates these)
-constexpr int kLanePix = 4;                            // consecutive pixels per lane
-constexpr int kCols = 64 * kLanePix;                   // columns per wave
-constexpr int kTtaMaxSide = 32767;                     // a tap weight's numerator and denominator are exact in float32
-constexpr int kTtaMaxC = 256;                          // a class index fits the mask's byte
 constexpr int kTtaMaxV = 4096;
-constexpr int kProbMaxC = 8;                           // prob mode: acc and the samples, kProbMaxC x kLanePix registers each
+constexpr int kProbMaxC = 8;                           // prob mode: acc and the samples, kProbMaxC x kStripLanePix registers each
 
 // the two taps and weights of one axis for output pixel p, the indices clamped into [0, side - 1] and mirrored for a flipped axis
 struct Taps { int i0, i1; float l0, l1; };
@@ -54,24 +51,12 @@ __device__ __forceinline__ float bilinear(const float* __restrict__ r0, const fl
     return vt + vb;
 }
 
-__device__ __forceinline__ void store_row4(float* o, const float (&out)[kLanePix], int x, int W, int vec) {
-    if (vec) {                                                 // W % 4 == 0 and the base aligned: the lane's four pixels are inside the row
-        egm_u32x4 a;
-        a.x = __float_as_uint(out[0]); a.y = __float_as_uint(out[1]); a.z = __float_as_uint(out[2]); a.w = __float_as_uint(out[3]);
-        egm_store16_as<EGM_STORE_MODE>(o, a);
-    } else {
-#pragma unroll
-        for (int e = 0; e < kLanePix; ++e)
-            if (x + e < W) o[e] = out[e];
-    }
-}
-
 __global__ __launch_bounds__(256) void tta_views_kernel(const float* __restrict__ src, int N, int C, int H, int W, int h, int w,
                                                         const int* __restrict__ yi, const float* __restrict__ yl,
                                                         const int* __restrict__ xi, const float* __restrict__ xl,
                                                         const int* __restrict__ flips, long long rows, float* __restrict__ dst, int vec) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long row = blockIdx.x * (long long)kRows + wave;        // row y of class c of view f of image n: dst[f * N + n][c][y]
+    const long long row = blockIdx.x * (long long)kStripRows + wave;   // row y of class c of view f of image n: dst[f * N + n][c][y]
     if (row >= rows) return;                                   // (a whole wave; the kernel has no barrier)
     long long q, k, f;
     int y, c, n;
@@ -84,10 +69,10 @@ __global__ __launch_bounds__(256) void tta_views_kernel(const float* __restrict_
     const float* r0 = plane + (long long)ty.i0 * W;
     const float* r1 = plane + (long long)ty.i1 * W;
     float* d = dst + row * w;
-    for (int x = lane * kLanePix; x < w; x += kCols) {
-        float out[kLanePix];
+    for (int x = lane * kStripLanePix; x < w; x += kStripCols) {
+        float out[kStripLanePix];
 #pragma unroll
-        for (int e = 0; e < kLanePix; ++e) {
+        for (int e = 0; e < kStripLanePix; ++e) {
             out[e] = 0.f;
             if (x + e < w) {
                 const Taps tx = load_taps(xi, xl, (flip & 1) ? w - 1 - (x + e) : x + e, W, false);
@@ -103,21 +88,14 @@ __global__ __launch_bounds__(256) void tta_merge_mean_kernel(const egm_tta_view*
                                                              const unsigned char* __restrict__ lut, float* __restrict__ logits,
                                                              unsigned char* __restrict__ mask, int nrg, int ncg, int vec_logits,
                                                              int vec_mask) {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b = blockIdx.x;
-    const int cg = b % ncg, rn = b / ncg, rg = rn % nrg, n = rn / nrg;
-    const int y = rg * kRows + wave;
-    const int x = cg * kCols + lane * kLanePix;
-    if (y >= H || x >= W) return;                              // (the kernel has no barrier)
+    const auto [n, y, x, outside] = strip_pos(nrg, ncg, H, W);
+    if (outside) return;
     const float fV = (float)V;
-    float best[kLanePix];
-    int arg[kLanePix];
-#pragma unroll
-    for (int e = 0; e < kLanePix; ++e) { best[e] = 0.f; arg[e] = 0; }
+    StripArgmax top;
     for (int c = 0; c < C; ++c) {
-        float acc[kLanePix];
+        float acc[kStripLanePix];
 #pragma unroll
-        for (int e = 0; e < kLanePix; ++e) acc[e] = 0.f;
+        for (int e = 0; e < kStripLanePix; ++e) acc[e] = 0.f;
         for (int v = 0; v < V; ++v) {
             const egm_tta_view& d = views[v];                  // wave-uniform
             const int h = max(d.h, 1), w = max(d.w, 1), flip = d.flip & 3;
@@ -126,7 +104,7 @@ __global__ __launch_bounds__(256) void tta_merge_mean_kernel(const egm_tta_view*
             const float* r0 = plane + (long long)ty.i0 * w;
             const float* r1 = plane + (long long)ty.i1 * w;
 #pragma unroll
-            for (int e = 0; e < kLanePix; ++e) {
+            for (int e = 0; e < kStripLanePix; ++e) {
                 if (x + e < W) {
                     const Taps tx = load_taps(d.xi, d.xl, x + e, w, flip & 1);
                     const float val = bilinear(r0, r1, ty, tx);
@@ -134,27 +112,15 @@ __global__ __launch_bounds__(256) void tta_merge_mean_kernel(const egm_tta_view*
                 }
             }
         }
-        float out[kLanePix];
+        float out[kStripLanePix];
 #pragma unroll
-        for (int e = 0; e < kLanePix; ++e) {
+        for (int e = 0; e < kStripLanePix; ++e) {
             out[e] = acc[e] / fV;                               // correctly rounded: hipcc's default for fp32 division
-            if (c == 0 || out[e] > best[e]) { best[e] = out[e]; arg[e] = c; }      // ties to the lowest class, as egm_argmax_u8
+            top.take(c, e, out[e]);
         }
         if (logits) store_row4(logits + (((long long)n * C + c) * H + y) * W + x, out, x, W, vec_logits);
     }
-    if (mask) {
-        unsigned char* o = mask + ((long long)n * H + y) * W + x;
-        unsigned int m[kLanePix];
-#pragma unroll
-        for (int e = 0; e < kLanePix; ++e) m[e] = lut ? lut[arg[e]] : (unsigned int)arg[e];
-        if (vec_mask) {
-            *reinterpret_cast<unsigned int*>(o) = m[0] | (m[1] << 8) | (m[2] << 16) | (m[3] << 24);
-        } else {
-#pragma unroll
-            for (int e = 0; e < kLanePix; ++e)
-                if (x + e < W) o[e] = (unsigned char)m[e];
-        }
-    }
+    if (mask) top.store_mask(mask + ((long long)n * H + y) * W + x, lut, x, W, vec_mask);
 }
 
 // prob: out_c = (sum_v softmax_c(sample_v)) / V.  The views are the outermost loop; acc and one view's samples stay in registers, every
@@ -163,26 +129,22 @@ __global__ __launch_bounds__(256) void tta_merge_prob_kernel(const egm_tta_view*
                                                              const unsigned char* __restrict__ lut, float* __restrict__ logits,
                                                              unsigned char* __restrict__ mask, int nrg, int ncg, int vec_logits,
                                                              int vec_mask) {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b = blockIdx.x;
-    const int cg = b % ncg, rn = b / ncg, rg = rn % nrg, n = rn / nrg;
-    const int y = rg * kRows + wave;
-    const int x = cg * kCols + lane * kLanePix;
-    if (y >= H || x >= W) return;                              // (the kernel has no barrier)
+    const auto [n, y, x, outside] = strip_pos(nrg, ncg, H, W);
+    if (outside) return;
     const float fV = (float)V;
-    float acc[kProbMaxC][kLanePix];
+    float acc[kProbMaxC][kStripLanePix];
 #pragma unroll
     for (int c = 0; c < kProbMaxC; ++c)
 #pragma unroll
-        for (int e = 0; e < kLanePix; ++e) acc[c][e] = 0.f;
+        for (int e = 0; e < kStripLanePix; ++e) acc[c][e] = 0.f;
     for (int v = 0; v < V; ++v) {
         const egm_tta_view& d = views[v];                      // wave-uniform
         const int h = max(d.h, 1), w = max(d.w, 1), flip = d.flip & 3;
         const Taps ty = load_taps(d.yi, d.yl, y, h, flip & 2);
-        Taps tx[kLanePix];
+        Taps tx[kStripLanePix];
 #pragma unroll
-        for (int e = 0; e < kLanePix; ++e) tx[e] = load_taps(d.xi, d.xl, min(x + e, W - 1), w, flip & 1);
-        float s[kProbMaxC][kLanePix];
+        for (int e = 0; e < kStripLanePix; ++e) tx[e] = load_taps(d.xi, d.xl, min(x + e, W - 1), w, flip & 1);
+        float s[kProbMaxC][kStripLanePix];
 #pragma unroll
         for (int c = 0; c < kProbMaxC; ++c) {
             if (c < C) {
@@ -190,11 +152,11 @@ __global__ __launch_bounds__(256) void tta_merge_prob_kernel(const egm_tta_view*
                 const float* r0 = plane + (long long)ty.i0 * w;
                 const float* r1 = plane + (long long)ty.i1 * w;
 #pragma unroll
-                for (int e = 0; e < kLanePix; ++e) s[c][e] = bilinear(r0, r1, ty, tx[e]);
+                for (int e = 0; e < kStripLanePix; ++e) s[c][e] = bilinear(r0, r1, ty, tx[e]);
             }
         }
 #pragma unroll
-        for (int e = 0; e < kLanePix; ++e) {
+        for (int e = 0; e < kStripLanePix; ++e) {
             float m = s[0][e];
 #pragma unroll
             for (int c = 1; c < kProbMaxC; ++c)
@@ -216,35 +178,20 @@ __global__ __launch_bounds__(256) void tta_merge_prob_kernel(const egm_tta_view*
             }
         }
     }
-    float best[kLanePix];
-    int arg[kLanePix];
-#pragma unroll
-    for (int e = 0; e < kLanePix; ++e) { best[e] = 0.f; arg[e] = 0; }
+    StripArgmax top;
 #pragma unroll
     for (int c = 0; c < kProbMaxC; ++c) {
         if (c < C) {
-            float out[kLanePix];
+            float out[kStripLanePix];
 #pragma unroll
-            for (int e = 0; e < kLanePix; ++e) {
+            for (int e = 0; e < kStripLanePix; ++e) {
                 out[e] = acc[c][e] / fV;
-                if (c == 0 || out[e] > best[e]) { best[e] = out[e]; arg[e] = c; }
+                top.take(c, e, out[e]);
             }
             if (logits) store_row4(logits + (((long long)n * C + c) * H + y) * W + x, out, x, W, vec_logits);
         }
     }
-    if (mask) {
-        unsigned char* o = mask + ((long long)n * H + y) * W + x;
-        unsigned int m[kLanePix];
-#pragma unroll
-        for (int e = 0; e < kLanePix; ++e) m[e] = lut ? lut[arg[e]] : (unsigned int)arg[e];
-        if (vec_mask) {
-            *reinterpret_cast<unsigned int*>(o) = m[0] | (m[1] << 8) | (m[2] << 16) | (m[3] << 24);
-        } else {
-#pragma unroll
-            for (int e = 0; e < kLanePix; ++e)
-                if (x + e < W) o[e] = (unsigned char)m[e];
-        }
-    }
+    if (mask) top.store_mask(mask + ((long long)n * H + y) * W + x, lut, x, W, vec_mask);
 }
 
 }  // namespace
@@ -257,13 +204,13 @@ extern "C" int egm_tta_views_f32(const float* src, int N, int C, int H, int W, i
                 name);
     EGM_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "%s: bad shape N=%d C=%d H=%d W=%d", name, N, C, H, W);
     EGM_REQUIRE(h > 0 && w > 0 && F > 0, "%s: bad views: %d flips of %d x %d pixels", name, F, h, w);
-    EGM_REQUIRE(H <= kTtaMaxSide && W <= kTtaMaxSide && h <= kTtaMaxSide && w <= kTtaMaxSide,
-                "%s: %d x %d -> %d x %d pixels, at most %d rows and columns are supported", name, H, W, h, w, kTtaMaxSide);
+    EGM_REQUIRE(H <= kStripMaxSide && W <= kStripMaxSide && h <= kStripMaxSide && w <= kStripMaxSide,
+                "%s: %d x %d -> %d x %d pixels, at most %d rows and columns are supported", name, H, W, h, w, kStripMaxSide);
     const long long rows = (long long)F * N * C * h;
-    EGM_REQUIRE(rows < (1ll << 32), "%s: %lld rows in one call, fewer than 2^32 are supported", name, rows);
-    const int vec = (w % kLanePix == 0) && egm_aligned16(dst);
-    hipLaunchKernelGGL(tta_views_kernel, dim3((unsigned)((rows + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)s, src, N, C, H, W, h, w,
-                       yi_dev, yl_dev, xi_dev, xl_dev, flips_dev, rows, dst, vec);
+    StripRows g;
+    if (const int rc = strip_rows_check(name, rows, w, dst, &g); rc != EGM_OK) return rc;
+    hipLaunchKernelGGL(tta_views_kernel, dim3(g.groups), dim3(256), 0, (hipStream_t)s, src, N, C, H, W, h, w, yi_dev, yl_dev, xi_dev, xl_dev,
+                       flips_dev, rows, dst, g.vec);
     EGM_CHECK_LAUNCH("tta_views_f32");
     return EGM_OK;
 }
@@ -272,25 +219,14 @@ extern "C" int egm_tta_merge_f32(const egm_tta_view* views_dev, int V, int N, in
                                  float* logits_out, unsigned char* mask_out, egm_stream_t s) {
     const char* name = "tta_merge_f32";
     EGM_REQUIRE(views_dev, "%s: null pointer (the table of view descriptors is required)", name);
-    EGM_REQUIRE(logits_out || mask_out, "%s: null pointer (no output: logits_out and mask_out are both NULL)", name);
-    EGM_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "%s: bad shape N=%d C=%d H=%d W=%d", name, N, C, H, W);
+    StripGrid g;
+    if (const int rc = strip_check(name, N, C, H, W, logits_out, mask_out, &g); rc != EGM_OK) return rc;
     EGM_REQUIRE(V > 0 && V <= kTtaMaxV, "%s: %d views, between 1 and %d are supported", name, V, kTtaMaxV);
     EGM_REQUIRE(mode == 0 || mode == 1, "%s: bad mode %d (0 = mean of the samples, 1 = mean of their softmax probabilities)", name, mode);
-    EGM_REQUIRE(H <= kTtaMaxSide && W <= kTtaMaxSide, "%s: %d x %d pixels, at most %d rows and columns are supported", name, H, W, kTtaMaxSide);
-    EGM_REQUIRE(!mask_out || C <= kTtaMaxC, "%s: %d classes, a mask holds at most %d", name, C, kTtaMaxC);
     EGM_REQUIRE(mode == 0 || C <= kProbMaxC, "%s: %d classes, mode 1 (prob) keeps the samples in registers and holds at most %d", name, C,
                 kProbMaxC);
-    const int nrg = egm_cdiv(H, kRows), ncg = egm_cdiv(W, kCols);
-    const long long items = (long long)N * nrg * ncg;
-    EGM_REQUIRE(items < (1ll << 31), "%s: %lld workgroups of %d x %d pixels, fewer than 2^31 are supported", name, items, kRows, kCols);
-    const int vec_logits = logits_out && (W % kLanePix == 0) && egm_aligned16(logits_out);
-    const int vec_mask = mask_out && (W % kLanePix == 0) && (reinterpret_cast<uintptr_t>(mask_out) & 3) == 0;
-    if (mode == 0)
-        hipLaunchKernelGGL(tta_merge_mean_kernel, dim3((unsigned)items), dim3(256), 0, (hipStream_t)s, views_dev, V, C, H, W, lut, logits_out,
-                           mask_out, nrg, ncg, vec_logits, vec_mask);
-    else
-        hipLaunchKernelGGL(tta_merge_prob_kernel, dim3((unsigned)items), dim3(256), 0, (hipStream_t)s, views_dev, V, C, H, W, lut, logits_out,
-                           mask_out, nrg, ncg, vec_logits, vec_mask);
+    hipLaunchKernelGGL(mode == 0 ? tta_merge_mean_kernel : tta_merge_prob_kernel, dim3((unsigned)g.items), dim3(256), 0, (hipStream_t)s,
+                       views_dev, V, C, H, W, lut, logits_out, mask_out, g.nrg, g.ncg, g.vec_logits, g.vec_mask);
     EGM_CHECK_LAUNCH("tta_merge_f32");
     return EGM_OK;
 }

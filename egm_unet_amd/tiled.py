@@ -11,14 +11,12 @@ One captured graph at (batch, window, window) serves photos of every size, and m
 [T, C, h, w] buffer of their logits.  The plan (tile_starts, TilePlan) and the weights (tile_weights) are plain host code: importing
 this module and using them needs no GPU and no library.  gather_tiles and blend_tiles expose the two kernels of csrc/tiles.hip.
 """
-import collections
-import math
-
 import numpy as np
-import torch
+
+from . import _strips
+from ._strips import MAX_SIDE as _MAX_SIDE, check_input as _check_input
 
 WEIGHT_KINDS = ("constant", "gaussian")
-_MAX_SIDE = 32767                           # kTileMaxSide of csrc/tiles.hip
 _GAUSS_SIGMA = 0.125                        # of the window, MONAI's default sigma_scale
 _GAUSS_FLOOR = 1e-3
 
@@ -106,43 +104,21 @@ def tile_weights(kind, size):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the two kernels
-_PLAN_TABLES = 8                            # plans (and weight kinds) whose device tables are kept, least recently used first out
-_plan_tables = collections.OrderedDict()
+_plan_tables = _strips.LRU(8)               # plans (and weight kinds) whose device tables are kept, least recently used first out
 
 
 def _tables(plan, weight, device):
     """The plan's ys / xs (int32) and the weight profiles wy / wx (fp32; None without `weight`) on the device, uploaded once per plan
     through an ops.DeviceTable of their own (a caller's captured graph keeps reading them)."""
-    from . import ops
     if weight is not None and weight not in WEIGHT_KINDS:
         raise ValueError(f"weight: one of {WEIGHT_KINDS} expected, got {weight!r}")
-    key = (tuple(plan.ys), tuple(plan.xs), plan.h, plan.w, weight, str(device))
-    hit = _plan_tables.pop(key, None)
-    if hit is None:
+
+    def make():
         parts = [np.asarray(plan.ys, dtype=np.int32), np.asarray(plan.xs, dtype=np.int32)]
-        if weight is not None:
-            parts += [tile_weights(weight, plan.h), tile_weights(weight, plan.w)]
-        blob, offs = bytearray(), []
-        for p in parts:                                        # every table starts on a 16-byte boundary of the blob
-            blob += bytes(-len(blob) % 16)
-            offs.append(len(blob))
-            blob += p.tobytes()
-        hit = (ops.DeviceTable(), bytes(blob), offs, [p.size for p in parts])
-    _plan_tables[key] = hit
-    while len(_plan_tables) > _PLAN_TABLES:
-        _plan_tables.popitem(last=False)
-    table, blob, offs, sizes = hit
-    dev = table.get(blob, device)
-    views = [dev[o:o + 4 * n].view(torch.int32 if k < 2 else torch.float32) for k, (o, n) in enumerate(zip(offs, sizes))]
+        return _strips.PlanTables(parts + ([tile_weights(weight, plan.h), tile_weights(weight, plan.w)] if weight is not None else []))
+
+    views = _plan_tables.get((tuple(plan.ys), tuple(plan.xs), plan.h, plan.w, weight, str(device)), make).views(device)
     return views + [None] * (4 - len(views))
-
-
-def _check_input(x, who, what="the input"):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError(f"egm_unet_amd models run on the GPU only: move {what} (and the model) to cuda")
-    if x.dim() != 4 or x.dtype != torch.float32:
-        raise ValueError(f"{who}: a float32 tensor [N, C, H, W] expected, got {x.dtype} {tuple(x.shape)}")
-    return x.contiguous()
 
 
 def _check_plan(plan, who, N, H, W):
@@ -165,12 +141,7 @@ def gather_tiles(x, plan, t0=0, count=None, out=None):
     count = plan.T - t0 if count is None else int(count)
     if not 0 <= t0 < plan.T or count < 1:
         raise ValueError(f"gather_tiles: bad range: {count} tiles from tile {t0} of {plan.T}")
-    shape = (count, C, plan.h, plan.w)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif not (isinstance(out, torch.Tensor) and out.device == x.device and out.dtype == torch.float32 and tuple(out.shape) == shape
-              and out.is_contiguous()):
-        raise ValueError(f"gather_tiles: out must be a contiguous float32 tensor {list(shape)} on {x.device}")
+    out = _strips.check_out(out, (count, C, plan.h, plan.w), x.device, "gather_tiles")
     ys, xs, _, _ = _tables(plan, None, x.device)
     lib().call("egm_tile_gather_f32", ptr(x), N, C, H, W, ptr(ys), plan.ny, ptr(xs), plan.nx, plan.h, plan.w, t0, count, ptr(out), stream())
     return out
@@ -183,9 +154,7 @@ def blend_tiles(tiles, plan, weight="gaussian", lut=None, want="logits"):
     want: "logits" -> fp32 [N, C, H, W]; "mask" -> uint8 [N, H, W] = lut[argmax_c], ties to the lowest class, lut as for
     Predictor.predict_mask (no logits are written); "both" -> (logits, mask).  One launch, no host wait."""
     from ._lib import lib, ptr, require_gpu, stream
-    from .infer import lut256
-    if want not in ("logits", "mask", "both"):
-        raise ValueError(f"want: one of 'logits', 'mask', 'both' expected, got {want!r}")
+    _strips.check_want(want)
     tiles = _check_input(tiles, "blend_tiles", "the tiles")
     require_gpu()
     if not isinstance(plan, TilePlan) or tuple(tiles.shape[:1] + tiles.shape[2:]) != (plan.T, plan.h, plan.w):
@@ -194,18 +163,14 @@ def blend_tiles(tiles, plan, weight="gaussian", lut=None, want="logits"):
     _check_plan(plan, "blend_tiles", N, H, W)
     dev = tiles.device
     ys, xs, wy, wx = _tables(plan, weight, dev)
-    logits = torch.empty((N, C, H, W), dtype=torch.float32, device=dev) if want != "mask" else None
-    mask = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if want != "logits" else None
-    if mask is not None and C > 256:
-        raise ValueError(f"blend_tiles: {C} classes, a mask holds at most 256")
-    lt = lut256(lut, C, dev, "blend_tiles: lut") if mask is not None else None
+    logits, mask, lt = _strips.alloc_outputs(want, N, C, H, W, dev, lut, "blend_tiles")
     lib().call("egm_tile_blend_f32", ptr(tiles), N, C, H, W, ptr(ys), plan.ny, ptr(xs), plan.nx, plan.h, plan.w, ptr(wy), ptr(wx), ptr(lt),
                ptr(logits), ptr(mask), stream())
     return logits if want == "logits" else mask if want == "mask" else (logits, mask)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the predictor
-class TiledPredictor:
+class TiledPredictor(_strips.StripPredictor):
     """Sliding-window inference of a GRFBUNet / UNet: gather -> model -> blend per call, the model through an infer.Predictor(model,
     dtype, graph) of its own (self.predictor).
 
@@ -228,51 +193,29 @@ class TiledPredictor:
         self.window, self.overlap, self.stride, self.weight, self.batch = window, overlap, stride, weight, int(batch)
         self.predictor = Predictor(model, dtype=dtype, graph=graph)
         self.max_plans = max(1, int(max_plans))
-        self._buffers = collections.OrderedDict()    # (plan key, C, device) -> (chunk [B', Cin, h, w], logits [T, C, h, w])
+        self._buffers = _strips.PlanBuffers(self.max_plans)      # (plan key, "in" | "out", ...) -> (chunk [B', Cin, h, w],) or (logits [T, C, h, w],)
 
     def plan(self, N, H, W):
         """The TilePlan a batch of N images of H x W gets."""
         return TilePlan(N, H, W, self.window, self.stride, self.overlap)
 
-    def refresh(self):
-        """Predictor.refresh of the inner predictor (for callers that capture a call into a graph of their own)."""
-        self.predictor.refresh()
-
-    def _workspace(self, key, shapes, device):
-        bufs = self._buffers.pop(key, None)
-        if bufs is None:
-            bufs = tuple(torch.empty(s, dtype=torch.float32, device=device) for s in shapes)
-        self._buffers[key] = bufs
-        while len(self._buffers) > 2 * self.max_plans:                           # a chunk buffer and a logit buffer per plan
-            self._buffers.popitem(last=False)
-        return bufs
-
-    def _tile_logits(self, x):
+    def _parts(self, x):
         """-> (plan, [T, C, h, w] logits of every tile, in this predictor's buffer for the plan)."""
         x = _check_input(x, "TiledPredictor")
         N, Cin, H, W = x.shape
         plan = self.plan(N, H, W)
         _check_plan(plan, "TiledPredictor", N, H, W)
         B = min(self.batch, plan.T)
-        chunk, = self._workspace((plan.key, "in", Cin, B, str(x.device)), [(B, Cin, plan.h, plan.w)], x.device)
+        chunk, = self._buffers.get((plan.key, "in", Cin, B, str(x.device)), [(B, Cin, plan.h, plan.w)], x.device)
         logits = None
         for t0 in range(0, plan.T, B):
             out = self.predictor(gather_tiles(x, plan, t0, B, out=chunk))["out"]
             if logits is None:
                 C = out.shape[1]
-                logits, = self._workspace((plan.key, "out", C, str(x.device)), [(plan.T, C, plan.h, plan.w)], x.device)
+                logits, = self._buffers.get((plan.key, "out", C, str(x.device)), [(plan.T, C, plan.h, plan.w)], x.device)
             n = min(B, plan.T - t0)
             logits[t0:t0 + n].copy_(out[:n])                                    # before the next replay overwrites the static output
         return plan, logits
 
-    def __call__(self, x):
-        with torch.no_grad():
-            plan, logits = self._tile_logits(x)
-            return {"out": blend_tiles(logits, plan, self.weight)}
-
-    def predict_mask(self, x, lut=None):
-        """-> uint8 [N, H, W]: lut[argmax_c of the blended logits], ties to the lowest class, written by the blend kernel itself (the
-        blended logits never reach memory).  lut as for Predictor.predict_mask."""
-        with torch.no_grad():
-            plan, logits = self._tile_logits(x)
-            return blend_tiles(logits, plan, self.weight, lut=lut, want="mask")
+    def _combine(self, logits, plan, lut, want):
+        return blend_tiles(logits, plan, self.weight, lut=lut, want=want)

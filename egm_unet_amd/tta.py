@@ -13,17 +13,18 @@ Per scale one launch makes the batch of F * N views, one forward runs them, and 
 taps of every axis are made here IN INTEGERS and uploaded as tables; the device never computes a coordinate, and every multiply, add
 and subtract of a sample is one float32 rounding, so tests/tta_oracle.py gives the same bits.  make_views and merge_views expose the
 two kernels of csrc/tta.hip."""
-import collections
 import math
 import struct
 
 import numpy as np
 import torch
 
+from . import _strips
+from ._strips import MAX_SIDE as _MAX_SIDE, check_input as _check_input
+
 FLIPS = ("", "h", "v", "hv")                # the flip code of a view is the index: bit 0 mirrors the columns, bit 1 the rows
 MERGE_MODES = ("mean", "prob")
 PROB_MAX_CLASSES = 8                        # kProbMaxC of csrc/tta.hip: merge="prob" keeps a view's samples of every class in registers
-_MAX_SIDE = 32767                           # kTtaMaxSide of csrc/tta.hip: both operands of a tap weight's division are exact in float32
 _VIEW_DESC = struct.Struct("<5Q4i")         # egm_tta_view (include/egm_hip.h), 56 bytes
 
 
@@ -108,8 +109,7 @@ class TTAPlan:
 
 
 # ---------------------------------------------------------------------------------------------------------------- the two kernels
-_PLAN_TABLES = 8                            # plans whose device tables are kept, least recently used first out
-_plan_tables = collections.OrderedDict()
+_plan_tables = _strips.LRU(8)               # plans whose device tables are kept, least recently used first out
 
 
 def _axis_tables(n_in, n_out):
@@ -121,34 +121,16 @@ def _tables(plan, device):
     """The plan's tables on the device, uploaded once per plan through an ops.DeviceTable of their own (a caller's captured graph keeps
     reading them) -> (flip codes int32 [F], per scale the four axis tables (yi [h][2], yl [h], xi [w][2], xl [w]) of the views, per
     scale the four (yi [H][2], yl [H], xi [W][2], xl [W]) of the merge, the DeviceTable of the merge's view descriptors)."""
-    from . import ops
-    key = (plan.key, str(device))
-    hit = _plan_tables.pop(key, None)
-    if hit is None:
+    def make():
+        from . import ops
         parts = [np.asarray(plan.flip_codes, dtype=np.int32)]
         for h, w in plan.sizes:
             parts += _axis_tables(plan.H, h) + _axis_tables(plan.W, w) + _axis_tables(h, plan.H) + _axis_tables(w, plan.W)
-        blob, offs = bytearray(), []
-        for p in parts:                                        # every table starts on a 16-byte boundary of the blob
-            blob += bytes(-len(blob) % 16)
-            offs.append(len(blob))
-            blob += p.tobytes()
-        hit = (ops.DeviceTable(), bytes(blob), offs, [(p.size, p.dtype) for p in parts], ops.DeviceTable())
-    _plan_tables[key] = hit
-    while len(_plan_tables) > _PLAN_TABLES:
-        _plan_tables.popitem(last=False)
-    table, blob, offs, kinds, desc = hit
-    dev = table.get(blob, device)
-    t = [dev[o:o + 4 * n].view(torch.int32 if dt == np.int32 else torch.float32) for o, (n, dt) in zip(offs, kinds)]
+        return _strips.PlanTables(parts), ops.DeviceTable()
+
+    tables, desc = _plan_tables.get((plan.key, str(device)), make)
+    t = tables.views(device)
     return t[0], [t[1 + 8 * s:5 + 8 * s] for s in range(plan.S)], [t[5 + 8 * s:9 + 8 * s] for s in range(plan.S)], desc
-
-
-def _check_input(x, who, what="the input"):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError(f"egm_unet_amd models run on the GPU only: move {what} (and the model) to cuda")
-    if x.dim() != 4 or x.dtype != torch.float32:
-        raise ValueError(f"{who}: a float32 tensor [N, C, H, W] expected, got {x.dtype} {tuple(x.shape)}")
-    return x.contiguous()
 
 
 def make_views(x, plan, s, out=None):
@@ -167,12 +149,7 @@ def make_views(x, plan, s, out=None):
     if not 0 <= s < plan.S:
         raise ValueError(f"make_views: bad scale number {s}: the plan has {plan.S}")
     h, w = plan.sizes[s]
-    shape = (plan.F * N, C, h, w)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif not (isinstance(out, torch.Tensor) and out.device == x.device and out.dtype == torch.float32 and tuple(out.shape) == shape
-              and out.is_contiguous()):
-        raise ValueError(f"make_views: out must be a contiguous float32 tensor {list(shape)} on {x.device}")
+    out = _strips.check_out(out, (plan.F * N, C, h, w), x.device, "make_views")
     flips, view_axes, _, _ = _tables(plan, x.device)
     yi, yl, xi, xl = view_axes[s]
     lib().call("egm_tta_views_f32", ptr(x), N, C, H, W, h, w, ptr(yi), ptr(yl), ptr(xi), ptr(xl), ptr(flips), plan.F, ptr(out), stream())
@@ -190,9 +167,7 @@ def merge_views(views, plan, mode="mean", lut=None, want="logits"):
     lut[argmax_c out], ties to the lowest class, lut as for Predictor.predict_mask, at most 256 classes (the merged tensor is not
     written); "both" -> (logits, mask).  One launch whatever N and V are, no host wait."""
     from ._lib import lib, ptr, require_gpu, stream
-    from .infer import lut256
-    if want not in ("logits", "mask", "both"):
-        raise ValueError(f"want: one of 'logits', 'mask', 'both' expected, got {want!r}")
+    _strips.check_want(want)
     if mode not in MERGE_MODES:
         raise ValueError(f"merge: one of {MERGE_MODES} expected, got {mode!r}")
     if not isinstance(views, (list, tuple)) or not views:
@@ -208,11 +183,7 @@ def merge_views(views, plan, mode="mean", lut=None, want="logits"):
             raise ValueError(f"merge_views: view {v} {tuple(t.shape)} on {t.device} does not fit the plan {plan!r} with {C} classes on {dev}")
     if mode == "prob" and C > PROB_MAX_CLASSES:
         raise ValueError(f"merge_views: {C} classes, merge='prob' holds at most {PROB_MAX_CLASSES}")
-    logits = torch.empty((N, C, H, W), dtype=torch.float32, device=dev) if want != "mask" else None
-    mask = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if want != "logits" else None
-    if mask is not None and C > 256:
-        raise ValueError(f"merge_views: {C} classes, a mask holds at most 256")
-    lt = lut256(lut, C, dev, "merge_views: lut") if mask is not None else None
+    logits, mask, lt = _strips.alloc_outputs(want, N, C, H, W, dev, lut, "merge_views")
     _, _, merge_axes, desc = _tables(plan, dev)
     blob = bytearray()
     for v, t in enumerate(views):
@@ -226,7 +197,7 @@ def merge_views(views, plan, mode="mean", lut=None, want="logits"):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the predictor
-class TTAPredictor:
+class TTAPredictor(_strips.StripPredictor):
     """Flip and multi-scale test-time augmentation around a predictor: make_views -> forward at batch F * N -> (next scale) -> one
     merge_views per call.
 
@@ -253,34 +224,19 @@ class TTAPredictor:
         else:
             raise TypeError("TTAPredictor: a model, or a predictor with __call__(x) -> {'out': ...}, expected")
         self.max_plans = max(1, int(max_plans))
-        self._buffers = collections.OrderedDict()    # (plan key, "in" | "out", channels, device) -> one buffer per scale
+        self._buffers = _strips.PlanBuffers(self.max_plans)      # (plan key, "in" | "out", channels, device) -> one buffer per scale
 
     def plan(self, N, H, W):
         """The TTAPlan a batch of N images of H x W gets."""
         return TTAPlan(N, H, W, *self._plan_args)
 
-    def refresh(self):
-        """refresh() of the inner predictor where it has one (for callers that capture a call into a graph of their own)."""
-        fn = getattr(self.predictor, "refresh", None)
-        if fn is not None:
-            fn()
-
-    def _workspace(self, key, shapes, device):
-        bufs = self._buffers.pop(key, None)
-        if bufs is None:
-            bufs = tuple(torch.empty(s, dtype=torch.float32, device=device) for s in shapes)
-        self._buffers[key] = bufs
-        while len(self._buffers) > 2 * self.max_plans:                           # the view buffers and the output buffers per plan
-            self._buffers.popitem(last=False)
-        return bufs
-
-    def _view_logits(self, x):
+    def _parts(self, x):
         """-> (plan, the V outputs [N, C, h_s, w_s], slices of this predictor's buffers for the plan)."""
         x = _check_input(x, "TTAPredictor")
         N, Cin, H, W = x.shape
         plan = self.plan(N, H, W)
         B = plan.F * N
-        ins = self._workspace((plan.key, "in", Cin, str(x.device)), [(B, Cin, h, w) for h, w in plan.sizes], x.device)
+        ins = self._buffers.get((plan.key, "in", Cin, str(x.device)), [(B, Cin, h, w) for h, w in plan.sizes], x.device)
         outs = None
         for s in range(plan.S):
             out = self.predictor(make_views(x, plan, s, out=ins[s]))["out"]
@@ -289,18 +245,9 @@ class TTAPredictor:
                                  f"[{B}, C, {plan.sizes[s][0]}, {plan.sizes[s][1]}] expected")
             if outs is None:
                 C = out.shape[1]
-                outs = self._workspace((plan.key, "out", C, str(x.device)), [(B, C, h, w) for h, w in plan.sizes], x.device)
+                outs = self._buffers.get((plan.key, "out", C, str(x.device)), [(B, C, h, w) for h, w in plan.sizes], x.device)
             outs[s].copy_(out)                                                  # before the next replay overwrites the static output
         return plan, [outs[s][f * N:(f + 1) * N] for s in range(plan.S) for f in range(plan.F)]
 
-    def __call__(self, x):
-        with torch.no_grad():
-            plan, views = self._view_logits(x)
-            return {"out": merge_views(views, plan, self.merge)}
-
-    def predict_mask(self, x, lut=None):
-        """-> uint8 [N, H, W]: lut[argmax_c of the merged views], ties to the lowest class, written by the merge kernel itself (the
-        merged tensor never reaches memory).  lut as for Predictor.predict_mask."""
-        with torch.no_grad():
-            plan, views = self._view_logits(x)
-            return merge_views(views, plan, self.merge, lut=lut, want="mask")
+    def _combine(self, views, plan, lut, want):
+        return merge_views(views, plan, self.merge, lut=lut, want=want)

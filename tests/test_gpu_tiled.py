@@ -15,8 +15,8 @@ from test_gpu_infer import _randomize_bn, _small_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-BLEND_ROWS = 4                     # kBlendRows of csrc/tiles.hip, restated: image rows per workgroup, one per wave
-BLEND_COLS = 256                   # kBlendCols: columns per wave, 4 per lane
+BLEND_ROWS = 4                     # kStripRows of csrc/strip_out.h, restated: image rows per workgroup, one per wave
+BLEND_COLS = 256                   # kStripCols: columns per wave, 4 per lane
 
 # (N, C, (H, W), window, stride)
 SHAPES = [

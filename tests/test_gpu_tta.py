@@ -18,8 +18,8 @@ from test_gpu_infer import _randomize_bn, _small_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-ROWS = 4                           # kRows of csrc/tta.hip, restated: image rows per workgroup, one per wave
-COLS = 256                         # kCols: columns per wave, 4 per lane
+ROWS = 4                           # kStripRows of csrc/strip_out.h, restated: image rows per workgroup, one per wave
+COLS = 256                         # kStripCols: columns per wave, 4 per lane
 PROB_MAX_C = 8                     # kProbMaxC: classes the prob merge holds in registers
 ALL_FLIPS = ("", "h", "v", "hv")
 
