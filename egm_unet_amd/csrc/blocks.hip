@@ -10,12 +10,6 @@
 
 namespace {
 
-inline int stream_grid(long long total_threads) {
-    long long b = (total_threads + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 __device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + expf(-v)); }
 
 #define PIX_LOOP(total_expr)                                                                           \
@@ -781,9 +775,6 @@ __global__ void merge357_pack_kernel(const float* __restrict__ w3, const float* 
 
 }  // namespace
 
-#define EGM_REQ_VEC(name, ptr, ld, C)                                                                      \
-    EGM_REQUIRE((ptr) != nullptr && egm_aligned16(ptr) && (C) > 0 && (C) % 8 == 0 && (ld) >= (C) && (ld) % 8 == 0, \
-                name ": bad tensor (ptr/alignment/C=%d/ld=%d)", (int)(C), (int)(ld))
 #define EGM_GROUP_SWITCH(G, ...)                                                                \
     switch (G) { case 1: { constexpr int GROUP = 1; __VA_ARGS__; break; } case 2: { constexpr int GROUP = 2; __VA_ARGS__; break; } \
                  case 4: { constexpr int GROUP = 4; __VA_ARGS__; break; } case 8: { constexpr int GROUP = 8; __VA_ARGS__; break; } \
@@ -793,7 +784,7 @@ __global__ void merge357_pack_kernel(const float* __restrict__ w3, const float* 
 extern "C" int egm_highpass3(int dtype, const void* x, int ldx, void* out, int ldo, int N, int H, int W, int C, egm_stream_t s) {
     EGM_REQ_VEC("highpass3", x, ldx, C); EGM_REQ_VEC("highpass3", out, ldo, C);
     EGM_REQUIRE(N > 0 && H > 0 && W > 0, "highpass3: bad shape");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((highpass3_kernel<T>), dim3(stream_grid((long long)N * H * W * (C / 8))), dim3(256), 0,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((highpass3_kernel<T>), dim3(egm_stream_grid((long long)N * H * W * (C / 8))), dim3(256), 0,
                                                  (hipStream_t)s, (const T*)x, ldx, (T*)out, ldo, N, H, W, C));
     EGM_CHECK_LAUNCH("highpass3");
     return EGM_OK;
@@ -801,7 +792,7 @@ extern "C" int egm_highpass3(int dtype, const void* x, int ldx, void* out, int l
 extern "C" int egm_gate_mul_fwd(int dtype, const void* x, int ldx, const void* w, int ldw, void* out, int ldo, long long npix, int C,
                                 egm_stream_t s) {
     EGM_REQ_VEC("gate_mul_fwd", x, ldx, C); EGM_REQ_VEC("gate_mul_fwd", w, ldw, C); EGM_REQ_VEC("gate_mul_fwd", out, ldo, C);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate_mul_fwd_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate_mul_fwd_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)x, ldx, (const T*)w, ldw, (T*)out, ldo, npix, C));
     EGM_CHECK_LAUNCH("gate_mul_fwd");
     return EGM_OK;
@@ -810,7 +801,7 @@ extern "C" int egm_gate_mul_bwd(int dtype, const void* g, int ldg, const void* x
                                 void* dw, int lddw, long long npix, int C, egm_stream_t s) {
     EGM_REQ_VEC("gate_mul_bwd", g, ldg, C); EGM_REQ_VEC("gate_mul_bwd", x, ldx, C); EGM_REQ_VEC("gate_mul_bwd", w, ldw, C);
     EGM_REQ_VEC("gate_mul_bwd", dx, lddx, C); EGM_REQ_VEC("gate_mul_bwd", dw, lddw, C);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate_mul_bwd_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate_mul_bwd_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)g, ldg, (const T*)x, ldx, (const T*)w, ldw, (T*)dx, lddx, (T*)dw, lddw, npix, C));
     EGM_CHECK_LAUNCH("gate_mul_bwd");
     return EGM_OK;
@@ -818,7 +809,7 @@ extern "C" int egm_gate_mul_bwd(int dtype, const void* g, int ldg, const void* x
 extern "C" int egm_scale_add_relu_fwd(int dtype, const void* a, int lda, float alpha, const void* b, int ldb, void* out, int ldo,
                                       long long npix, int C, egm_stream_t s) {
     EGM_REQ_VEC("scale_add_relu_fwd", a, lda, C); EGM_REQ_VEC("scale_add_relu_fwd", b, ldb, C); EGM_REQ_VEC("scale_add_relu_fwd", out, ldo, C);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((scale_add_relu_fwd_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((scale_add_relu_fwd_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0,
                                                  (hipStream_t)s, (const T*)a, lda, alpha, (const T*)b, ldb, (T*)out, ldo, npix, C));
     EGM_CHECK_LAUNCH("scale_add_relu_fwd");
     return EGM_OK;
@@ -827,7 +818,7 @@ extern "C" int egm_scale_add_relu_bwd(int dtype, const void* g, int ldg, const v
                                       void* db, int lddb, long long npix, int C, egm_stream_t s) {
     EGM_REQ_VEC("scale_add_relu_bwd", g, ldg, C); EGM_REQ_VEC("scale_add_relu_bwd", out, ldo, C);
     EGM_REQ_VEC("scale_add_relu_bwd", da, ldda, C); EGM_REQ_VEC("scale_add_relu_bwd", db, lddb, C);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((scale_add_relu_bwd_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((scale_add_relu_bwd_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0,
                                                  (hipStream_t)s, (const T*)g, ldg, (const T*)out, ldo, alpha, (T*)da, ldda, (T*)db, lddb, npix, C));
     EGM_CHECK_LAUNCH("scale_add_relu_bwd");
     return EGM_OK;
@@ -835,7 +826,7 @@ extern "C" int egm_scale_add_relu_bwd(int dtype, const void* g, int ldg, const v
 extern "C" int egm_gate3_fwd(int dtype, const void* x, int ldx, const void* t, int ldt, void* out, int ldo, long long npix, int C,
                              egm_stream_t s) {
     EGM_REQ_VEC("gate3_fwd", x, ldx, C); EGM_REQ_VEC("gate3_fwd", t, ldt, 8); EGM_REQ_VEC("gate3_fwd", out, ldo, C);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate3_fwd_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate3_fwd_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)x, ldx, (const T*)t, ldt, (T*)out, ldo, npix, C));
     EGM_CHECK_LAUNCH("gate3_fwd");
     return EGM_OK;
@@ -845,7 +836,7 @@ extern "C" int egm_gate3_bwd(int dtype, const void* g, int ldg, const void* x, i
     EGM_REQ_VEC("gate3_bwd", g, ldg, C); EGM_REQ_VEC("gate3_bwd", x, ldx, C); EGM_REQ_VEC("gate3_bwd", t, ldt, 8);
     EGM_REQ_VEC("gate3_bwd", dx, lddx, C); EGM_REQ_VEC("gate3_bwd", dt, lddt, 8);
     const int G = group_for(C / 8 > 64 ? 64 : C / 8);
-    const int grid = stream_grid(npix * G);
+    const int grid = egm_stream_grid(npix * G);
     EGM_DISPATCH_DTYPE(dtype, EGM_GROUP_SWITCH(G, hipLaunchKernelGGL((gate3_bwd_kernel<T, GROUP>), dim3(grid), dim3(256), 0, (hipStream_t)s,
                                                                      (const T*)g, ldg, (const T*)x, ldx, (const T*)t, ldt, (T*)dx, lddx,
                                                                      (T*)dt, lddt, npix, C)));
@@ -855,7 +846,7 @@ extern "C" int egm_gate3_bwd(int dtype, const void* g, int ldg, const void* x, i
 extern "C" int egm_bcast_gate_fwd(int dtype, const void* a, int lda, const void* gl, int ldgl, void* out, int ldo, long long npix, int C,
                                   egm_stream_t s) {
     EGM_REQ_VEC("bcast_gate_fwd", a, lda, C); EGM_REQ_VEC("bcast_gate_fwd", gl, ldgl, 8); EGM_REQ_VEC("bcast_gate_fwd", out, ldo, C);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bcast_gate_fwd_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bcast_gate_fwd_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)a, lda, (const T*)gl, ldgl, (T*)out, ldo, npix, C));
     EGM_CHECK_LAUNCH("bcast_gate_fwd");
     return EGM_OK;
@@ -865,7 +856,7 @@ extern "C" int egm_bcast_gate_bwd(int dtype, const void* g, int ldg, const void*
     EGM_REQ_VEC("bcast_gate_bwd", g, ldg, C); EGM_REQ_VEC("bcast_gate_bwd", a, lda, C); EGM_REQ_VEC("bcast_gate_bwd", gl, ldgl, 8);
     EGM_REQ_VEC("bcast_gate_bwd", da, ldda, C); EGM_REQ_VEC("bcast_gate_bwd", dgl, lddgl, 8);
     const int G = group_for(C / 8 > 64 ? 64 : C / 8);
-    const int grid = stream_grid(npix * G);
+    const int grid = egm_stream_grid(npix * G);
     EGM_DISPATCH_DTYPE(dtype, EGM_GROUP_SWITCH(G, hipLaunchKernelGGL((bcast_gate_bwd_kernel<T, GROUP>), dim3(grid), dim3(256), 0,
                                                                      (hipStream_t)s, (const T*)g, ldg, (const T*)a, lda, (const T*)gl, ldgl,
                                                                      (T*)da, ldda, (T*)dgl, lddgl, npix, C)));
@@ -874,7 +865,7 @@ extern "C" int egm_bcast_gate_bwd(int dtype, const void* g, int ldg, const void*
 }
 extern "C" int egm_gelu_fwd(int dtype, const void* x, int ldx, void* out, int ldo, long long npix, int C, egm_stream_t s) {
     EGM_REQ_VEC("gelu_fwd", x, ldx, C); EGM_REQ_VEC("gelu_fwd", out, ldo, C);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gelu_fwd_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gelu_fwd_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)x, ldx, (T*)out, ldo, npix, C));
     EGM_CHECK_LAUNCH("gelu_fwd");
     return EGM_OK;
@@ -882,7 +873,7 @@ extern "C" int egm_gelu_fwd(int dtype, const void* x, int ldx, void* out, int ld
 extern "C" int egm_gelu_bwd(int dtype, const void* g, int ldg, const void* x, int ldx, void* dx, int lddx, long long npix, int C,
                             egm_stream_t s) {
     EGM_REQ_VEC("gelu_bwd", g, ldg, C); EGM_REQ_VEC("gelu_bwd", x, ldx, C); EGM_REQ_VEC("gelu_bwd", dx, lddx, C);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gelu_bwd_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gelu_bwd_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)g, ldg, (const T*)x, ldx, (T*)dx, lddx, npix, C));
     EGM_CHECK_LAUNCH("gelu_bwd");
     return EGM_OK;
@@ -892,7 +883,7 @@ extern "C" int egm_chan_meanmax_fwd(int dtype, const void* x, int ldx, void* out
     EGM_REQ_VEC("chan_meanmax_fwd", x, ldx, C); EGM_REQ_VEC("chan_meanmax_fwd", out, ldo, 8);
     EGM_REQUIRE(C_real > 0 && C_real <= C, "chan_meanmax_fwd: bad C_real");
     const int G = group_for(C / 8 > 64 ? 64 : C / 8);
-    EGM_DISPATCH_DTYPE(dtype, EGM_GROUP_SWITCH(G, hipLaunchKernelGGL((chan_meanmax_fwd_kernel<T, GROUP>), dim3(stream_grid(npix * G)), dim3(256),
+    EGM_DISPATCH_DTYPE(dtype, EGM_GROUP_SWITCH(G, hipLaunchKernelGGL((chan_meanmax_fwd_kernel<T, GROUP>), dim3(egm_stream_grid(npix * G)), dim3(256),
                                                                      0, (hipStream_t)s, (const T*)x, ldx, (T*)out, ldo, npix, C, C_real)));
     EGM_CHECK_LAUNCH("chan_meanmax_fwd");
     return EGM_OK;
@@ -902,7 +893,7 @@ extern "C" int egm_chan_meanmax_bwd(int dtype, const void* g, int ldg, const voi
     EGM_REQ_VEC("chan_meanmax_bwd", g, ldg, 8); EGM_REQ_VEC("chan_meanmax_bwd", x, ldx, C); EGM_REQ_VEC("chan_meanmax_bwd", dx, lddx, C);
     EGM_REQUIRE(C_real > 0 && C_real <= C, "chan_meanmax_bwd: bad C_real");
     const int G = group_for(C / 8 > 64 ? 64 : C / 8);
-    EGM_DISPATCH_DTYPE(dtype, EGM_GROUP_SWITCH(G, hipLaunchKernelGGL((chan_meanmax_bwd_kernel<T, GROUP>), dim3(stream_grid(npix * G)), dim3(256),
+    EGM_DISPATCH_DTYPE(dtype, EGM_GROUP_SWITCH(G, hipLaunchKernelGGL((chan_meanmax_bwd_kernel<T, GROUP>), dim3(egm_stream_grid(npix * G)), dim3(256),
                                                                      0, (hipStream_t)s, (const T*)g, ldg, (const T*)x, ldx, (T*)dx, lddx, npix,
                                                                      C, C_real)));
     EGM_CHECK_LAUNCH("chan_meanmax_bwd");
@@ -938,7 +929,7 @@ extern "C" int egm_global_avgmax_bwd(int dtype, const void* gout, const int* arg
                                      egm_stream_t s) {
     EGM_REQ_VEC("global_avgmax_bwd", dx, lddx, C);
     EGM_REQUIRE(gout && argidx && egm_aligned16(gout) && N > 0 && HW > 0, "global_avgmax_bwd: bad args");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((global_pool_bwd_kernel<T>), dim3(stream_grid((long long)N * HW * (C / 8))), dim3(256), 0,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((global_pool_bwd_kernel<T>), dim3(egm_stream_grid((long long)N * HW * (C / 8))), dim3(256), 0,
                                                  (hipStream_t)s, (const T*)gout, argidx, (T*)dx, lddx, N, HW, C));
     EGM_CHECK_LAUNCH("global_avgmax_bwd");
     return EGM_OK;
@@ -978,7 +969,7 @@ extern "C" int egm_fusion_combine_fwd(int dtype, const void* f, int ldf, const v
     EGM_REQ_VEC("fusion_combine_fwd", f, ldf, C); EGM_REQ_VEC("fusion_combine_fwd", sv, lds, C); EGM_REQ_VEC("fusion_combine_fwd", sa, ldsa, 8);
     EGM_REQ_VEC("fusion_combine_fwd", out, ldo, C);
     EGM_REQUIRE(ca && egm_aligned16(ca) && N > 0 && HW > 0, "fusion_combine_fwd: bad args");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((fusion_combine_fwd_kernel<T>), dim3(stream_grid((long long)N * HW * (C / 8))), dim3(256), 0,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((fusion_combine_fwd_kernel<T>), dim3(egm_stream_grid((long long)N * HW * (C / 8))), dim3(256), 0,
                                                  (hipStream_t)s, (const T*)f, ldf, (const T*)sv, lds, (const T*)sa, ldsa, (const T*)ca, (T*)out,
                                                  ldo, N, HW, C));
     EGM_CHECK_LAUNCH("fusion_combine_fwd");

@@ -4,6 +4,7 @@
 // channel-contiguous so a wave reads whole pixels; reductions are two-stage with plain stores (deterministic).
 #include "common.h"
 #include "bn_elem.h"
+#include "bn_frames.h"
 #include <stdlib.h>
 
 namespace {
@@ -19,22 +20,9 @@ __device__ __forceinline__ void channel_partials_body(const T* __restrict__ a, i
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                       int act, long long npix, int C, float* __restrict__ out, int bid, int nb) {
     __shared__ float red[2 * 256 * 8];
-    const int ncv = C >> 3, rows = 256 / ncv;
-    const int tid = threadIdx.x, cv = tid % ncv, row = tid / ncv;
-    float s[8], q[8];
-    zero8(s); zero8(q);
-    if (MODE == 1) {                                           // stage the per-channel coefficients once per block
-        for (int c = tid; c < C; c += 256) { red[c] = scale[c]; red[C + c] = shift[c]; red[2 * C + c] = mean[c]; red[3 * C + c] = rstd[c]; }
-        __syncthreads();
-    }
-    float sc[8], sh[8], mu[8], rs[8];
-    if (MODE == 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc[j] = red[cv * 8 + j]; sh[j] = red[C + cv * 8 + j]; mu[j] = red[2 * C + cv * 8 + j]; rs[j] = red[3 * C + cv * 8 + j]; }
-        __syncthreads();                                       // red[] is reused for the reduction below
-    }
-    if (row < rows) {
-        for (long long p = (long long)bid * rows + row; p < npix; p += (long long)nb * rows) {
+    bn_partials<MODE == 1>(red, scale, shift, mean, rstd, npix, C, out, bid, nb,
+        [&](long long p, int cv, const float (&sc)[8], const float (&sh)[8], const float (&mu)[8], const float (&rs)[8], float (&s)[8],
+            float (&q)[8]) __attribute__((always_inline)) {
             float v[8];
             load8(a + p * lda + cv * 8, v);
             if (MODE == 0) {
@@ -49,18 +37,7 @@ __device__ __forceinline__ void channel_partials_body(const T* __restrict__ a, i
                     s[j] += g; q[j] += g * (yv[j] - mu[j]) * rs[j];
                 }
             }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { red[tid * 8 + j] = s[j]; red[(256 + tid) * 8 + j] = q[j]; }
-    __syncthreads();
-    // thread t < 2*C sums column t over the `rows` pixel rows (fixed order)
-    for (int t = tid; t < 2 * C; t += 256) {
-        const int which = t / C, c = t - which * C, ccv = c >> 3, j = c & 7;
-        float v = 0.f;
-        for (int r = 0; r < rows; ++r) v += red[(which * 256 + r * ncv + ccv) * 8 + j];
-        out[((long long)bid * 2 + which) * C + c] = v;
-    }
+        });
 }
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void channel_partials_kernel(const T* __restrict__ a, int lda, const T* __restrict__ y, int ldy,
@@ -159,11 +136,7 @@ __device__ __forceinline__ void bn_bwd_coefs_body(const float* __restrict__ st, 
         sums[c] = s0; sums[C + c] = s1;
         const float scv = scale[c];
         float cbv = 0.f, ccv = 0.f;
-        if (train) {
-            const float m0 = s0 * inv_count, m1 = s1 * inv_count;
-            ccv = -scv * rstd[c] * m1;
-            cbv = -scv * m0 - ccv * mean[c];
-        }
+        if (train) bn_bwd_cb_cc(scv, s0, s1, inv_count, mean[c], rstd[c], cbv, ccv);
         cf[c] = scv; cf[C + c] = shift[c]; cf[2 * C + c] = cbv; cf[3 * C + c] = ccv;
     }
 }
@@ -192,46 +165,16 @@ template <typename T>
 __device__ __forceinline__ void bn_act_fwd_body(const T* __restrict__ y, int ldy, const float* __restrict__ scale,
                                                 const float* __restrict__ shift, int act, T* __restrict__ z, int ldz,
                                                 long long npix, int C, int bid, int nb) {
-    const int ncv = C >> 3;
-    if (256 % ncv == 0) {
-        // per-channel coefficients: staged once per block through LDS (every thread of every block reading the same few
-        // global lines serialises on one L2 channel)
-        __shared__ float cf[2 * 2048];
-        for (int c = threadIdx.x; c < C; c += 256) { cf[c] = scale[c]; cf[C + c] = shift[c]; }
-        __syncthreads();
-        const int cv = threadIdx.x % ncv, ppb = 256 / ncv;
-        float sc[8], sh[8];
+    __shared__ float cf[2 * 2048];
+    struct V { float v[8]; };
+    bn_stream<V, 2>(npix, C, bid, nb, cf,
+        [&](int c, float (&r)[2]) __attribute__((always_inline)) { r[0] = scale[c]; r[1] = shift[c]; },
+        [&](long long p, int cv, V& a) __attribute__((always_inline)) { load8(y + p * ldy + cv * 8, a.v); },
+        [&](V& a, const float (&k)[2][8]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { sc[j] = cf[cv * 8 + j]; sh[j] = cf[C + cv * 8 + j]; }
-        const long long stride = (long long)nb * ppb;
-        long long p = (long long)bid * ppb + threadIdx.x / ncv;
-        for (; p + stride < npix; p += 2 * stride) {              // two independent vectors in flight
-            float v[8], u[8];
-            load8(y + p * ldy + cv * 8, v);
-            load8(y + (p + stride) * ldy + cv * 8, u);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { v[j] = bn_fwd_elem<sizeof(T) == 2>(v[j], sc[j], sh[j], act); u[j] = bn_fwd_elem<sizeof(T) == 2>(u[j], sc[j], sh[j], act); }
-            store8(z + p * ldz + cv * 8, v);
-            store8(z + (p + stride) * ldz + cv * 8, u);
-        }
-        if (p < npix) {
-            float v[8];
-            load8(y + p * ldy + cv * 8, v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = bn_fwd_elem<sizeof(T) == 2>(v[j], sc[j], sh[j], act);
-            store8(z + p * ldz + cv * 8, v);
-        }
-        return;
-    }
-    const long long total = npix * ncv;
-    for (long long i = bid * 256LL + threadIdx.x; i < total; i += (long long)nb * 256) {
-        const long long p = i / ncv; const int cv = (int)(i - p * ncv);
-        float v[8];
-        load8(y + p * ldy + cv * 8, v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = bn_fwd_elem<sizeof(T) == 2>(v[j], scale[cv * 8 + j], shift[cv * 8 + j], act);
-        store8(z + p * ldz + cv * 8, v);
-    }
+            for (int j = 0; j < 8; ++j) a.v[j] = bn_fwd_elem<sizeof(T) == 2>(a.v[j], k[0][j], k[1][j], act);
+        },
+        [&](long long p, int cv, V& a) __attribute__((always_inline)) { store8(z + p * ldz + cv * 8, a.v); });
 }
 template <typename T>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y, int ldy, const float* __restrict__ scale,
@@ -248,72 +191,19 @@ __device__ __forceinline__ void bn_act_bwd_apply_body(const T* __restrict__ dz, 
                                                       const float* __restrict__ mean, const float* __restrict__ rstd, int act,
                                                       int train, const float* __restrict__ sums, float inv_count,
                                                       T* __restrict__ dy, int lddy, long long npix, int C, int bid, int nb) {
-    const int ncv = C >> 3;
-    if (256 % ncv == 0) {
-        __shared__ float cf[4 * 2048];                     // scale | shift | cb | cc, computed once per block
-        for (int c = threadIdx.x; c < C; c += 256) {
-            const float scv = scale[c];
-            float cbv = 0.f, ccv = 0.f;
-            if (train) {
-                const float m0 = sums[c] * inv_count, m1 = sums[C + c] * inv_count;
-                ccv = -scv * rstd[c] * m1;
-                cbv = -scv * m0 - ccv * mean[c];
-            }
-            cf[c] = scv; cf[C + c] = shift[c]; cf[2 * C + c] = cbv; cf[3 * C + c] = ccv;
-        }
-        __syncthreads();
-        const int cv = threadIdx.x % ncv, ppb = 256 / ncv;
-        float sc[8], sh[8], cb[8], cc[8];
+    __shared__ float cf[4 * 2048];                         // scale | shift | cb | cc, computed once per block
+    struct V { float g[8], y[8]; };
+    bn_stream<V, 4>(npix, C, bid, nb, cf,
+        [&](int c, float (&r)[4]) __attribute__((always_inline)) {
+            r[0] = scale[c]; r[1] = shift[c]; r[2] = 0.f; r[3] = 0.f;
+            if (train) bn_bwd_cb_cc(r[0], sums[c], sums[C + c], inv_count, mean[c], rstd[c], r[2], r[3]);
+        },
+        [&](long long p, int cv, V& a) __attribute__((always_inline)) { load8(dz + p * lddz + cv * 8, a.g); load8(y + p * ldy + cv * 8, a.y); },
+        [&](V& a, const float (&k)[4][8]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = cv * 8 + j;
-            sc[j] = cf[c]; sh[j] = cf[C + c]; cb[j] = cf[2 * C + c]; cc[j] = cf[3 * C + c];
-        }
-        const long long stride = (long long)nb * ppb;
-        long long p = (long long)bid * ppb + threadIdx.x / ncv;
-        for (; p + stride < npix; p += 2 * stride) {              // two independent vector pairs in flight
-            float g[8], yv[8], g2[8], y2[8];
-            load8(dz + p * lddz + cv * 8, g);
-            load8(y + p * ldy + cv * 8, yv);
-            load8(dz + (p + stride) * lddz + cv * 8, g2);
-            load8(y + (p + stride) * ldy + cv * 8, y2);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                g[j] = bn_bwd_elem<sizeof(T) == 2>(g[j], yv[j], sc[j], sh[j], cb[j], cc[j], act);
-                g2[j] = bn_bwd_elem<sizeof(T) == 2>(g2[j], y2[j], sc[j], sh[j], cb[j], cc[j], act);
-            }
-            store8(dy + p * lddy + cv * 8, g);
-            store8(dy + (p + stride) * lddy + cv * 8, g2);
-        }
-        if (p < npix) {
-            float g[8], yv[8];
-            load8(dz + p * lddz + cv * 8, g);
-            load8(y + p * ldy + cv * 8, yv);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = bn_bwd_elem<sizeof(T) == 2>(g[j], yv[j], sc[j], sh[j], cb[j], cc[j], act);
-            store8(dy + p * lddy + cv * 8, g);
-        }
-        return;
-    }
-    const long long total = npix * ncv;
-    for (long long i = bid * 256LL + threadIdx.x; i < total; i += (long long)nb * 256) {
-        const long long p = i / ncv; const int cv = (int)(i - p * ncv);
-        float g[8], yv[8], o[8];
-        load8(dz + p * lddz + cv * 8, g);
-        load8(y + p * ldy + cv * 8, yv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = cv * 8 + j;
-            float cbv = 0.f, ccv = 0.f;
-            if (train) {
-                const float m0 = sums[c] * inv_count, m1 = sums[C + c] * inv_count;
-                ccv = -scale[c] * rstd[c] * m1;
-                cbv = -scale[c] * m0 - ccv * mean[c];
-            }
-            o[j] = bn_bwd_elem<sizeof(T) == 2>(g[j], yv[j], scale[c], shift[c], cbv, ccv, act);
-        }
-        store8(dy + p * lddy + cv * 8, o);
-    }
+            for (int j = 0; j < 8; ++j) a.g[j] = bn_bwd_elem<sizeof(T) == 2>(a.g[j], a.y[j], k[0][j], k[1][j], k[2][j], k[3][j], act);
+        },
+        [&](long long p, int cv, V& a) __attribute__((always_inline)) { store8(dy + p * lddy + cv * 8, a.g); });
 }
 template <typename T>
 __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const T* __restrict__ dz, int lddz, const T* __restrict__ y, int ldy,
@@ -322,13 +212,6 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const T* __restri
                                                                int train, const float* __restrict__ sums, float inv_count,
                                                                T* __restrict__ dy, int lddy, long long npix, int C) {
     bn_act_bwd_apply_body<T>(dz, lddz, y, ldy, scale, shift, mean, rstd, act, train, sums, inv_count, dy, lddy, npix, C, blockIdx.x, gridDim.x);
-}
-
-inline int stream_grid(long long total_threads) {
-    long long b = (total_threads + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;          // ~16 blocks per CU, grid-stride the rest
-    if (b < 1) b = 1;
-    return (int)b;
 }
 
 
@@ -377,7 +260,7 @@ int multi_blocks(const egm_bn_desc& d, int which) {
     switch (which) {
         case 0: case 3: return (d.C + 7) / 8;
         case 2: return egm_partial_blocks(d.npix, d.C);
-        default: return stream_grid(d.npix * (d.C >> 3));
+        default: return egm_stream_grid(d.npix * (d.C >> 3));
     }
 }
 int multi_build(const egm_bn_desc* descs, int n, int which, BnMulti* m) {
@@ -395,9 +278,6 @@ int multi_build(const egm_bn_desc* descs, int n, int which, BnMulti* m) {
 
 }  // namespace
 
-#define EGM_REQ_VEC(name, ptr, ld, C)                                                                      \
-    EGM_REQUIRE((ptr) != nullptr && egm_aligned16(ptr) && (C) > 0 && (C) % 8 == 0 && (ld) >= (C) && (ld) % 8 == 0, \
-                name ": bad tensor (ptr/alignment/C=%d/ld=%d)", (int)(C), (int)(ld))
 
 extern "C" int egm_channel_partials_blocks(long long npix, int C) {
     if (C <= 0 || C % 8 || C > 2048) return -1;
@@ -502,7 +382,7 @@ extern "C" int egm_bn_act_fwd(int dtype, const void* y, int ldy, const float* sc
     EGM_REQ_VEC("bn_act_fwd", y, ldy, C);
     EGM_REQ_VEC("bn_act_fwd", z, ldz, C);
     EGM_REQUIRE(scale && shift && npix > 0, "bn_act_fwd: bad args");
-    const int grid = stream_grid(npix * (C >> 3));
+    const int grid = egm_stream_grid(npix * (C >> 3));
     EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_act_fwd_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)y, ldy,
                                                  scale, shift, act, (T*)z, ldz, npix, C));
     EGM_CHECK_LAUNCH("bn_act_fwd");
@@ -540,7 +420,7 @@ extern "C" int egm_bn_act_bwd_apply(int dtype, const void* dz, int lddz, const v
     EGM_REQ_VEC("bn_act_bwd_apply", y, ldy, C);
     EGM_REQ_VEC("bn_act_bwd_apply", dy, lddy, C);
     EGM_REQUIRE(scale && shift && save_mean && save_rstd && sums && npix > 0, "bn_act_bwd_apply: bad args");
-    const int grid = stream_grid(npix * (C >> 3));
+    const int grid = egm_stream_grid(npix * (C >> 3));
     EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)dz,
                                                  lddz, (const T*)y, ldy, scale, shift, save_mean, save_rstd, act, train, sums,
                                                  1.f / (float)npix, (T*)dy, lddy, npix, C));

@@ -11,15 +11,9 @@
 // tensor reads disappear.  Same partial-sum geometry as bn.hip (egm_channel_partials_blocks), same element formulas (bn_elem.h).
 #include "common.h"
 #include "bn_elem.h"
+#include "bn_frames.h"
 
 namespace {
-
-inline int stream_grid(long long total_threads) {
-    long long b = (total_threads + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 enum { DZ_CLS = 0, DZ_MCA = 1, DZ_CLS2 = 2 };      // DZ_CLS2: at most two classes (the binary segmentation head): 16 instead of 64 FMAs per vector
 
@@ -99,19 +93,11 @@ __global__ __launch_bounds__(256) void bn_dz_bwd_reduce_kernel(DzArgs d, const T
                                                                const float* __restrict__ rstd, int act, long long npix, int C,
                                                                float* __restrict__ out) {
     __shared__ float red[2 * 256 * 8];
-    const int ncv = C >> 3, rows = 256 / ncv;
-    const int tid = threadIdx.x, cv = tid % ncv, row = tid / ncv;
-    for (int c = tid; c < C; c += 256) { red[c] = scale[c]; red[C + c] = shift[c]; red[2 * C + c] = mean[c]; red[3 * C + c] = rstd[c]; }
-    __syncthreads();
-    float sc[8], sh[8], mu[8], rs[8], s[8], q[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sc[j] = red[cv * 8 + j]; sh[j] = red[C + cv * 8 + j]; mu[j] = red[2 * C + cv * 8 + j]; rs[j] = red[3 * C + cv * 8 + j]; }
-    __syncthreads();
-    zero8(s); zero8(q);
     DzCtx<T, MODE> ctx;
-    ctx.init(d, cv, C);
-    if (row < rows) {
-        for (long long p = (long long)blockIdx.x * rows + row; p < npix; p += (long long)gridDim.x * rows) {
+    ctx.init(d, (int)threadIdx.x % (C >> 3), C);               // the frame's cv
+    bn_partials<true>(red, scale, shift, mean, rstd, npix, C, out, blockIdx.x, gridDim.x,
+        [&](long long p, int cv, const float (&sc)[8], const float (&sh)[8], const float (&mu)[8], const float (&rs)[8], float (&s)[8],
+            float (&q)[8]) __attribute__((always_inline)) {
             float yv[8], z[8], g[8];
             load8(y + p * ldy + cv * 8, yv);
             if constexpr (MODE == DZ_MCA) {
@@ -124,20 +110,11 @@ __global__ __launch_bounds__(256) void bn_dz_bwd_reduce_kernel(DzArgs d, const T
                 const float gg = g[j] * act_grad<sizeof(T) == 2>(fmaf(yv[j], sc[j], sh[j]), act);
                 s[j] += gg; q[j] += gg * (yv[j] - mu[j]) * rs[j];
             }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { red[tid * 8 + j] = s[j]; red[(256 + tid) * 8 + j] = q[j]; }
-    __syncthreads();
-    for (int t = tid; t < 2 * C; t += 256) {
-        const int which = t / C, c = t - which * C, ccv = c >> 3, j = c & 7;
-        float v = 0.f;
-        for (int r = 0; r < rows; ++r) v += red[(which * 256 + r * ncv + ccv) * 8 + j];
-        out[((long long)blockIdx.x * 2 + which) * C + c] = v;
-    }
+        });
 }
 
-// dy = scale*dzp + cb + cc*y   (bn.hip bn_act_bwd_apply)
+// dy = scale*dzp + cb + cc*y   (bn.hip bn_act_bwd_apply).  Its own loop, not bn_stream: one pixel in flight (DzCtx<DZ_MCA> carries state from
+// pixel to pixel), and on the frame the bf16 DZ_MCA instantiation took 130 VGPRs against 128 here: 3 waves per SIMD instead of 4.
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void bn_dz_bwd_apply_kernel(DzArgs d, const T* __restrict__ y, int ldy, const float* __restrict__ scale,
                                                               const float* __restrict__ shift, const float* __restrict__ mean,
@@ -147,11 +124,7 @@ __global__ __launch_bounds__(256) void bn_dz_bwd_apply_kernel(DzArgs d, const T*
     for (int c = threadIdx.x; c < C; c += 256) {
         const float scv = scale[c];
         float cbv = 0.f, ccv = 0.f;
-        if (train) {
-            const float m0 = sums[c] * inv_count, m1 = sums[C + c] * inv_count;
-            ccv = -scv * rstd[c] * m1;
-            cbv = -scv * m0 - ccv * mean[c];
-        }
+        if (train) bn_bwd_cb_cc(scv, sums[c], sums[C + c], inv_count, mean[c], rstd[c], cbv, ccv);
         cf[c] = scv; cf[C + c] = shift[c]; cf[2 * C + c] = cbv; cf[3 * C + c] = ccv;
     }
     __syncthreads();
@@ -270,7 +243,7 @@ template <int MODE>
 int launch_apply(int dtype, const DzArgs& d, const void* y, int ldy, const float* scale, const float* shift, const float* mean, const float* rstd,
                  int act, int train, const float* sums, void* dy, int lddy, long long npix, int C, egm_stream_t s) {
     EGM_REQUIRE(scale && shift && mean && rstd && sums && dy && egm_aligned16(dy) && lddy >= C && lddy % 8 == 0, "bn_dz_bwd_apply: bad args");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_dz_bwd_apply_kernel<T, MODE>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_dz_bwd_apply_kernel<T, MODE>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  d, (const T*)y, ldy, scale, shift, mean, rstd, act, train, sums, 1.f / (float)npix, (T*)dy, lddy,
                                                  npix, C));
     EGM_CHECK_LAUNCH("bn_dz_bwd_apply");
@@ -325,7 +298,7 @@ extern "C" int egm_bn_act_cls_fwd(int dtype, const void* y, int ldy, const float
     EGM_REQUIRE(z && egm_aligned16(z) && ldz >= C && ldz % 8 == 0 && scale && shift && w_cls && logits_nchw && nc >= 1 && nc <= 8 &&
                 ldw >= 1 && ldw <= C && C / 8 <= 64 && ((C / 8) & (C / 8 - 1)) == 0,
                 "bn_act_cls_fwd: bad args (nc=%d <= 8, C/8 = %d a power of two <= 64)", nc, C / 8);
-    const int grid = stream_grid(npix * (C / 8));
+    const int grid = egm_stream_grid(npix * (C / 8));
     const long long HW = (long long)H * W;
     if (nc <= 2) {
         EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_act_cls_fwd_kernel<T, 2>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)y, ldy, scale,

@@ -37,6 +37,17 @@ __device__ __forceinline__ float act_grad(float v, int act) {
     if (act == EGM_ACT_SILU) { const float z = logistic<FAST>(v); return z * (1.f + v * (1.f - z)); }
     return 1.f;
 }
+// The train-mode backward coefficients of one channel: dy = scale*(dzp - m0 - xhat*m1) = scale*dzp + cb + cc*y with m = sums*inv_count,
+// cc = -scale*rstd*m1, cb = -scale*m0 - cc*mean (eval: cb = cc = 0, the callers' default).  The ONE definition: egm_bn_bwd_coefs and
+// every apply pass that folds the sums itself must agree bit for bit.  Contraction is off: every product and the difference round on
+// their own, so the result does not depend on what the compiler makes of the code around a call (where it packs the products into
+// v_pk_mul_f32 the subtraction stays apart; where it does not, it would fuse it into the second product).
+__device__ __forceinline__ void bn_bwd_cb_cc(float scv, float s0, float s1, float inv_count, float mean, float rstd, float& cbv, float& ccv) {
+#pragma clang fp contract(off)
+    const float m0 = s0 * inv_count, m1 = s1 * inv_count;
+    ccv = -scv * rstd * m1;
+    cbv = -scv * m0 - ccv * mean;
+}
 template <bool FAST = false>
 __device__ __forceinline__ float bn_fwd_elem(float y, float sc, float sh, int act) { return act_fwd<FAST>(fmaf(y, sc, sh), act); }
 // dy = scale*(dzp - mean(dzp) - xhat*mean(dzp*xhat)) = scale*dzp + cb + cc*y,  dzp = dz*act'(y*scale + shift)

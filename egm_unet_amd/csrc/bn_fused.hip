@@ -13,6 +13,7 @@
 // to the storage type in registers before they are used), so fused and unfused results agree bit for bit.
 #include "common.h"
 #include "bn_elem.h"
+#include "bn_frames.h"
 
 namespace {
 
@@ -38,51 +39,16 @@ template <typename T, int MODE>
 __global__ __launch_bounds__(256) void bn_ew_fwd_kernel(const T* __restrict__ y, int ldy, const float* __restrict__ scale,
                                                         const float* __restrict__ shift, int act, const T* __restrict__ p, int ldp,
                                                         float alpha, T* __restrict__ out, int ldo, long long npix, int C) {
-    const int ncv = C >> 3;
-    if (256 % ncv == 0) {
-        __shared__ float cfl[2 * 2048];
-        for (int c = threadIdx.x; c < C; c += 256) { cfl[c] = scale[c]; cfl[C + c] = shift[c]; }
-        __syncthreads();
-        const int cv = threadIdx.x % ncv, ppb = 256 / ncv;
-        float sc[8], sh[8];
+    __shared__ float cfl[2 * 2048];
+    struct V { float y[8], p[8]; };
+    bn_stream<V, 2>(npix, C, blockIdx.x, gridDim.x, cfl,
+        [&](int c, float (&r)[2]) __attribute__((always_inline)) { r[0] = scale[c]; r[1] = shift[c]; },
+        [&](long long px, int cv, V& a) __attribute__((always_inline)) { load8(y + px * ldy + cv * 8, a.y); load8(p + px * ldp + cv * 8, a.p); },
+        [&](V& a, const float (&k)[2][8]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { sc[j] = cfl[cv * 8 + j]; sh[j] = cfl[C + cv * 8 + j]; }
-        const long long stride = (long long)gridDim.x * ppb;
-        long long px = (long long)blockIdx.x * ppb + threadIdx.x / ncv;
-        for (; px + stride < npix; px += 2 * stride) {
-            float y0[8], p0[8], y1[8], p1[8];
-            load8(y + px * ldy + cv * 8, y0); load8(p + px * ldp + cv * 8, p0);
-            load8(y + (px + stride) * ldy + cv * 8, y1); load8(p + (px + stride) * ldp + cv * 8, p1);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                p0[j] = ew_fwd<T, MODE>(p0[j], rnd<T>(bn_fwd_elem<sizeof(T) == 2>(y0[j], sc[j], sh[j], act)), alpha);
-                p1[j] = ew_fwd<T, MODE>(p1[j], rnd<T>(bn_fwd_elem<sizeof(T) == 2>(y1[j], sc[j], sh[j], act)), alpha);
-            }
-            store8(out + px * ldo + cv * 8, p0);
-            store8(out + (px + stride) * ldo + cv * 8, p1);
-        }
-        if (px < npix) {
-            float y0[8], p0[8];
-            load8(y + px * ldy + cv * 8, y0); load8(p + px * ldp + cv * 8, p0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) p0[j] = ew_fwd<T, MODE>(p0[j], rnd<T>(bn_fwd_elem<sizeof(T) == 2>(y0[j], sc[j], sh[j], act)), alpha);
-            store8(out + px * ldo + cv * 8, p0);
-        }
-        return;
-    }
-    const long long total = npix * ncv;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const long long px = i / ncv; const int cv = (int)(i - px * ncv);
-        float yv[8], pv[8];
-        load8(y + px * ldy + cv * 8, yv);
-        load8(p + px * ldp + cv * 8, pv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float z = rnd<T>(bn_fwd_elem<sizeof(T) == 2>(yv[j], scale[cv * 8 + j], shift[cv * 8 + j], act));
-            pv[j] = ew_fwd<T, MODE>(pv[j], z, alpha);
-        }
-        store8(out + px * ldo + cv * 8, pv);
-    }
+            for (int j = 0; j < 8; ++j) a.p[j] = ew_fwd<T, MODE>(a.p[j], rnd<T>(bn_fwd_elem<sizeof(T) == 2>(a.y[j], k[0][j], k[1][j], act)), alpha);
+        },
+        [&](long long px, int cv, V& a) __attribute__((always_inline)) { store8(out + px * ldo + cv * 8, a.p); });
 }
 
 // block = 256 threads = (256 / ncv) pixel rows x ncv channel vectors; out[blk][2][C] (the layout of channel_partials_kernel, bn.hip)
@@ -93,17 +59,9 @@ __global__ __launch_bounds__(256) void bn_ew_bwd_reduce_kernel(const T* __restri
                                                                const float* __restrict__ rstd, int act, float alpha, long long npix,
                                                                int C, float* __restrict__ out) {
     __shared__ float red[2 * 256 * 8];
-    const int ncv = C >> 3, rows = 256 / ncv;
-    const int tid = threadIdx.x, cv = tid % ncv, row = tid / ncv;
-    float s[8], t[8], sc[8], sh[8], mu[8], rs[8];
-    zero8(s); zero8(t);
-    for (int c = tid; c < C; c += 256) { red[c] = scale[c]; red[C + c] = shift[c]; red[2 * C + c] = mean[c]; red[3 * C + c] = rstd[c]; }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { const int c = cv * 8 + j; sc[j] = red[c]; sh[j] = red[C + c]; mu[j] = red[2 * C + c]; rs[j] = red[3 * C + c]; }
-    __syncthreads();                                           // red[] is reused for the reduction below
-    if (row < rows) {
-        for (long long px = (long long)blockIdx.x * rows + row; px < npix; px += (long long)gridDim.x * rows) {
+    bn_partials<true>(red, scale, shift, mean, rstd, npix, C, out, blockIdx.x, gridDim.x,
+        [&](long long px, int cv, const float (&sc)[8], const float (&sh)[8], const float (&mu)[8], const float (&rs)[8], float (&s)[8],
+            float (&t)[8]) __attribute__((always_inline)) {
             float gv[8], qv[8], yv[8];
             load8(g + px * ldg + cv * 8, gv);
             load8(q + px * ldq + cv * 8, qv);
@@ -115,17 +73,7 @@ __global__ __launch_bounds__(256) void bn_ew_bwd_reduce_kernel(const T* __restri
                 const float dzp = dz * act_grad<sizeof(T) == 2>(fmaf(yv[j], sc[j], sh[j]), act);
                 s[j] += dzp; t[j] += dzp * (yv[j] - mu[j]) * rs[j];
             }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { red[tid * 8 + j] = s[j]; red[(256 + tid) * 8 + j] = t[j]; }
-    __syncthreads();
-    for (int k = tid; k < 2 * C; k += 256) {
-        const int which = k / C, c = k - which * C, ccv = c >> 3, j = c & 7;
-        float v = 0.f;
-        for (int r = 0; r < rows; ++r) v += red[(which * 256 + r * ncv + ccv) * 8 + j];
-        out[((long long)blockIdx.x * 2 + which) * C + c] = v;
-    }
+        });
 }
 
 template <typename T, int MODE>
@@ -146,61 +94,19 @@ __global__ __launch_bounds__(256) void bn_ew_bwd_apply_kernel(const T* __restric
                                                               const T* __restrict__ y, int ldy, const float* __restrict__ cf, int act,
                                                               float alpha, T* __restrict__ dy, int lddy, T* __restrict__ dp, int lddp,
                                                               long long npix, int C) {
-    const int ncv = C >> 3;
-    if (256 % ncv == 0) {
-        __shared__ float cfl[4 * 2048];
-        for (int c = threadIdx.x; c < 4 * C; c += 256) cfl[c] = cf[c];
-        __syncthreads();
-        const int cv = threadIdx.x % ncv, ppb = 256 / ncv;
-        float sc[8], sh[8], cb[8], cc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const int c = cv * 8 + j; sc[j] = cfl[c]; sh[j] = cfl[C + c]; cb[j] = cfl[2 * C + c]; cc[j] = cfl[3 * C + c]; }
-        const long long stride = (long long)gridDim.x * ppb;
-        long long px = (long long)blockIdx.x * ppb + threadIdx.x / ncv;
-        for (; px + stride < npix; px += 2 * stride) {
-            float g0[8], q0[8], y0[8], g1[8], q1[8], y1[8], a0[8], b0[8], a1[8], b1[8];
-            load8(g + px * ldg + cv * 8, g0); load8(q + px * ldq + cv * 8, q0); load8(y + px * ldy + cv * 8, y0);
-            load8(g + (px + stride) * ldg + cv * 8, g1); load8(q + (px + stride) * ldq + cv * 8, q1); load8(y + (px + stride) * ldy + cv * 8, y1);
-            ew_apply8<T, MODE>(g0, q0, y0, sc, sh, cb, cc, act, alpha, a0, b0);
-            ew_apply8<T, MODE>(g1, q1, y1, sc, sh, cb, cc, act, alpha, a1, b1);
-            store8(dy + px * lddy + cv * 8, a0); store8(dp + px * lddp + cv * 8, b0);
-            store8(dy + (px + stride) * lddy + cv * 8, a1); store8(dp + (px + stride) * lddp + cv * 8, b1);
-        }
-        if (px < npix) {
-            float g0[8], q0[8], y0[8], a0[8], b0[8];
-            load8(g + px * ldg + cv * 8, g0); load8(q + px * ldq + cv * 8, q0); load8(y + px * ldy + cv * 8, y0);
-            ew_apply8<T, MODE>(g0, q0, y0, sc, sh, cb, cc, act, alpha, a0, b0);
-            store8(dy + px * lddy + cv * 8, a0); store8(dp + px * lddp + cv * 8, b0);
-        }
-        return;
-    }
-    const long long total = npix * ncv;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const long long px = i / ncv; const int cv = (int)(i - px * ncv);
-        float gv[8], qv[8], yv[8], o1[8], o2[8], sc[8], sh[8], cb[8], cc[8];
-        load8(g + px * ldg + cv * 8, gv);
-        load8(q + px * ldq + cv * 8, qv);
-        load8(y + px * ldy + cv * 8, yv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const int c = cv * 8 + j; sc[j] = cf[c]; sh[j] = cf[C + c]; cb[j] = cf[2 * C + c]; cc[j] = cf[3 * C + c]; }
-        ew_apply8<T, MODE>(gv, qv, yv, sc, sh, cb, cc, act, alpha, o1, o2);
-        store8(dy + px * lddy + cv * 8, o1);
-        store8(dp + px * lddp + cv * 8, o2);
-    }
-}
-
-inline int stream_grid(long long total_threads) {
-    long long b = (total_threads + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (int)b;
+    __shared__ float cfl[4 * 2048];
+    struct V { float g[8], q[8], y[8], o1[8], o2[8]; };
+    bn_stream<V, 4>(npix, C, blockIdx.x, gridDim.x, cfl,
+        [&](int c, float (&r)[4]) __attribute__((always_inline)) { r[0] = cf[c]; r[1] = cf[C + c]; r[2] = cf[2 * C + c]; r[3] = cf[3 * C + c]; },
+        [&](long long px, int cv, V& a) __attribute__((always_inline)) {
+            load8(g + px * ldg + cv * 8, a.g); load8(q + px * ldq + cv * 8, a.q); load8(y + px * ldy + cv * 8, a.y);
+        },
+        [&](V& a, const float (&k)[4][8]) __attribute__((always_inline)) { ew_apply8<T, MODE>(a.g, a.q, a.y, k[0], k[1], k[2], k[3], act, alpha, a.o1, a.o2); },
+        [&](long long px, int cv, V& a) __attribute__((always_inline)) { store8(dy + px * lddy + cv * 8, a.o1); store8(dp + px * lddp + cv * 8, a.o2); });
 }
 
 }  // namespace
 
-#define EGM_REQ_VEC(name, ptr, ld, C)                                                                      \
-    EGM_REQUIRE((ptr) != nullptr && egm_aligned16(ptr) && (C) > 0 && (C) % 8 == 0 && (ld) >= (C) && (ld) % 8 == 0, \
-                name ": bad tensor (ptr/alignment/C=%d/ld=%d)", (int)(C), (int)(ld))
 #define EGM_EW_DISPATCH(mode, ...)                                                                       \
     do { if ((mode) == EGM_EW_GATE) { constexpr int MODE = EGM_EW_GATE; EGM_DISPATCH_DTYPE(dtype, __VA_ARGS__); } \
          else if ((mode) == EGM_EW_SAR) { constexpr int MODE = EGM_EW_SAR; EGM_DISPATCH_DTYPE(dtype, __VA_ARGS__); } \
@@ -210,7 +116,7 @@ extern "C" int egm_bn_ew_fwd(int dtype, int mode, const void* y, int ldy, const 
                              int ldp, float alpha, void* out, int ldo, long long npix, int C, egm_stream_t s) {
     EGM_REQ_VEC("bn_ew_fwd", y, ldy, C); EGM_REQ_VEC("bn_ew_fwd", p, ldp, C); EGM_REQ_VEC("bn_ew_fwd", out, ldo, C);
     EGM_REQUIRE(scale && shift && npix > 0 && C <= 2048, "bn_ew_fwd: bad args (C <= 2048)");
-    EGM_EW_DISPATCH(mode, hipLaunchKernelGGL((bn_ew_fwd_kernel<T, MODE>), dim3(stream_grid(npix * (C >> 3))), dim3(256), 0, (hipStream_t)s,
+    EGM_EW_DISPATCH(mode, hipLaunchKernelGGL((bn_ew_fwd_kernel<T, MODE>), dim3(egm_stream_grid(npix * (C >> 3))), dim3(256), 0, (hipStream_t)s,
                                              (const T*)y, ldy, scale, shift, act, (const T*)p, ldp, alpha, (T*)out, ldo, npix, C));
     EGM_CHECK_LAUNCH("bn_ew_fwd");
     return EGM_OK;
@@ -235,7 +141,7 @@ extern "C" int egm_bn_ew_bwd_apply(int dtype, int mode, const void* g, int ldg, 
     EGM_REQ_VEC("bn_ew_bwd_apply", g, ldg, C); EGM_REQ_VEC("bn_ew_bwd_apply", q, ldq, C); EGM_REQ_VEC("bn_ew_bwd_apply", y, ldy, C);
     EGM_REQ_VEC("bn_ew_bwd_apply", dy, lddy, C); EGM_REQ_VEC("bn_ew_bwd_apply", dp, lddp, C);
     EGM_REQUIRE(cf_4xC && npix > 0 && C <= 2048, "bn_ew_bwd_apply: bad args (C <= 2048)");
-    EGM_EW_DISPATCH(mode, hipLaunchKernelGGL((bn_ew_bwd_apply_kernel<T, MODE>), dim3(stream_grid(npix * (C >> 3))), dim3(256), 0,
+    EGM_EW_DISPATCH(mode, hipLaunchKernelGGL((bn_ew_bwd_apply_kernel<T, MODE>), dim3(egm_stream_grid(npix * (C >> 3))), dim3(256), 0,
                                              (hipStream_t)s, (const T*)g, ldg, (const T*)q, ldq, (const T*)y, ldy, cf_4xC, act, alpha,
                                              (T*)dy, lddy, (T*)dp, lddp, npix, C));
     EGM_CHECK_LAUNCH("bn_ew_bwd_apply");

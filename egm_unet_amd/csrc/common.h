@@ -189,6 +189,18 @@ static inline int egm_partial_blocks(long long npix, int C) {
     return (int)b;
 }
 
+// Workgroups of a grid-stride streaming launch of 256-thread blocks, one item per thread and sweep.
+static inline int egm_stream_grid(long long total_threads) {
+    long long b = (total_threads + 255) / 256;
+    if (b > 256 * 16) b = 256 * 16;          // ~16 blocks per CU, grid-stride the rest
+    if (b < 1) b = 1;
+    return (int)b;
+}
+// What every launcher asks of an NHWC activation tensor it reads or writes in 8-channel (16-byte bf16) vectors.
+#define EGM_REQ_VEC(name, ptr, ld, C)                                                                      \
+    EGM_REQUIRE((ptr) != nullptr && egm_aligned16(ptr) && (C) > 0 && (C) % 8 == 0 && (ld) >= (C) && (ld) % 8 == 0, \
+                name ": bad tensor (ptr/alignment/C=%d/ld=%d)", (int)(C), (int)(ld))
+
 // Index arithmetic of the streaming kernels without 64-bit divisions.  A 64-bit divide by a run-time value is ~60 VALU instructions on
 // this part (no hardware divider): the (item -> pixel, channel vector) and (pixel -> row, column) splits of an element-wise or stencil
 // kernel cost more than its arithmetic.  Channel-vector counts are powers of two in every network here (a shift); everything else is

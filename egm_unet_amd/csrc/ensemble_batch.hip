@@ -78,8 +78,6 @@ __global__ __launch_bounds__(256) void unet_vresample_norm_kernel(const unsigned
     }
 }
 
-inline int stream_grid(long long n) { long long b = (n + 255) / 256; if (b > 4096) b = 4096; return (int)(b < 1 ? 1 : b); }
-
 }  // namespace
 
 extern "C" int egm_unet_preprocess_batch_u8(const void* imgs_bhwc3, int B, int H, int W, float* out_bchw, int oh, int ow, const int* xbounds,
@@ -96,12 +94,12 @@ extern "C" int egm_unet_preprocess_batch_u8(const void* imgs_bhwc3, int B, int H
     const unsigned char* src = (const unsigned char*)imgs_bhwc3;
     if (xbounds) {
         const long long rows = (long long)B * H;
-        hipLaunchKernelGGL(unet_hresample_rows_kernel, dim3(stream_grid(rows * ow)), dim3(256), 0, (hipStream_t)s, src, rows, W,
+        hipLaunchKernelGGL(unet_hresample_rows_kernel, dim3(egm_stream_grid(rows * ow)), dim3(256), 0, (hipStream_t)s, src, rows, W,
                            (unsigned char*)tmp_bhwc3, ow, xbounds, xcoefs, xksize);
         EGM_CHECK_LAUNCH("unet_preprocess_batch_u8 (horizontal)");
         src = (const unsigned char*)tmp_bhwc3;
     }
-    hipLaunchKernelGGL(unet_vresample_norm_kernel, dim3(stream_grid((long long)B * oh * ow)), dim3(256), 0, (hipStream_t)s, src, B, H, ow, out_bchw,
+    hipLaunchKernelGGL(unet_vresample_norm_kernel, dim3(egm_stream_grid((long long)B * oh * ow)), dim3(256), 0, (hipStream_t)s, src, B, H, ow, out_bchw,
                        oh, ybounds, ycoefs, yksize, mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0], std3_host[1], std3_host[2]);
     EGM_CHECK_LAUNCH("unet_preprocess_batch_u8 (vertical)");
     return EGM_OK;

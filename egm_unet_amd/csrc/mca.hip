@@ -20,12 +20,6 @@
 
 namespace {
 
-inline int stream_grid(long long total_threads) {
-    long long b = (total_threads + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 __device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + expf(-v)); }
 
 // ---- pass 1: one block per image row (n,h).  MODE 0: sums of (a, a^2); MODE 1: sums of (a*b, (a*b)^2);
@@ -727,11 +721,8 @@ bool mca_c_ok(int C) { return C >= 8 && C <= 512 && (C & (C - 1)) == 0; }
 
 }  // namespace
 
-#define EGM_REQ_VEC(name, ptr, ld, C)                                                                      \
-    EGM_REQUIRE((ptr) != nullptr && egm_aligned16(ptr) && (C) > 0 && (C) % 8 == 0 && (ld) >= (C) && (ld) % 8 == 0, \
-                name ": bad tensor (ptr/alignment/C=%d/ld=%d)", (int)(C), (int)(ld))
 #define EGM_REQ_SHAPE(name) EGM_REQUIRE(N > 0 && H > 0 && W > 0, name ": bad shape")
-#define EGM_MCA_GRID stream_grid((long long)N * H * W * (C / 8))
+#define EGM_MCA_GRID egm_stream_grid((long long)N * H * W * (C / 8))
 
 extern "C" long long egm_mca_reduce_workspace(int N, int H, int W, int C) {
     if (N <= 0 || H <= 0 || W <= 0 || !mca_c_ok(C)) return -1;

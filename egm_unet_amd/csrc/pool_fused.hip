@@ -13,17 +13,11 @@
 // except for the fp32 BatchNorm partial sums, which are accumulated in a different pixel order.
 #include "common.h"
 #include "bn_elem.h"
+#include "bn_frames.h"
 
 namespace {
 
 __device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + expf(-v)); }
-
-inline int stream_grid(long long total_threads) {
-    long long b = (total_threads + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 // window w of an [N, H, W] image grid with even H, W -> pixel index of its top-left corner and of the pooled pixel
 // (32-bit arithmetic: the launchers require N*H*W*C/8 < 2^31; a 64-bit division per item costs more than the item's arithmetic)
@@ -88,17 +82,10 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const T* __rest
                                                                  const float* __restrict__ rstd, int act, long long nwin, int Ho, int Wo,
                                                                  int C, float* __restrict__ out) {
     __shared__ float red[2 * 256 * 8];
-    const int ncv = C >> 3, rows = 256 / ncv, W = Wo * 2;
-    const int tid = threadIdx.x, cv = tid % ncv, row = tid / ncv;
-    for (int c = tid; c < C; c += 256) { red[c] = scale[c]; red[C + c] = shift[c]; red[2 * C + c] = mean[c]; red[3 * C + c] = rstd[c]; }
-    __syncthreads();
-    float sc[8], sh[8], mu[8], rs[8], s[8], q[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sc[j] = red[cv * 8 + j]; sh[j] = red[C + cv * 8 + j]; mu[j] = red[2 * C + cv * 8 + j]; rs[j] = red[3 * C + cv * 8 + j]; }
-    __syncthreads();                                            // red[] is reused for the reduction below
-    zero8(s); zero8(q);
-    if (row < rows) {
-        for (long long w = (long long)blockIdx.x * rows + row; w < nwin; w += (long long)gridDim.x * rows) {
+    const int W = Wo * 2;
+    bn_partials<true>(red, scale, shift, mean, rstd, nwin, C, out, blockIdx.x, gridDim.x,
+        [&](long long w, int cv, const float (&sc)[8], const float (&sh)[8], const float (&mu)[8], const float (&rs)[8], float (&s)[8],
+            float (&q)[8]) __attribute__((always_inline)) {
             long long base, pooled;
             window_of((unsigned)w, Ho, Wo, W, base, pooled);
             const long long off[4] = {base, base + 1, base + W, base + W + 1};
@@ -118,17 +105,7 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const T* __rest
                     const float g = gs[k][j] * act_grad<sizeof(T) == 2>(fmaf(yv[k][j], sc[j], sh[j]), act);
                     s[j] += g; q[j] += g * (yv[k][j] - mu[j]) * rs[j];
                 }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { red[tid * 8 + j] = s[j]; red[(256 + tid) * 8 + j] = q[j]; }
-    __syncthreads();
-    for (int t = tid; t < 2 * C; t += 256) {                    // thread t sums column t over the `rows` window rows (fixed order)
-        const int which = t / C, c = t - which * C, ccv = c >> 3, j = c & 7;
-        float v = 0.f;
-        for (int r = 0; r < rows; ++r) v += red[(which * 256 + r * ncv + ccv) * 8 + j];
-        out[((long long)blockIdx.x * 2 + which) * C + c] = v;
-    }
+        });
 }
 
 // ---- BatchNorm backward, second stage: dy = scale*dzp + cb + cc*y with the same on-the-fly dz ----------------------------------------
@@ -143,11 +120,7 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const T* __restr
     for (int c = threadIdx.x; c < C; c += 256) {
         const float scv = scale[c];
         float cbv = 0.f, ccv = 0.f;
-        if (train) {
-            const float m0 = sums[c] * inv_count, m1 = sums[C + c] * inv_count;
-            ccv = -scv * rstd[c] * m1;
-            cbv = -scv * m0 - ccv * mean[c];
-        }
+        if (train) bn_bwd_cb_cc(scv, sums[c], sums[C + c], inv_count, mean[c], rstd[c], cbv, ccv);
         cf[c] = scv; cf[C + c] = shift[c]; cf[2 * C + c] = cbv; cf[3 * C + c] = ccv;
     }
     __syncthreads();
@@ -277,9 +250,6 @@ inline int group_for(int ncv) { int g = 1; while (g < ncv && g < 64) g <<= 1; re
 
 }  // namespace
 
-#define EGM_REQ_VEC(name, ptr, ld, C)                                                                      \
-    EGM_REQUIRE((ptr) != nullptr && egm_aligned16(ptr) && (C) > 0 && (C) % 8 == 0 && (ld) >= (C) && (ld) % 8 == 0, \
-                name ": bad tensor (ptr/alignment/C=%d/ld=%d)", (int)(C), (int)(ld))
 #define EGM_REQ_POOL_SHAPE(name) \
     EGM_REQUIRE(N > 0 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1) && C <= 1024 && (long long)N * H * W * (C / 8) < (1LL << 31), \
                 name ": H and W must be even, C <= 1024, N*H*W*C/8 < 2^31 (got %d x %d, C=%d)", H, W, C)
@@ -296,7 +266,7 @@ extern "C" int egm_bn_act_fwd_pool(int dtype, const void* y, int ldy, const floa
     EGM_REQUIRE(scale && shift, "bn_act_fwd_pool: bad args");
     const int Ho = H / 2, Wo = W / 2;
     const long long nwin = (long long)N * Ho * Wo;
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_act_fwd_pool_kernel<T>), dim3(stream_grid(nwin * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_act_fwd_pool_kernel<T>), dim3(egm_stream_grid(nwin * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)y, ldy, scale, shift, act, (T*)z, ldz, (T*)pooled, ldp, nwin, Ho, Wo, C));
     EGM_CHECK_LAUNCH("bn_act_fwd_pool");
     return EGM_OK;
@@ -332,7 +302,7 @@ extern "C" int egm_bn_pool_bwd_apply(int dtype, const void* gskip, int ldgs, con
     EGM_REQUIRE(scale && shift && save_mean && save_rstd && sums, "bn_pool_bwd_apply: bad args");
     const int Ho = H / 2, Wo = W / 2;
     const long long nwin = (long long)N * Ho * Wo;
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_pool_bwd_apply_kernel<T>), dim3(stream_grid(nwin * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_pool_bwd_apply_kernel<T>), dim3(egm_stream_grid(nwin * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)gskip, ldgs, (const T*)gpool, ldgp, (const T*)y, ldy, scale, shift, save_mean, save_rstd,
                                                  act, train, sums, 1.f / (float)((long long)N * H * W), (T*)dy, lddy, nwin, Ho, Wo, C));
     EGM_CHECK_LAUNCH("bn_pool_bwd_apply");
@@ -346,7 +316,7 @@ extern "C" int egm_gate3_fwd_pool(int dtype, const void* x, int ldx, const void*
     EGM_REQ_POOL_SHAPE("gate3_fwd_pool");
     const int Ho = H / 2, Wo = W / 2;
     const long long nwin = (long long)N * Ho * Wo;
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate3_fwd_pool_kernel<T>), dim3(stream_grid(nwin * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate3_fwd_pool_kernel<T>), dim3(egm_stream_grid(nwin * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)x, ldx, (const T*)t, ldt, (T*)out, ldo, (T*)pooled, ldp, nwin, Ho, Wo, C));
     EGM_CHECK_LAUNCH("gate3_fwd_pool");
     return EGM_OK;
@@ -360,7 +330,7 @@ extern "C" int egm_gate3_pool_bwd(int dtype, const void* gskip, int ldgs, const 
     const int Ho = H / 2, Wo = W / 2;
     const long long nwin = (long long)N * Ho * Wo;
     const int G = group_for(C / 8);
-    const int grid = stream_grid(nwin * G);
+    const int grid = egm_stream_grid(nwin * G);
     EGM_DISPATCH_DTYPE(dtype, EGM_GROUP_SWITCH(G, hipLaunchKernelGGL((gate3_pool_bwd_kernel<T, GROUP>), dim3(grid), dim3(256), 0, (hipStream_t)s,
                                                                      (const T*)gskip, ldgs, (const T*)gpool, ldgp, (const T*)x, ldx, (const T*)t, ldt,
                                                                      (T*)dx, lddx, (T*)dt, lddt, nwin, Ho, Wo, C)));

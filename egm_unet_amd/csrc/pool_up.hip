@@ -7,13 +7,6 @@
 
 namespace {
 
-inline int stream_grid(long long total_threads) {
-    long long b = (total_threads + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // ---- NCHW fp32 <-> NHWC T (module boundary: few channels) -----------------------------------------
 template <typename T>
 __global__ void nchw_to_nhwc_kernel(const float* __restrict__ src, T* __restrict__ dst, int ld, int N, int C, long long HW) {
@@ -536,14 +529,11 @@ __global__ void fill_f32_kernel(float* __restrict__ y, float v, long long n) {
 
 }  // namespace
 
-#define EGM_REQ_VEC(name, ptr, ld, C)                                                                      \
-    EGM_REQUIRE((ptr) != nullptr && egm_aligned16(ptr) && (C) > 0 && (C) % 8 == 0 && (ld) >= (C) && (ld) % 8 == 0, \
-                name ": bad tensor (ptr/alignment/C=%d/ld=%d)", (int)(C), (int)(ld))
 
 extern "C" int egm_nchw_to_nhwc(int dtype, const void* src, void* dst, int ld, int N, int C, int H, int W, egm_stream_t s) {
     EGM_REQUIRE(src && dst && egm_aligned16(dst) && N > 0 && C > 0 && H > 0 && W > 0 && ld >= C && ld % 8 == 0, "nchw_to_nhwc: bad args");
     const long long HW = (long long)H * W;
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), dim3(stream_grid(N * HW)), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), dim3(egm_stream_grid(N * HW)), dim3(256), 0, (hipStream_t)s,
                                                  (const float*)src, (T*)dst, ld, N, C, HW));
     EGM_CHECK_LAUNCH("nchw_to_nhwc");
     return EGM_OK;
@@ -551,7 +541,7 @@ extern "C" int egm_nchw_to_nhwc(int dtype, const void* src, void* dst, int ld, i
 extern "C" int egm_nhwc_to_nchw(int dtype, const void* src, int ld, void* dst, int N, int C, int H, int W, egm_stream_t s) {
     EGM_REQUIRE(src && dst && egm_aligned16(src) && N > 0 && C > 0 && H > 0 && W > 0 && ld >= C && ld % 8 == 0, "nhwc_to_nchw: bad args");
     const long long HW = (long long)H * W;
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((nhwc_to_nchw_kernel<T>), dim3(stream_grid(N * HW)), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((nhwc_to_nchw_kernel<T>), dim3(egm_stream_grid(N * HW)), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)src, ld, (float*)dst, N, C, HW));
     EGM_CHECK_LAUNCH("nhwc_to_nchw");
     return EGM_OK;
@@ -562,7 +552,7 @@ extern "C" int egm_maxpool2_fwd(int dtype, const void* x, int ldx, void* y, int 
     EGM_REQ_VEC("maxpool2_fwd", y, ldy, C);
     EGM_REQUIRE(N > 0 && H >= 2 && W >= 2, "maxpool2_fwd: bad shape");
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 8);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((maxpool2_fwd_kernel<T>), dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((maxpool2_fwd_kernel<T>), dim3(egm_stream_grid(total)), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)x, ldx, (T*)y, ldy, N, H, W, C));
     EGM_CHECK_LAUNCH("maxpool2_fwd");
     return EGM_OK;
@@ -575,10 +565,10 @@ extern "C" int egm_maxpool2_bwd(int dtype, const void* x, int ldx, const void* d
     EGM_REQUIRE(N > 0 && H >= 2 && W >= 2, "maxpool2_bwd: bad shape");
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 8);
     EGM_DISPATCH_DTYPE(dtype, {
-        hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)s, (const T*)x, ldx,
+        hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(egm_stream_grid(total)), dim3(256), 0, (hipStream_t)s, (const T*)x, ldx,
                            (const T*)dy, lddy, (const T*)nullptr, 0, (T*)dx, lddx, N, H, W, C);
         if ((H & 1) || (W & 1))
-            hipLaunchKernelGGL((zero_tail_kernel<T>), dim3(stream_grid((long long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)s,
+            hipLaunchKernelGGL((zero_tail_kernel<T>), dim3(egm_stream_grid((long long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                (T*)dx, lddx, N, H, W, C);
     });
     EGM_CHECK_LAUNCH("maxpool2_bwd");
@@ -593,7 +583,7 @@ extern "C" int egm_maxpool2_bwd_add(int dtype, const void* x, int ldx, const voi
     EGM_REQ_VEC("maxpool2_bwd_add", dx, lddx, C);
     EGM_REQUIRE(N > 0 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1), "maxpool2_bwd_add: H and W must be even (got %d x %d)", H, W);
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 8);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)s, (const T*)x, ldx,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(egm_stream_grid(total)), dim3(256), 0, (hipStream_t)s, (const T*)x, ldx,
                                                  (const T*)dy, lddy, (const T*)add, ldadd, (T*)dx, lddx, N, H, W, C));
     EGM_CHECK_LAUNCH("maxpool2_bwd_add");
     return EGM_OK;
@@ -605,7 +595,7 @@ extern "C" int egm_sum4_hp(int dtype, const void* a, int lda, const void* b, int
     if (c != nullptr) EGM_REQ_VEC("sum4_hp", c, ldc, C);
     if (d != nullptr) EGM_REQ_VEC("sum4_hp", d, ldd, C);
     EGM_REQUIRE(N > 0 && H > 0 && W > 0, "sum4_hp: bad shape");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((sum4_hp_kernel<T>), dim3(stream_grid((long long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((sum4_hp_kernel<T>), dim3(egm_stream_grid((long long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)a, lda, (const T*)b, ldb, (const T*)c, ldc, (const T*)d, ldd, (T*)out, ldo, N, H, W, C));
     EGM_CHECK_LAUNCH("sum4_hp");
     return EGM_OK;
@@ -618,7 +608,7 @@ extern "C" int egm_upcat_fwd(int dtype, const void* skip, int lds, const void* l
     EGM_REQ_VEC("upcat_fwd", out, ldo, Cs + Cl);
     EGM_REQUIRE(N > 0 && Hl > 0 && Wl > 0 && Hs >= 2 * Hl && Ws >= 2 * Wl, "upcat_fwd: skip must be at least 2x the low-res size");
     const long long total = (long long)N * Hs * Ws * ((skip ? Cs + Cl : Cl) / 8);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((upcat_fwd_kernel<T>), dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((upcat_fwd_kernel<T>), dim3(egm_stream_grid(total)), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)skip, lds, (const T*)low, ldl, (T*)out, ldo, N, Hs, Ws, Cs, Hl, Wl, Cl));
     EGM_CHECK_LAUNCH("upcat_fwd");
     return EGM_OK;
@@ -636,7 +626,7 @@ extern "C" int egm_upcat_bwd_low(int dtype, const void* dout, int ldo, void* dlo
         EGM_CHECK_LAUNCH("upcat_bwd_low");
         return EGM_OK;
     }
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((upcat_bwd_low_kernel<T>), dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((upcat_bwd_low_kernel<T>), dim3(egm_stream_grid(total)), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)dout, ldo, (T*)dlow, ldl, N, Hs, Ws, Cs, Hl, Wl, Cl));
     EGM_CHECK_LAUNCH("upcat_bwd_low");
     return EGM_OK;
@@ -648,7 +638,7 @@ extern "C" int egm_dwconv3_fwd(int dtype, const void* x, int ldx, const float* w
     EGM_REQ_VEC("dwconv3_fwd", y, ldy, C);
     EGM_REQUIRE(w && N > 0 && H > 0 && W > 0, "dwconv3_fwd: bad args");
     const long long total = (long long)N * H * W * (C / 8);
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((dwconv3_fwd_kernel<T>), dim3(stream_grid(total)), dim3(256), (size_t)C * 10 * sizeof(float), (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((dwconv3_fwd_kernel<T>), dim3(egm_stream_grid(total)), dim3(256), (size_t)C * 10 * sizeof(float), (hipStream_t)s,
                                                  (const T*)x, ldx, w, b, scale, (T*)y, ldy, N, H, W, C));
     EGM_CHECK_LAUNCH("dwconv3_fwd");
     return EGM_OK;
@@ -673,7 +663,7 @@ extern "C" int egm_dwconv3_bwd(int dtype, const void* x, int ldx, const void* dy
     const long long npix = (long long)N * H * W;
     const int nb = dw_blocks(npix, C);
     EGM_DISPATCH_DTYPE(dtype, {
-        hipLaunchKernelGGL((dwconv3_bwd_data_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), (size_t)C * 9 * sizeof(float), (hipStream_t)s, (const T*)dy,
+        hipLaunchKernelGGL((dwconv3_bwd_data_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), (size_t)C * 9 * sizeof(float), (hipStream_t)s, (const T*)dy,
                            lddy, w, scale, (T*)dx, lddx, N, H, W, C);
         hipLaunchKernelGGL((dwconv3_bwd_param_kernel<T>), dim3(nb), dim3(256), (256 * 8 + (size_t)C * 10) * sizeof(float), (hipStream_t)s, (const T*)x, ldx,
                            (const T*)dy, lddy, w, b, scale, (float*)workspace, N, H, W, C);
@@ -742,7 +732,7 @@ extern "C" int egm_shuffle2x2_fwd(int dtype, const void* y4, int ld4, const floa
                                   int Ho, int Wo, int oy, int ox, egm_stream_t s) {
     EGM_REQ_VEC("shuffle2x2_fwd", out, ldo, C);
     EGM_REQUIRE(y4 && ld4 >= 4 * C && N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0, "shuffle2x2_fwd: bad args");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((shuffle2x2_fwd_kernel<T>), dim3(stream_grid((long long)N * Ho * Wo * (C / 8))), dim3(256), 0,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((shuffle2x2_fwd_kernel<T>), dim3(egm_stream_grid((long long)N * Ho * Wo * (C / 8))), dim3(256), 0,
                                                  (hipStream_t)s, (const T*)y4, ld4, bias, bias_n, (T*)out, ldo, N, H, W, C, Ho, Wo, oy, ox));
     EGM_CHECK_LAUNCH("shuffle2x2_fwd");
     return EGM_OK;
@@ -751,14 +741,14 @@ extern "C" int egm_shuffle2x2_bwd(int dtype, const void* g, int ldg, void* d4, i
                                   egm_stream_t s) {
     EGM_REQ_VEC("shuffle2x2_bwd", g, ldg, C);
     EGM_REQUIRE(d4 && ld4 >= 4 * C && N > 0 && H > 0 && W > 0, "shuffle2x2_bwd: bad args");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((shuffle2x2_bwd_kernel<T>), dim3(stream_grid((long long)N * H * W * 4 * (C / 8))), dim3(256), 0,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((shuffle2x2_bwd_kernel<T>), dim3(egm_stream_grid((long long)N * H * W * 4 * (C / 8))), dim3(256), 0,
                                                  (hipStream_t)s, (const T*)g, ldg, (T*)d4, ld4, N, H, W, C, Ho, Wo, oy, ox));
     EGM_CHECK_LAUNCH("shuffle2x2_bwd");
     return EGM_OK;
 }
 extern "C" int egm_convT2x2_pack(float* w_iohw, float* w4, int Cin, int Cout, int CoutP, int to_packed, egm_stream_t s) {
     EGM_REQUIRE(w_iohw && w4 && Cin > 0 && Cout > 0 && CoutP >= Cout, "convT2x2_pack: bad args");
-    hipLaunchKernelGGL(convT_pack_kernel, dim3(stream_grid((long long)4 * CoutP * Cin)), dim3(256), 0, (hipStream_t)s, w_iohw, w4, Cin, Cout, CoutP,
+    hipLaunchKernelGGL(convT_pack_kernel, dim3(egm_stream_grid((long long)4 * CoutP * Cin)), dim3(256), 0, (hipStream_t)s, w_iohw, w4, Cin, Cout, CoutP,
                        to_packed);
     EGM_CHECK_LAUNCH("convT2x2_pack");
     return EGM_OK;
@@ -770,7 +760,7 @@ extern "C" int egm_axpby(int dtype, const void* a, int lda, float alpha, const v
     EGM_REQ_VEC("axpby", out, ldo, C);
     if (b) EGM_REQ_VEC("axpby", b, ldb, C);
     EGM_REQUIRE(npix > 0, "axpby: bad npix");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((axpby_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((axpby_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s,
                                                  (const T*)a, lda, alpha, (const T*)b, ldb, beta, (T*)out, ldo, npix, C));
     EGM_CHECK_LAUNCH("axpby");
     return EGM_OK;
@@ -780,14 +770,14 @@ extern "C" int egm_sum4(int dtype, const void* a, int lda, const void* b, int ld
     EGM_REQ_VEC("sum4", a, lda, C); EGM_REQ_VEC("sum4", b, ldb, C); EGM_REQ_VEC("sum4", c, ldc, C); EGM_REQ_VEC("sum4", out, ldo, C);
     if (d) EGM_REQ_VEC("sum4", d, ldd, C);
     EGM_REQUIRE(npix > 0, "sum4: bad npix");
-    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((sum4_kernel<T>), dim3(stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s, (const T*)a,
+    EGM_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((sum4_kernel<T>), dim3(egm_stream_grid(npix * (C / 8))), dim3(256), 0, (hipStream_t)s, (const T*)a,
                                                  lda, (const T*)b, ldb, (const T*)c, ldc, (const T*)d, ldd, (T*)out, ldo, npix, C));
     EGM_CHECK_LAUNCH("sum4");
     return EGM_OK;
 }
 extern "C" int egm_vec_add_f32(float* y, const float* x, long long n, egm_stream_t s) {
     EGM_REQUIRE(y && x && n > 0, "vec_add_f32: bad args");
-    hipLaunchKernelGGL(vec_add_f32_kernel, dim3(stream_grid(n)), dim3(256), 0, (hipStream_t)s, y, x, n);
+    hipLaunchKernelGGL(vec_add_f32_kernel, dim3(egm_stream_grid(n)), dim3(256), 0, (hipStream_t)s, y, x, n);
     EGM_CHECK_LAUNCH("vec_add_f32");
     return EGM_OK;
 }
@@ -805,14 +795,14 @@ extern "C" int egm_copy_cols_f32(const float* src, int ld_src, int col0_src, flo
                                  egm_stream_t s) {
     EGM_REQUIRE(src && dst && rows > 0 && ncols > 0 && col0_src >= 0 && col0_dst >= 0 && col0_src + ncols <= ld_src && col0_dst + ncols <= ld_dst,
                 "copy_cols_f32: bad args");
-    hipLaunchKernelGGL(copy_cols_f32_kernel, dim3(stream_grid((long long)rows * ncols)), dim3(256), 0, (hipStream_t)s, src, ld_src, col0_src, dst,
+    hipLaunchKernelGGL(copy_cols_f32_kernel, dim3(egm_stream_grid((long long)rows * ncols)), dim3(256), 0, (hipStream_t)s, src, ld_src, col0_src, dst,
                        ld_dst, col0_dst, rows, ncols);
     EGM_CHECK_LAUNCH("copy_cols_f32");
     return EGM_OK;
 }
 extern "C" int egm_fill_f32(float* y, float v, long long n, egm_stream_t s) {
     EGM_REQUIRE(y && n > 0, "fill_f32: bad args");
-    hipLaunchKernelGGL(fill_f32_kernel, dim3(stream_grid(n)), dim3(256), 0, (hipStream_t)s, y, v, n);
+    hipLaunchKernelGGL(fill_f32_kernel, dim3(egm_stream_grid(n)), dim3(256), 0, (hipStream_t)s, y, v, n);
     EGM_CHECK_LAUNCH("fill_f32");
     return EGM_OK;
 }

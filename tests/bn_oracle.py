@@ -1,5 +1,6 @@
-"""Plain reference of the BatchNorm passes (csrc/bn.hip, csrc/bn_fused.hip, csrc/bn_dz_fused.hip on the element formulas of
-csrc/bn_elem.h), pass by pass, with the case tables and the error bounds of test_bn_cpu.py / test_gpu_bn.py.
+"""Plain reference of the BatchNorm passes (csrc/bn.hip, csrc/bn_fused.hip, csrc/bn_dz_fused.hip and the BatchNorm passes of
+csrc/pool_fused.hip, on the element formulas of csrc/bn_elem.h), pass by pass, with the case tables and the error bounds of
+test_bn_cpu.py / test_gpu_bn.py.
 
 One numpy function per pass on [npix, C] arrays (NHWC with the pixels flattened), in the precision of its operands: float64 in every
 bounded comparison, float32 or integers in the exact ones.  Nothing is copied from the kernels: the activations and their derivatives
@@ -465,6 +466,58 @@ def mca_exact(case, k, shape, a, rt):
     dyadic(raw, 8, "mca dz", 2 ** 12)
     dz = rt(raw)
     return dz, exact_bwd_sums(dz, case, a, q=16, what="mca dz")
+
+
+# the 2x2 max pool fused around a BatchNorm (csrc/pool_fused.hip): (N, H, W, C), the smallest shapes that reach each branch -- one
+# window; 256 % (C/8) != 0 with rows = 85; a middle case; rows = 2 with the staged coefficients filling the reduction's LDS; 2304
+# windows, more than the 1024 x 2 window rows of the capped reduction grid (the block loop wraps) and an apply grid at its cap
+POOL_SHAPES = [(1, 2, 2, 8), (2, 4, 6, 24), (2, 6, 4, 64), (1, 4, 4, 1024), (1, 96, 96, 1024)]
+POOL_WIDE = (2, 6, 4, 64)
+
+
+def pool_windows(a, shape):
+    """[N H W][C] -> [N][H/2][W/2][4][C]: the pixels of each 2x2 window in the scan order (0,0), (0,1), (1,0), (1,1)."""
+    N, H, W = shape
+    return a.reshape(N, H // 2, 2, W // 2, 2, -1).transpose(0, 1, 3, 2, 4, 5).reshape(N, H // 2, W // 2, 4, -1)
+
+
+def pool_pixels(w, shape):
+    """The inverse of pool_windows."""
+    N, H, W = shape
+    return w.reshape(N, H // 2, W // 2, 2, 2, -1).transpose(0, 1, 3, 2, 4, 5).reshape(N * H * W, -1)
+
+
+def pool_max(z, shape):
+    """-> [N H/2 W/2][C], the 2x2 maximum."""
+    return pool_windows(z, shape).max(3).reshape(-1, z.shape[1])
+
+
+def pool_dz(z, gskip, gpool, shape, rt=ID):
+    """The gradient a BatchNorm whose output z feeds a skip connection AND a 2x2 max pool receives: dz = rt(gskip + [first maximum of
+    the window in scan order] gpool) (torch max_pool2d routes a tie to the first; np.argmax returns the first occurrence too).
+    gskip [N H W][C], gpool [N H/2 W/2][C]."""
+    zw = pool_windows(z, shape)
+    hit = zw.argmax(3)[:, :, :, None, :] == np.arange(4)[None, None, None, :, None]
+    return rt(pool_pixels(hit * gpool.reshape(zw.shape[:3] + (1, -1)), shape) + gskip)
+
+
+def pool_case(shape, seed):
+    """The exact case of the shape's pixel count with gskip = its dz and gpool = the first N H/2 W/2 rows of its g."""
+    N, H, W, C = shape
+    c = exact_case(N * H * W, C, seed)
+    c["gskip"], c["gpool"] = c["dz"], c["g"][:N * (H // 2) * (W // 2)]
+    return c
+
+
+def pool_exact(c, shape, a):
+    """z, its 2x2 maximum, dz = gskip + scatter(gpool) (integers in [-6, 6]) and the backward sums behind it, all proved exact."""
+    y = np.asarray(c["y"], np.float64)
+    v = y * c["scale"] + c["shift"]
+    dyadic(v, 2, "v", 2 ** 8)
+    z = act(v, a)
+    dz = pool_dz(z, np.asarray(c["gskip"], np.float64), np.asarray(c["gpool"], np.float64), shape[:3])
+    dyadic(dz, 1, "pool dz", 2 ** 8)
+    return {"z": z, "pooled": pool_max(z, shape[:3]), "dz": dz, "sums": exact_bwd_sums(dz, c, a, what="pool dz")}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

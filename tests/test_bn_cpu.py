@@ -2,7 +2,7 @@
 
 test_gpu_bn.py judges every kernel of csrc/bn.hip, csrc/bn_fused.hip and csrc/bn_dz_fused.hip by that oracle, so the oracle is pinned
 here by something that shares nothing with it: float64 torch autograd of nn.BatchNorm2d (train and eval) behind ReLU / Sigmoid / SiLU,
-of the gate and residual-tail expressions, and of a 1 x 1 classifier behind BatchNorm + ReLU.  Then the exact cases: every table case
+of the gate and residual-tail expressions, of a 1 x 1 classifier behind BatchNorm + ReLU, and of a 2x2 max pool beside a skip connection.  Then the exact cases: every table case
 is proved exact (check_bounds) and equal to the same computation in int64.  Then the two conditions of the float cases, on the
 reference alone: the first-order bound of the relative error of rstd stays below 2^-10, and at most 0.1 % of the ReLU / residual-mask
 decisions lie within their bound of zero."""
@@ -230,6 +230,34 @@ def test_exact_producers_are_exact(a):
             dz, _ = B.mca_exact(c, B.mca_case(shape, C, 400), shape, a, r)
             cb, cc = B.exact_coefs32(c["sums"], npix, c["scale"], c["mean"], c["rstd"], True)
             B.exact_apply32(dz, c["y"], c["scale"], c["shift"], cb, cc, a)
+
+
+@pytest.mark.parametrize("a", ["none", "relu"])
+@pytest.mark.parametrize("shape", B.POOL_SHAPES, ids=str)
+def test_pool_dz_equals_autograd(shape, a):
+    """The window dz of the pool fusions is float64 autograd of loss = <gskip, z> + <gpool, max_pool2d(z, 2)> on the exact cases
+    themselves (integer z: many windows hold a tie, so the first-maximum rule decides); the exact results are storage values, the sums
+    behind them are proved exact (pool_exact raises otherwise) and every fma of the apply pass is exact in float64."""
+    N, H, W, C = shape
+    c = B.pool_case(shape, 100 + C)
+    r = B.pool_exact(c, shape, a)
+    zw = B.pool_windows(r["z"], shape[:3])
+    assert shape == (1, 2, 2, 8) or float((np.sort(zw, 3)[:, :, :, 3] == np.sort(zw, 3)[:, :, :, 2]).mean()) > 0.1, "ties are meant to be frequent"
+    zt = torch.from_numpy(np.ascontiguousarray(r["z"].reshape(N, H, W, C))).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    pooled = torch.nn.functional.max_pool2d(zt, 2)
+    gp = torch.from_numpy(np.ascontiguousarray(np.asarray(c["gpool"], np.float64).reshape(N, H // 2, W // 2, C))).permute(0, 3, 1, 2)
+    gs = torch.from_numpy(np.ascontiguousarray(np.asarray(c["gskip"], np.float64).reshape(N, H, W, C))).permute(0, 3, 1, 2)
+    ((pooled * gp).sum() + (zt * gs).sum()).backward()
+    assert np.array_equal(zt.grad.permute(0, 2, 3, 1).reshape(-1, C).numpy(), r["dz"])
+    assert np.array_equal(pooled.detach().permute(0, 2, 3, 1).reshape(-1, C).numpy(), r["pooled"])
+    rt = B.round_to(torch.bfloat16)
+    for k in ("z", "pooled", "dz"):
+        assert np.array_equal(rt(r[k]), r[k]), k + " of an exact pool case is meant to be a bfloat16 value"
+    npix = N * H * W
+    if shape == B.POOL_SHAPES[-1]:                     # the reduction's block loop wraps: more window rows than 1024 blocks x 2
+        assert npix // 4 > 2 * 1024 and B.partial_blocks(npix // 4, C) == 1024
+    cb, cc = B.exact_coefs32(c["sums"], npix, c["scale"], c["mean"], c["rstd"], True)
+    B.exact_apply32(r["dz"], c["y"], c["scale"], c["shift"], cb, cc, a)
 
 
 def test_boundary_clear():

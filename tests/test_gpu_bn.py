@@ -1,5 +1,5 @@
-"""The BatchNorm kernels of csrc/bn.hip, csrc/bn_fused.hip and csrc/bn_dz_fused.hip, one pass at a time, through the C ABI, against the
-oracle of tests/bn_oracle.py (pinned against torch autograd in test_bn_cpu.py).
+"""The BatchNorm kernels of csrc/bn.hip, csrc/bn_fused.hip, csrc/bn_dz_fused.hip and csrc/pool_fused.hip, one pass at a time, through
+the C ABI, against the oracle of tests/bn_oracle.py (pinned against torch autograd in test_bn_cpu.py).
 
 Every pass's reference consumes the DEVICE output of the pass before it (float32 / bfloat16 values are exact in float64), so each
 comparison judges one kernel.  Outputs are pre-filled with NaN; channel-slice runs (ld = C + 16) sit in a sentinel-filled buffer that
@@ -233,6 +233,31 @@ def d_cls_fwd(y, scale, shift, a, W, bias, shape, wide=False):
     _L().call("egm_bn_act_cls_fwd", _dt(y.dtype), _ptr(y), _ld(y), _ptr(scale), _ptr(shift), B.ACTS[a], _ptr(z), _ld(z), _ptr(W), W.shape[0],
               W.shape[1], _ptr(bias), _ptr(logits), N, H, Wd, C, _st())
     return guarded(z), logits
+
+
+def d_pool_fwd(y, scale, shift, a, shape, wide=False):
+    N, H, W = shape
+    C = y.shape[1]
+    z, pooled = slot(N * H * W, C, y.dtype, wide), slot(N * (H // 2) * (W // 2), C, y.dtype, wide)
+    _L().call("egm_bn_act_fwd_pool", _dt(y.dtype), _ptr(y), _ld(y), _ptr(scale), _ptr(shift), B.ACTS[a], _ptr(z), _ld(z), _ptr(pooled),
+              _ld(pooled), N, H, W, C, _st())
+    return guarded(z, pooled)
+
+
+def d_pool_reduce(gskip, gpool, y, co, a, shape):
+    C = y.shape[1]
+    part = nanf(_L().query("egm_bn_pool_bwd_blocks", *shape, C), 2, C)
+    _L().call("egm_bn_pool_bwd_reduce", _dt(y.dtype), _ptr(gskip), _ld(gskip), _ptr(gpool), _ld(gpool), _ptr(y), _ld(y), *_co(co), B.ACTS[a],
+              _ptr(part), *shape, C, _st())
+    return part
+
+
+def d_pool_apply(gskip, gpool, y, co, a, train, sums, shape, wide=False):
+    npix, C = y.shape
+    dy = slot(npix, C, y.dtype, wide)
+    _L().call("egm_bn_pool_bwd_apply", _dt(y.dtype), _ptr(gskip), _ld(gskip), _ptr(gpool), _ld(gpool), _ptr(y), _ld(y), *_co(co), B.ACTS[a],
+              int(train), _ptr(sums), _ptr(dy), _ld(dy), *shape, C, _st())
+    return guarded(dy)
 
 
 def mismatch(got, want, what):
@@ -484,6 +509,68 @@ def test_cls_fwd_exact(C, dtype):
     errs = []
     for nc in B.CLS_NC:
         run_cls_fwd_exact(C, (2, 3, 5), nc, dtype, "relu" if nc % 2 else "none", nc == 3, errs)
+    assert not errs, "\n".join(errs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# exact: the 2x2 max pool fused around a BatchNorm (csrc/pool_fused.hip)
+# ---------------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=2)
+def pool_ref(shape, a):
+    """The exact case of a pool shape, its float64 results and dy before the store's rounding (train 1 and 0): computed once, shared by
+    both storage types (every value but dy is a bfloat16 value: test_bn_cpu.py)."""
+    c = B.pool_case(shape, 100 + shape[3])
+    r = B.pool_exact(c, shape, a)
+    npix = shape[0] * shape[1] * shape[2]
+    dy = {}
+    for train in (1, 0):
+        cb, cc = B.exact_coefs32(c["sums"], npix, c["scale"], c["mean"], c["rstd"], train)
+        dy[train] = B.exact_apply32(np.asarray(r["dz"], np.float32), c["y"], c["scale"], c["shift"], cb, cc, a)
+    return c, r, dy
+
+
+def run_pool_exact(shape, dtype, a, wide, errs):
+    N, H, W, C = shape
+    npix, grid = N * H * W, shape[:3]
+    c, r, dy_r = pool_ref(shape, a)
+    t, co, tag = put(c, dtype, ("y", "gskip", "gpool"), wide), co_dev(c), f"{shape} {a}{' ld=C+16' if wide else ''}: "
+    z, pooled = d_pool_fwd(t["y"], co["scale"], co["shift"], a, grid, wide)
+    same(errs, host(z), r["z"], tag + "egm_bn_act_fwd_pool z")
+    same(errs, host(pooled), r["pooled"], tag + "egm_bn_act_fwd_pool pooled")
+    part = d_pool_reduce(t["gskip"], t["gpool"], t["y"], co, a, grid)
+    nb = B.partial_blocks(npix // 4, C)
+    assert _L().query("egm_bn_pool_bwd_blocks", N, H, W, C) == nb
+    totals(errs, part, nb, r["sums"], tag + "egm_bn_pool_bwd_reduce")
+    sums_d, _ = d_coefs(part, npix, co, True)
+    same(errs, host(sums_d), r["sums"], tag + "egm_bn_bwd_coefs sums")
+    for train in (1, 0):
+        dy = d_pool_apply(t["gskip"], t["gpool"], t["y"], co, a, train, f32(c["sums"]), grid, wide)
+        same(errs, host(dy), rt_of(dtype)(dy_r[train]), tag + f"egm_bn_pool_bwd_apply train={train}")
+        if wide:
+            assert_slot_untouched(dy, tag + "dy")
+    if wide:
+        assert_slot_untouched(z, tag + "z")
+        assert_slot_untouched(pooled, tag + "pooled")
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+@pytest.mark.parametrize("a", ["none", "relu"])
+@pytest.mark.parametrize("shape", B.POOL_SHAPES, ids=str)
+def test_pool_exact(shape, a, dtype):
+    """egm_bn_act_fwd_pool (z and its 2x2 maximum), egm_bn_pool_bwd_reduce (+ egm_bn_bwd_coefs) and egm_bn_pool_bwd_apply (train and
+    eval) with dz = round(gskip + [first maximum of the rounded z in scan order] gpool): integer z makes ties frequent, so the tie
+    rule decides.  One window; 256 % (C/8) != 0, rows = 85; C = 1024 with rows = 2; 2304 windows against 1024 x 2 window rows (the
+    reduction's block loop wraps, the apply grid caps)."""
+    errs = []
+    run_pool_exact(shape, dtype, a, False, errs)
+    assert not errs, "\n".join(errs)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+def test_pool_exact_channel_slices(dtype):
+    """The same passes on channel slices (ld = C + 16) of sentinel-filled buffers, inputs and outputs."""
+    errs = []
+    run_pool_exact(B.POOL_WIDE, dtype, "relu", True, errs)
     assert not errs, "\n".join(errs)
 
 
