@@ -207,6 +207,37 @@ __global__ void ensemble_fuse_kernel(const float* __restrict__ clip, const float
         if (pred) pred[i] = best;
     }
 }
+// The fused logits alone with alpha read from the device (a captured graph follows its value), bit for bit ensemble_fuse_kernel's.  That
+// kernel's expression is compiled under the default contracting mode, and which multiply goes into which FMA is the optimiser's choice
+// there: a second kernel written with the same operators was vectorised and fused differently.  So this one states the form the kernel
+// above has on gfx950 with explicit fmaf under contract(off), which leaves the optimiser no choice (tests/test_gpu_guided.py compares):
+//   src = fma(dst + 0.5, in / out, -0.5);  top = fma(1 - wx, a, wx * b), bot = fma(1 - wx, c, wx * d);
+//   fused = fma(alpha, unet, fma(1 - wy, top, wy * bot))
+__global__ void ensemble_fuse_dev_kernel(const float* __restrict__ clip, const float* __restrict__ unet, const float* __restrict__ alpha_dev,
+                                         int N, int C, int hc, int wc, int H, int W, float* __restrict__ fused) {
+#pragma clang fp contract(off)
+    const float alpha = alpha_dev[0];
+    const float sy = (float)hc / (float)H, sx = (float)wc / (float)W;
+    const long long HW = (long long)H * W, total = (long long)N * HW;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int x = (int)(i % W), y = (int)((i / W) % H), n = (int)(i / HW);
+        float fy = fmaf((float)y + 0.5f, sy, -0.5f), fx = fmaf((float)x + 0.5f, sx, -0.5f);
+        if (fy < 0.f) fy = 0.f;
+        if (fx < 0.f) fx = 0.f;
+        int y0 = (int)fy, x0 = (int)fx;
+        if (y0 > hc - 1) y0 = hc - 1;
+        if (x0 > wc - 1) x0 = wc - 1;
+        const int y1 = y0 + (y0 < hc - 1 ? 1 : 0), x1 = x0 + (x0 < wc - 1 ? 1 : 0);
+        const float wy = fy - (float)y0, wx = fx - (float)x0, uy = 1.f - wy, ux = 1.f - wx;
+        for (int c = 0; c < C; ++c) {
+            const float* m = clip + ((long long)n * C + c) * hc * wc;
+            const float a = m[(long long)y0 * wc + x0], b = m[(long long)y0 * wc + x1], cc = m[(long long)y1 * wc + x0], d = m[(long long)y1 * wc + x1];
+            const float top = fmaf(ux, a, wx * b), bot = fmaf(ux, cc, wx * d);
+            const long long o = ((long long)n * C + c) * HW + (i - (long long)n * HW);
+            fused[o] = fmaf(alpha, unet[o], fmaf(uy, top, wy * bot));
+        }
+    }
+}
 // hist[a][t][p] += 1 for every alpha a of the grid (C <= 4, na <= 128)
 __global__ __launch_bounds__(256) void ensemble_alpha_hist_kernel(const float* __restrict__ clip, const float* __restrict__ unet,
                                                                   const long long* __restrict__ target, const float* __restrict__ alphas, int na,
@@ -301,6 +332,18 @@ extern "C" int egm_ensemble_fuse(const float* clip_logits, const float* unet_log
     int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(ensemble_fuse_kernel, dim3(grid), dim3(256), 0, (hipStream_t)s, clip_logits, unet_logits, alpha, N, C, hc, wc, H, W, pred, fused);
     EGM_CHECK_LAUNCH("ensemble_fuse");
+    return EGM_OK;
+}
+extern "C" int egm_ensemble_fuse_dev_f32(const float* clip_logits, const float* unet_logits, const float* alpha_dev, int N, int C, int hc,
+                                         int wc, int H, int W, float* fused, egm_stream_t s) {
+    EGM_REQUIRE(clip_logits && unet_logits && alpha_dev && fused, "ensemble_fuse_dev_f32: null pointer");
+    EGM_REQUIRE(N > 0 && C > 0 && hc > 0 && wc > 0 && H > 0 && W > 0, "ensemble_fuse_dev_f32: bad shape N=%d C=%d hc=%d wc=%d H=%d W=%d", N, C, hc,
+                wc, H, W);
+    const long long total = (long long)N * H * W;
+    int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(ensemble_fuse_dev_kernel, dim3(grid), dim3(256), 0, (hipStream_t)s, clip_logits, unet_logits, alpha_dev, N, C, hc, wc, H, W,
+                       fused);
+    EGM_CHECK_LAUNCH("ensemble_fuse_dev_f32");
     return EGM_OK;
 }
 /* hist: zeroed [na][C][C] uint64 (accumulates across calls = across images); miou: fp32 [na] */

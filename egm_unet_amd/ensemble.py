@@ -16,6 +16,10 @@ and with a connected-component clean-up (postprocess.MaskCleanup) of the class m
 
     ens = EnsemblePredictor(unet, clipseg, prompts, cleanup=MaskCleanup(min_area=0.002, max_hole=200))
     ens.cleanup = MaskCleanup(min_area=0.004, max_hole=200)        # new numbers: followed by the captured graphs
+
+and with guided upsampling (refine.GuidedUpsample) in place of the nearest resize, so that the mask's edge follows the photo's colour edge:
+
+    ens = EnsemblePredictor(unet, clipseg, prompts, refine=GuidedUpsample(radius=4, eps=1e-3))
 """
 import collections
 import math
@@ -28,6 +32,7 @@ from .clip import ops as clip_ops
 from ._lib import lib, ptr, require_gpu, stream
 from .infer import Predictor, lut256
 from .postprocess import CleanupState, MaskCleanup, _state_for, clean_mask, label_components      # noqa: F401 (re-exported)
+from .refine import GuidedUpsample, guided_apply, guided_coefs, guided_tables, guided_workspace
 from .replay import ReplayCache
 
 
@@ -41,6 +46,27 @@ def fuse_predict(clip_logits, unet_logits, alpha, return_fused=False):
     fused = torch.empty((N, C, H, W), dtype=torch.float32, device=u.device) if return_fused else None
     lib().call("egm_ensemble_fuse", ptr(c), ptr(u), float(alpha), N, C, hc, wc, H, W, ptr(pred), ptr(fused), stream())
     return (pred, fused) if return_fused else pred
+
+
+def fuse_logits(clip_logits, unet_logits, alpha, out=None):
+    """fuse_predict's fused logits alone, fp32 [N, C, H, W], bit for bit, with alpha read on the device: alpha is a number or a
+    one-element fp32 CUDA tensor (a captured graph follows its value).  out: a contiguous fp32 CUDA tensor of that shape to write into
+    (and returned).  One launch, no host wait."""
+    require_gpu()
+    c, u = clip_logits.contiguous().float(), unet_logits.contiguous().float()
+    N, C, hc, wc = c.shape
+    if u.dim() != 4 or u.shape[0] != N or u.shape[1] != C:
+        raise ValueError(f"fuse_logits: clip_logits {tuple(c.shape)} and unet_logits {tuple(u.shape)} must agree in N and C")
+    H, W = u.shape[2:]
+    if not (isinstance(alpha, torch.Tensor) and alpha.is_cuda and alpha.dtype == torch.float32 and alpha.numel() == 1):
+        alpha = torch.full((1,), float(alpha), dtype=torch.float32, device=u.device)
+    if out is None:
+        out = torch.empty((N, C, H, W), dtype=torch.float32, device=u.device)
+    elif not (isinstance(out, torch.Tensor) and out.device == u.device and out.dtype == torch.float32 and tuple(out.shape) == (N, C, H, W)
+              and out.is_contiguous()):
+        raise ValueError(f"fuse_logits: out must be a contiguous float32 tensor [{N}, {C}, {H}, {W}] on {u.device}")
+    lib().call("egm_ensemble_fuse_dev_f32", ptr(c), ptr(u), ptr(alpha), N, C, hc, wc, H, W, ptr(out), stream())
+    return out
 
 
 def search_best_alpha(clip_logits_list, unet_logits_list, labels_list, search_scale=(0.1, 10.0), search_step=100, num_classes=2):
@@ -610,6 +636,20 @@ def search_best_alpha_fullres(clip_logits_list, unet_logits_list, labels_u8_list
     return (best, best_miou, m, hist) if return_hist else (best, best_miou, m)
 
 
+class _RefineState:
+    """The device memory the guided tail of [B, C, h, w] logits and [B, H0, W0, 3] photos needs, owned by the predictor so that a
+    captured graph can keep pointing at it: the scores (the fused logits, or with a clean-up the cleaned class map), the coefficients,
+    guided_coefs' workspace and the bilinear tables of guided_apply.  Made on the warm-up call of a size, before its capture."""
+
+    def __init__(self, B, C, h, w, H0, W0, with_cleanup, device):
+        self.shape = (B, C, h, w, H0, W0, with_cleanup)
+        self.fused = None if with_cleanup else torch.empty((B, C, h, w), dtype=torch.float32, device=device)
+        self.cls = torch.empty((B, h, w), dtype=torch.uint8, device=device) if with_cleanup else None
+        self.A = torch.empty((B, h, w, 4 * C), dtype=torch.float32, device=device)
+        self.workspace = guided_workspace(B, C, h, w, device)
+        self.tables = guided_tables(h, H0, w, W0, device)
+
+
 class EnsemblePredictor:
     """predict_CLIPseg.py per image (:438-534) as one object: a decoded uint8 photo [H0, W0, 3] already on the device goes in, the uint8
     mask [H0, W0] comes out.
@@ -645,14 +685,24 @@ class EnsemblePredictor:
     the UNet-size map of each photo size.  `ens.cleanup = MaskCleanup(...)` with other numbers only rewrites the tables (fill
     kernels, no host wait, no new capture: every stage's launches are in the graph whatever the numbers); a switch between None
     and a rule, or another connectivity, drops the captured graphs as a change of the compute dtype does.  cleanup_status() reads
-    the kernels' status words (0 = no device loop ever ran into its trip bound)."""
+    the kernels' status words (0 = no device loop ever ran into its trip bound).
+
+    refine: None (the tail above, exactly the pipeline without this option) or a refine.GuidedUpsample: the nearest resize to the
+    photo's size is replaced by guided upsampling.  The guide is the UNet's own input x, so the rule's mean and std are
+    replaced by unet_mean and unet_std; the photo is read once more, by the apply launch.  Without a clean-up the scores are the fused
+    logits (egm_ensemble_fuse_dev_f32, alpha read on the device); with one they are the cleaned class map, read as one-hot scores.
+    Every result that is a mask follows the option (__call__, predict_batch, predict_many, evaluate); the logits do not.  The rule's
+    numbers are passed by value, so `ens.refine = ...` drops the captured graphs; the buffers and the bilinear tables of a photo size
+    are owned by the predictor, next to that size's graph.  At most 8 classes."""
 
     def __init__(self, unet, clipseg, prompts, alpha=0.5, unet_mean=(0.709, 0.381, 0.224), unet_std=(0.127, 0.079, 0.043), base_size=565,
                  clip_size=352, clip_antialias=True, lut=(0, 255), dtype=None, graph=True, max_graphs=4, clip_mean=(0.485, 0.456, 0.406),
-                 clip_std=(0.229, 0.224, 0.225), cleanup=None):
+                 clip_std=(0.229, 0.224, 0.225), cleanup=None, refine=None):
         require_gpu()
         if cleanup is not None and not isinstance(cleanup, MaskCleanup):
             raise ValueError("EnsemblePredictor: cleanup must be None or a MaskCleanup")
+        if refine is not None and not isinstance(refine, GuidedUpsample):
+            raise ValueError("EnsemblePredictor: refine must be None or a GuidedUpsample")
         self._unet = Predictor(unet, dtype=dtype, graph=False)
         self.clipseg = clipseg
         dev = next(self._unet.model.parameters()).device
@@ -681,6 +731,9 @@ class EnsemblePredictor:
         self._condT = None
         self._cleanup = cleanup
         self._clean_states = collections.OrderedDict()     # (B, H0, W0) -> CleanupState of that size's UNet-size maps
+        self._refine_states = collections.OrderedDict()    # (B, H0, W0) -> _RefineState of that size's UNet-size logits
+        self._refine = self._refine_rule = None
+        self.refine = refine
 
     # ---- clean-up: a rule whose numbers live in device tables the kernels read
     @property
@@ -713,13 +766,54 @@ class EnsemblePredictor:
         state.set(self._cleanup)
         return state
 
-    def _prune_clean_states(self):
+    def _prune_states(self, states):
         """Keep the states of the sizes that have a graph entry (graph=True), or the max_graphs most recent ones (eager)."""
         if self.graph:
-            for key in [k for k in self._clean_states if k not in self._graphs and not (k[0] == 1 and k[1:] in self._graphs)]:
-                del self._clean_states[key]                # (a photo's entry is keyed (H0, W0), a batch's (B, H0, W0))
-        while len(self._clean_states) > self.max_graphs:
-            del self._clean_states[next(iter(self._clean_states))]
+            for key in [k for k in states if k not in self._graphs and not (k[0] == 1 and k[1:] in self._graphs)]:
+                del states[key]                            # (a photo's entry is keyed (H0, W0), a batch's (B, H0, W0))
+        while len(states) > self.max_graphs:
+            del states[next(iter(states))]
+
+    # ---- guided upsampling: a rule whose numbers the kernels get by value
+    @property
+    def refine(self):
+        return self._refine
+
+    @refine.setter
+    def refine(self, rule):
+        if rule is not None and not isinstance(rule, GuidedUpsample):
+            raise ValueError("EnsemblePredictor: refine must be None or a GuidedUpsample")
+        if rule is not None and self.num_classes > 8:
+            raise ValueError(f"EnsemblePredictor: refine holds at most 8 classes, the UNet has {self.num_classes}")
+        changed = rule != self._refine
+        self._refine = rule
+        self._refine_rule = None if rule is None else rule.with_norm(self.unet_mean, self.unet_std)     # the guide is the UNet's input
+        if changed:
+            self.reset_graphs()                            # other launches in the tail, or other numbers in their arguments
+
+    def _refine_state(self, key, B, C, h, w):
+        shape = (B, C, h, w, key[1], key[2], self._cleanup is not None)
+        state = self._refine_states.get(key)
+        if state is None or state.shape != shape:
+            state = self._refine_states[key] = _RefineState(*shape, self.device)
+        self._refine_states.move_to_end(key)
+        return state
+
+    def _refined(self, imgs, x, clip_l, unet_l):
+        """The tail with a refine rule: the scores at the UNet's size (the fused logits, or the cleaned class map) -> guided_coefs with
+        the UNet's input x as the guide -> guided_apply on the photos."""
+        B, H0, W0, _ = imgs.shape
+        C, h, w = unet_l.shape[1:]
+        rs, rule = self._refine_state((B, H0, W0), B, C, h, w), self._refine_rule
+        if self._cleanup is None:
+            fuse_logits(clip_l, unet_l, self._alpha, out=rs.fused)
+            guided_coefs(x, scores=rs.fused, rule=rule, out=rs.A, workspace=rs.workspace)
+        else:
+            cs = self._clean_state((B, H0, W0), B, h, w)
+            fuse_mask(clip_l, unet_l, self._alpha, (h, w), None, out=cs.cls)           # the bytes of fuse_predict, alpha read on the device
+            clean_mask(cs.cls, self._cleanup, out=rs.cls, state=cs)
+            guided_coefs(x, cls=rs.cls, num_classes=C, rule=rule, out=rs.A, workspace=rs.workspace)
+        return guided_apply(imgs, rs.A, rule, lut=self._lut, tables=rs.tables)
 
     # ---- alpha: a device scalar the fuse kernel reads
     @property
@@ -759,7 +853,9 @@ class EnsemblePredictor:
         xc = data.clip_preprocess_batch(imgs, self.clip_size, self.clip_mean, self.clip_std, self.clip_antialias)
         out = self.clipseg._decode_multi(xc, self._condT)
         clip_l = out.view(B, self._condT.shape[0], out.shape[-2], out.shape[-1])
-        if self._cleanup is None:
+        if self._refine is not None:
+            mask = self._refined(imgs, x, clip_l, unet_l)
+        elif self._cleanup is None:
             mask = fuse_mask(clip_l, unet_l, self._alpha, (H0, W0), self._lut)
         else:
             state = self._clean_state((B, H0, W0), B, unet_l.shape[2], unet_l.shape[3])
@@ -773,7 +869,9 @@ class EnsemblePredictor:
             self._refresh()
             out = self._replay(key, src, run) if self.graph else run(src)
             if self._clean_states:
-                self._prune_clean_states()
+                self._prune_states(self._clean_states)
+            if self._refine_states:
+                self._prune_states(self._refine_states)
             return out
 
     def _call(self, img):
@@ -833,6 +931,7 @@ class EnsemblePredictor:
         """Forget every captured graph (the next call at each photo size warms up again)."""
         self._replay.reset()
         self._clean_states.clear()
+        self._refine_states.clear()
 
     def captured_graph(self, size):
         """The captured torch.cuda.CUDAGraph of photo size (H0, W0), or of the batch (B, H0, W0), or None (for tools that count its

@@ -1061,6 +1061,41 @@ int egm_vprompt_crop_f32(const float* src_k3ss, const int* box_k4, float* out_k3
 int egm_cond_mix_f32(float* out_gd, const float* vis_kd, const int* group_off, const float* text_gd, float w, int G, int K, int D,
                      egm_stream_t s);
 
+/* ---- Guided upsampling: photo-guided mask edges at photo size (csrc/guided.hip, egm_unet_amd/refine.py) ----------------
+ * The fast guided filter (He, Sun, Tang: "Guided Image Filtering" 2013, "Fast Guided Filter" 2015) with a three-colour guide.  fp32, a
+ * fixed evaluation order with one rounding per multiply, add, subtract and divide and no FMA (tests/guided_oracle.py restates it).
+ * Box mean of a channel X at (y, x) with radius r, the window clipped to the image: t[y'][x] = X[y'][xlo], t = t + X[y'][k] for k
+ * ascending to xhi; u = t[ylo][x], u = u + t[k][x] for k ascending to yhi; mean = u / (float)(rows * columns of the window).
+ * egm_guided_coefs_f32: guide fp32 [N][3][h][w] (the low-resolution photo in the caller's units) and EXACTLY ONE of scores fp32
+ *   [N][C][h][w] and cls uint8 [N][h][w] (read as the one-hot scores S_c = cls == c ? 1 : 0) -> A_out fp32 [N][h][w][4C], per pixel and
+ *   class (a0, a1, a2, b).  With m(.) the box mean: s_ij = m(G_i G_j) - m(G_i) m(G_j), + eps_i on the diagonal; v_i = m(G_i S_c) -
+ *   m(G_i) m(S_c); the cofactors c00 = s11 s22 - s12 s12, c01 = s02 s12 - s01 s22, c02 = s01 s12 - s02 s11, c11 = s00 s22 - s02 s02,
+ *   c12 = s01 s02 - s00 s12, c22 = s00 s11 - s01 s01; det = (s00 c00 + s01 c01) + s02 c02; a0 = ((c00 v0 + c01 v1) + c02 v2) / det, a1
+ *   from the row (c01, c11, c12), a2 from (c02, c12, c22); b = ((m(S_c) - a0 m(G_0)) - a1 m(G_1)) - a2 m(G_2).  A = the box mean, same
+ *   r, of those 4C channels.  workspace: egm_guided_workspace(N, C, h, w) bytes of device memory (the unsmoothed coefficients).
+ *   TWO launches whatever N and C: a workgroup owns a 16 x 16 tile of one image with an r-pixel halo in LDS (at most 111 KiB).
+ * egm_guided_apply_u8: imgs uint8 [N][H0][W0][3] contiguous (image n starts n*H0*W0*3 bytes in, at whatever alignment that is) ->
+ *   mask_out uint8 [N][H0][W0] and, when q_out != NULL, q_out fp32 [N][C][H0][W0].  Per photo pixel I_i = (float)byte_i * scale_i +
+ *   offset_i; each of the 4C channels of A is sampled with the expression and the tables of egm_tta_views_f32 (yi [H0][2], yl [H0], xi
+ *   [W0][2], xl [W0] from (h, w) to (H0, W0), any ratio); q_c = ((a0 I_0 + a1 I_1) + a2 I_2) + b; mask = lut[argmax_c q_c], ties to the
+ *   lowest class, lut 256 bytes or NULL = the class id.  ONE launch, no atomics; the photo is read as dwords where a row's address
+ *   allows it, the mask leaves in non-temporal dwords (bytes on ragged ends and unaligned rows); the part of A behind a strip of
+ *   4 x 256 photo pixels is staged in LDS where it is at most 32 KiB, else gathered; table indices are clamped.  h*w*C < 2^29.
+ * Limits: 1 <= r <= 16, 1 <= C <= 8, N <= 65535, every side <= 32767, eps_i finite and > 0; A and the workspace 16-byte aligned.  Bad
+ *   scalars, null pointers and both or neither of scores and cls return EGM_ERR_ARG with a message before any launch.  Nothing waits
+ *   for the device; capturable on one stream.
+ * egm_ensemble_fuse_dev_f32: egm_ensemble_fuse's `fused` (fp32 [N][C][H][W], the same expression, bit for bit) with alpha read from
+ *   DEVICE memory, so a captured graph follows its value.  One launch. */
+long long egm_guided_workspace(int N, int C, int h, int w);
+int egm_guided_coefs_f32(const float* guide, const float* scores, const unsigned char* cls, int N, int C, int h, int w, int r, float eps0,
+                         float eps1, float eps2, float* A_out, void* workspace, egm_stream_t s);
+int egm_guided_apply_u8(const unsigned char* imgs, int N, int H0, int W0, const float* A, int C, int h, int w, const int* yi_dev,
+                        const float* yl_dev, const int* xi_dev, const float* xl_dev, float scale0, float scale1, float scale2,
+                        float offset0, float offset1, float offset2, const unsigned char* lut, unsigned char* mask_out, float* q_out,
+                        egm_stream_t s);
+int egm_ensemble_fuse_dev_f32(const float* clip_logits, const float* unet_logits, const float* alpha_dev, int N, int C, int hc, int wc,
+                              int H, int W, float* fused, egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
