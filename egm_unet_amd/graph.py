@@ -39,9 +39,10 @@ _serial = itertools.count()
 
 class GraphedTrainStep:
     def __init__(self, model, optimizer, example_image, example_target, loss_weight=None, num_classes=2, ignore_index=255,
-                 reducer=None, warmup=3, restore_after_warmup=False, split=None):
+                 reducer=None, warmup=3, restore_after_warmup=False, split=None, boundary=None):
         self.model, self.opt, self.reducer = model, optimizer, reducer
         self.lw, self.nc, self.ign = loss_weight, num_classes, ignore_index
+        self.boundary = boundary                      # a BoundaryLoss added to the criterion; its weight is read from device memory
         self.x = example_image.clone()
         self.t = example_target.clone()
         self.trace = []                               # host-order log of the last call (tests assert the overlap structure on it)
@@ -107,7 +108,8 @@ class GraphedTrainStep:
         else:
             self.graph = torch.cuda.CUDAGraph()
             with self._ns, torch.cuda.graph(self.graph, capture_error_mode=self._cap_mode):
-                loss = criterion(self.model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign)
+                loss = criterion(self.model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
+                                 boundary=self.boundary)
                 loss.backward(self._one)                  # the seed gradient is a resident tensor, not a fill launch per replay
                 if self.reducer is None:
                     self.opt.step()
@@ -122,7 +124,8 @@ class GraphedTrainStep:
         b0, b1 = red.buckets
         with self._ns, torch.cuda.graph(self.gA, capture_error_mode=self._cap_mode):
             model.ddp_boundary = []                   # forward() fills it with the encoder -> decoder tensors
-            loss = criterion(model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign)
+            loss = criterion(model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
+                             boundary=self.boundary)
             bnd = list(model.ddp_boundary)
             # the decoder half of backward: stops at the boundary tensors (their gradients land in .grad) and at bucket 0's parameters
             torch.autograd.backward(loss, self._one, inputs=list(b0) + bnd, retain_graph=True)
@@ -159,7 +162,8 @@ class GraphedTrainStep:
         self._lr_event.record()
 
     def _eager(self):
-        loss = criterion(self.model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign)
+        loss = criterion(self.model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
+                         boundary=self.boundary)
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         if self.reducer is not None:

@@ -1096,6 +1096,40 @@ int egm_guided_apply_u8(const unsigned char* imgs, int N, int H0, int W0, const 
 int egm_ensemble_fuse_dev_f32(const float* clip_logits, const float* unet_logits, const float* alpha_dev, int N, int C, int hc, int wc,
                               int H, int W, float* fused, egm_stream_t s);
 
+/* ---- Boundary loss: signed distance maps of the target made on the device (csrc/sdf.hip, train_utils/boundary_loss.py)
+ * Kervadec et al., "Boundary loss for highly unbalanced segmentation" (MIDL 2019; Medical Image Analysis 2021).
+ * egm_target_sdf_i64: target int64 [N][H][W], valid(p) = target(p) != ignore_index; classes = a HOST array of K distinct class ids >= 0,
+ *   1 <= K <= 4.  s_out int32 [N][K][H][W], every cell written, exact: for p of class k, s = -min |p - q|^2 over the valid q of the
+ *   same image that are not of class k; for p valid and not of class k, s = +min |p - q|^2 over the q of class k; s = 0 for an ignored
+ *   p and wherever the minimum runs over nothing, which makes the whole plane of (n, k) zero when image n has no pixel of class k or
+ *   no valid pixel outside it.  Every defined distance is >= 1.
+ *   workspace: egm_sdf_workspace(N, H, W, K) bytes of device memory owned by the caller (1 + 4 K bytes per pixel of a row padded to 16:
+ *   a byte of "is of class k" / "is valid and not of class k" bits and a 16-bit row distance per bit, 0xFFFF = none).
+ *   Two launches per call whatever the content (rows, then columns); nothing waits for the device, for another workgroup or for
+ *   another wave; no atomics; every device loop has a trip count of at most max(H, the chunks of a row); capturable on one stream.
+ *   H, W <= 32767, H*W <= 2^30, N*H <= 2^31; otherwise, and for a null pointer, K outside 1..4, a negative or a repeated class id:
+ *   EGM_ERR_ARG with a message before any launch.
+ * egm_sdf_phi_f32: phi of n cells of s as an fp32 tensor, for inspection and tests (the loss passes make it on the fly).
+ * egm_bloss_fwd: logits fp32 [N][C][H][W], sdf = s_out above for the same classes (ids in [0, C), C <= 16), target and ignore_index as
+ *   above (read for the count of valid pixels only).  phi_k = sqrt((float)s) for s > 0, -(sqrt((float)-s) - 1) for s < 0, 0 for s = 0
+ *   (the official one_hot2dist, correctly rounded fp32, never stored).  L_B = (1/D) sum_n sum_k sum_p phi_k(p) softmax(x[n,:,p])[class k],
+ *   D = K * max(1, valid pixels of the batch), the count an integer.  out2 = {w L_B, L_B} with w = w_dev[0] read on the DEVICE, so a
+ *   captured graph follows a new weight.  workspace: egm_bloss_workspace(N, C, H, W) bytes, 4-byte aligned, kept for the backward (per
+ *   workgroup partial sums written with plain stores and summed in a fixed order in double, the counts, 1 / D).  Two launches.
+ * egm_bloss_bwd: dlogits[n][j][p] = grad_out[0] (1 when NULL) * w / D * p_j ([j in classes] phi_j - sum_k phi_k p_k), exactly 0 at an
+ *   ignored pixel; every element written (non-temporal stores).  One launch.  N <= 65535.  Four pixels per lane where H*W is a multiple
+ *   of 4 and logits, sdf and dlogits are 16-byte aligned, one otherwise, in both passes: the same dlogits either way (the forward
+ *   groups its partial sums differently, so L_B agrees within rounding). */
+long long egm_sdf_workspace(int N, int H, int W, int K);
+int egm_target_sdf_i64(const long long* target, int N, int H, int W, const int* classes, int K, long long ignore_index, void* workspace,
+                       int* s_out, egm_stream_t s);
+int egm_sdf_phi_f32(const int* sdf, long long n, float* phi, egm_stream_t s);
+long long egm_bloss_workspace(int N, int C, int H, int W);
+int egm_bloss_fwd(const float* logits, const int* sdf, const long long* target, const int* classes, int K, int N, int C, int H, int W,
+                  long long ignore_index, const float* w_dev, void* workspace, float* out2, egm_stream_t s);
+int egm_bloss_bwd(const float* logits, const int* sdf, const int* classes, int K, int N, int C, int H, int W, const void* workspace,
+                  const float* grad_out, const float* w_dev, float* dlogits, egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
