@@ -1,5 +1,5 @@
 // Element formulas of BatchNorm (+activation), forward and backward, shared by every kernel that applies them (bn.hip, bn_fused.hip,
-// bn_dz_fused.hip, pool_fused.hip, mca.hip, pw_bn.hip), so a fused pass and the stand-alone pass it replaces agree bit for bit.
+// bn_dz_fused.hip, pool_fused.hip, mca.hip), so a fused pass and the stand-alone pass it replaces agree bit for bit.
 // nn.BatchNorm2d (+nn.ReLU / nn.Sigmoid / nn.SiLU) behind a convolution: src/EGM-UNet.py:25-43, 50-54, 894-901, 966-973.
 #pragma once
 #include "common.h"

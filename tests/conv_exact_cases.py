@@ -295,6 +295,29 @@ ALL_FWD_NAMES = {P + s for s in ("<1, 3, 3, 2>", "<2, 3, 3, 2>", "<1, 3, 3, 1>",
 ALL_WGRAD_NAMES = {WS + "<9, 1>", WS + "<9, 2>", WS + "<9, 4>", WS + "<7, 0>", WS + "<5, 0>", WG + "<bf16_t, 1>", WG + "<bf16_t, 3>",
                    "conv7x7_c16_wgrad_kernel", "conv3x3d_c16_wgrad_kernel"} | {WG + f"<float, {t}>" for t in (9, 7, 5, 3, 1)}
 
+# the fused 1x1 backward (conv1x1_bwd_kernel, test_gpu_conv1x1_bwd.py), which no planner query names: N, H, W, real Cin, Cout.
+# Tiles are 32 pixels, a workgroup has four waves and takes a 64-channel block of Cin.
+C1_SHAPES = [
+    (1, 5, 7, 8, 8),            # 35 pixels: two tiles, the second ragged; two of the four waves idle and sum zeros into the slab
+    (2, 9, 7, 64, 64),          # a full 64-channel block
+    (1, 10, 10, 16, 40),        # Cout no multiple of 32
+    (1, 33, 31, 24, 3),         # 1023 pixels: eight waves, four tiles each, so the prefetch loop runs; ragged tail; Cout = 3 in 8
+    (2, 6, 10, 72, 24),         # a second column block of 8 channels only
+    (2, 6, 10, 128, 128),       # two full column blocks, four cout blocks
+]
+C1_MULTI = [(2, 10, 14, 16, 16), (1, 5, 7, 16, 16), (1, 33, 31, 16, 16)]       # one launch of three problems with different pixel counts
+
+
+def c1_id(shape):
+    return "%dx%dx%d-%dto%d" % shape
+
+
+def c1_case(shape, dtype="bf16"):
+    """The 1x1 case of a C1_SHAPES / C1_MULTI shape (with a bias: db is checked); the operands do not depend on `dtype`."""
+    N, H, W, Cin, Cout = shape
+    return Case(dtype, N, H, W, Cin, Cout, 1, 1, bias=True, seed=500 + (C1_SHAPES + C1_MULTI).index(shape))
+
+
 DW_SHAPES = [(1, 9, 33, 8), (2, 17, 35, 24)]           # depthwise 3x3: N, H, W, C
 
 

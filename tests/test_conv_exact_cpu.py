@@ -58,6 +58,20 @@ def test_wgrad_table_meets_the_bound(case):
         assert torch.equal(r32["dw"], ref["dw"]) and torch.equal(r32["db"], ref["db"])
 
 
+@pytest.mark.parametrize("shape", X.C1_SHAPES + X.C1_MULTI, ids=[X.c1_id(s) for s in X.C1_SHAPES + X.C1_MULTI])
+def test_fused_1x1_backward_table_meets_the_bound(shape):
+    case = X.c1_case(shape)
+    x, w, b, dy = X.operands(case)
+    for t in (x, w, dy):
+        assert torch.equal(t.bfloat16().double(), t), "operands are bf16 numbers"
+    assert float(x.abs().min()) >= 1 and float(dy.abs().min()) >= 1 and float(w.abs().max()) == 1
+    ref = X.conv_ref(case, x, w, b, dy, ("dx", "dw", "db"))
+    X.check_bounds(case, ref)                                   # raises on |dx| > 256, |dw| or |db| >= 2^24 or a non-integer
+    assert torch.equal(ref["dx"].bfloat16().double(), ref["dx"])
+    assert 4 * case.N * case.H * case.W < X.SUM_LIMIT           # every partial sum of dw / db, in any order
+    assert int((ref["dx"] != 0).sum()) > 0.5 * ref["dx"].numel() and int((ref["dw"] != 0).sum()) > 0.5 * ref["dw"].numel()
+
+
 def test_other_tables_meet_the_bound():
     for c in X.GROUP_LAUNCH:
         X.build(c, ("y",))
