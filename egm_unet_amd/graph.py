@@ -25,6 +25,8 @@ replay, so LR schedulers keep working (a captured graph bakes by-value arguments
 `warmup` REAL eager training steps on the example batch (allocator warm-up, lazy kernel attributes, momentum buffers); pass
 restore_after_warmup=True to get weights, BatchNorm statistics and momentum back to their values from before the warm-up.
 """
+import contextlib
+import gc
 import itertools
 import weakref
 
@@ -37,12 +39,30 @@ from .train_utils.train_and_eval import criterion
 _serial = itertools.count()
 
 
+@contextlib.contextmanager
+def _collector_rests():
+    """Around a capture: dead reference cycles are collected first and the cyclic collector rests until the capture has ended.
+    model -> model._egm_train_graph -> step -> model is a cycle, so a dead GraphedTrainStep is freed by the collector only, whenever
+    its allocation counts say so; freeing its CUDAGraph inside another step's capture ended the process (an abort under "Garbage-
+    collecting" in the forward of a capture, first seen in a suite run where one test left three such cycles behind and the next one
+    captured).  torch.cuda.graph itself collects on entry only under torch.compiler.config.force_cudagraph_gc (torch 2.10)."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
 class GraphedTrainStep:
     def __init__(self, model, optimizer, example_image, example_target, loss_weight=None, num_classes=2, ignore_index=255,
-                 reducer=None, warmup=3, restore_after_warmup=False, split=None, boundary=None):
+                 reducer=None, warmup=3, restore_after_warmup=False, split=None, boundary=None, lovasz=None):
         self.model, self.opt, self.reducer = model, optimizer, reducer
         self.lw, self.nc, self.ign = loss_weight, num_classes, ignore_index
         self.boundary = boundary                      # a BoundaryLoss added to the criterion; its weight is read from device memory
+        self.lovasz = lovasz                          # a LovaszSoftmax added to the criterion, likewise
         self.x = example_image.clone()
         self.t = example_target.clone()
         self.trace = []                               # host-order log of the last call (tests assert the overlap structure on it)
@@ -107,9 +127,9 @@ class GraphedTrainStep:
             self._capture_split()
         else:
             self.graph = torch.cuda.CUDAGraph()
-            with self._ns, torch.cuda.graph(self.graph, capture_error_mode=self._cap_mode):
+            with _collector_rests(), self._ns, torch.cuda.graph(self.graph, capture_error_mode=self._cap_mode):
                 loss = criterion(self.model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
-                                 boundary=self.boundary)
+                                 boundary=self.boundary, lovasz=self.lovasz)
                 loss.backward(self._one)                  # the seed gradient is a resident tensor, not a fill launch per replay
                 if self.reducer is None:
                     self.opt.step()
@@ -122,24 +142,24 @@ class GraphedTrainStep:
         self.side = red.side if red.side is not None else torch.cuda.Stream(device=self.x.device)
         self.gA, self.gB, self.gC = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         b0, b1 = red.buckets
-        with self._ns, torch.cuda.graph(self.gA, capture_error_mode=self._cap_mode):
+        with _collector_rests(), self._ns, torch.cuda.graph(self.gA, capture_error_mode=self._cap_mode):
             model.ddp_boundary = []                   # forward() fills it with the encoder -> decoder tensors
             loss = criterion(model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
-                             boundary=self.boundary)
+                             boundary=self.boundary, lovasz=self.lovasz)
             bnd = list(model.ddp_boundary)
             # the decoder half of backward: stops at the boundary tensors (their gradients land in .grad) and at bucket 0's parameters
             torch.autograd.backward(loss, self._one, inputs=list(b0) + bnd, retain_graph=True)
             red.gather_bucket(0)
             self.loss = loss.detach()
             bgrads = [b.grad for b in bnd]
-        with self._ns, torch.cuda.graph(self.gB, pool=self.gA.pool(), capture_error_mode=self._cap_mode):
+        with _collector_rests(), self._ns, torch.cuda.graph(self.gB, pool=self.gA.pool(), capture_error_mode=self._cap_mode):
             torch.autograd.backward(bnd, bgrads, inputs=list(b1))
             red.gather_bucket(1)
         model.ddp_boundary = None
         for b in bnd:
             b.grad = None
         self.opt.grad_source = red.views
-        with self._ns, torch.cuda.graph(self.gC, pool=self.gA.pool(), capture_error_mode=self._cap_mode):
+        with _collector_rests(), self._ns, torch.cuda.graph(self.gC, pool=self.gA.pool(), capture_error_mode=self._cap_mode):
             self.opt.step()
 
     def __del__(self):
@@ -163,7 +183,7 @@ class GraphedTrainStep:
 
     def _eager(self):
         loss = criterion(self.model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
-                         boundary=self.boundary)
+                         boundary=self.boundary, lovasz=self.lovasz)
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         if self.reducer is not None:

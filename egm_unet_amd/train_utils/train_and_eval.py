@@ -5,9 +5,11 @@ from . import distributed_utils as utils
 from .dice_coefficient_loss import fused_criterion
 
 
-def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool = True, ignore_index: int = -100, boundary=None):
+def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool = True, ignore_index: int = -100, boundary=None,
+              lovasz=None):
     """Five-term loss of the reference (CE + Dice + Laplace + Lap + Sobel); `out` (+0.5*`aux`) convention kept.
-    boundary: a boundary_loss.BoundaryLoss; every head's loss then gets w * L_B added (the distance maps of the target are made once)."""
+    boundary: a boundary_loss.BoundaryLoss; every head's loss then gets w * L_B added (the distance maps of the target are made once).
+    lovasz: a lovasz_loss.LovaszSoftmax; every head's loss then gets w * L added, after the boundary term."""
     losses = {}
     sdf = boundary.sdf(target) if boundary is not None and target.is_cuda else None
     for name, x in inputs.items():
@@ -16,6 +18,8 @@ def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool
         losses[name] = fused_criterion(x, target, loss_weight, dice=dice, ignore_index=ignore_index)
         if boundary is not None:
             losses[name] = losses[name] + boundary.loss(x, target, sdf=sdf)
+        if lovasz is not None:
+            losses[name] = losses[name] + lovasz.loss(x, target)
     if len(losses) == 1:
         return losses["out"]
     return losses["out"] + 0.5 * losses["aux"]
@@ -47,7 +51,7 @@ def _graphable(model, optimizer, device):
 
 
 def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler, print_freq=10, scaler=None,
-                    boundary=None):
+                    boundary=None, lovasz=None):
     """scaler != None selects the reduced-precision path like the reference's autocast+GradScaler branch; on MI355X that
     is bf16 activation storage with fp32 accumulation and fp32 master weights, which needs no loss scaling.
 
@@ -59,7 +63,8 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
     EGM_GRAPH_TRAIN=0 forces the eager loop.
 
     boundary: a boundary_loss.BoundaryLoss added to the criterion of every step; its weight is a device scalar, so
-    boundary.set_weight(...) between epochs is followed by the replayed step."""
+    boundary.set_weight(...) between epochs is followed by the replayed step.
+    lovasz: a lovasz_loss.LovaszSoftmax, added the same way (under data parallel each rank takes the loss of its own batch)."""
     model.train()
     metric_logger = utils.MetricLogger(delimiter="  ")
     metric_logger.add_meter("lr", utils.SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -77,11 +82,12 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
         # up to a step behind the host: a single buffer let the copy of step i pick up the learning rate of step i+1)
         lr_pinned = [torch.zeros(1, dtype=torch.float32).pin_memory() for _ in range(2)]
         lr_events = [None, None]
-        # a step captured in an earlier epoch is reused while model, optimizer, precision, class count and boundary term are the same
-        # objects / values (the key holds the BoundaryLoss itself, compared by identity: a step without the term is never one with it)
+        # a step captured in an earlier epoch is reused while model, optimizer, precision, class count, boundary and Lovasz term are the
+        # same objects / values (the key holds the term objects themselves, compared by identity: a step without a term is never one
+        # with it)
         # (its graph holds the pointer of ITS lr scalar, so that tensor comes back with it)
         import weakref
-        key = (getattr(core, "compute_dtype", None), num_classes, boundary)
+        key = (getattr(core, "compute_dtype", None), num_classes, boundary, lovasz)
         cached = getattr(model, "_egm_train_graph", None)
         if cached is not None and cached[0] == key and cached[4]() is optimizer:      # the very same optimizer object, still alive
             _, step, step_shape, optimizer.lr_dev, _ = cached
@@ -117,13 +123,14 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
             from ..graph import GraphedTrainStep
             # warmup=1: the eager warm-up IS this batch's training step; capture records the next ones without executing anything
             step = GraphedTrainStep(model, optimizer, image, target, loss_weight, num_classes=num_classes, ignore_index=255, warmup=1,
-                                    boundary=boundary)
+                                    boundary=boundary, lovasz=lovasz)
             step_shape = shape
             model._egm_train_graph = (key, step, step_shape, optimizer.lr_dev, weakref.ref(optimizer))
             loss = step.warmup_loss
         else:
             output = model(image)
-            loss = criterion(output, target, loss_weight, num_classes=num_classes, ignore_index=255, boundary=boundary)
+            loss = criterion(output, target, loss_weight, num_classes=num_classes, ignore_index=255, boundary=boundary,
+                             lovasz=lovasz)
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()

@@ -1091,6 +1091,54 @@ int egm_bloss_fwd(const float* logits, const int* sdf, const long long* target, 
 int egm_bloss_bwd(const float* logits, const int* sdf, const int* classes, int K, int N, int C, int H, int W, const void* workspace,
                   const float* grad_out, const float* w_dev, float* dlogits, egm_stream_t s);
 
+/* ---- Stable radix sort of (key, value) pairs (csrc/sort.hip)
+ * egm_sort_pairs_u32: keys, vals uint32 [S][L] -> keys_out, vals_out [S][L]: each of the S segments sorted ascending on the key bits
+ *   [begin_bit, end_bit), 0 <= begin_bit < end_bit <= 32 (the other bits travel with the key and are not looked at); elements with equal
+ *   bits keep their input order (stable), so np.argsort(kind="stable") of the masked keys restates the permutation exactly and two calls
+ *   give the same bits.  An LSD sort of 8 bits per pass over tiles of 2048 elements: ceil((end_bit - begin_bit) / 8) passes of three
+ *   launches (tile histograms, an exclusive scan of the [segment][digit][tile] table, a scatter whose in-tile rank comes from 64-bit
+ *   __ballot matches and per-wave LDS counters), all segments of a pass in one launch.  No workgroup waits for another, every loop is
+ *   bounded by the arguments, no atomics on global memory; capturable on one stream.
+ *   workspace: egm_sort_pairs_workspace(S, L) bytes of device memory owned by the caller, 4-byte aligned (two ping-pong planes and
+ *   the table).  The outputs must not be the inputs (the inputs are left as they were).  1 <= S <= 65535, 1 <= L < 2^31; otherwise,
+ *   and for a null pointer or an empty bit range: EGM_ERR_ARG with a message before any launch. */
+long long egm_sort_pairs_workspace(int S, long long L);
+int egm_sort_pairs_u32(const unsigned int* keys, const unsigned int* vals, int S, long long L, int begin_bit, int end_bit, void* workspace,
+                       unsigned int* keys_out, unsigned int* vals_out, egm_stream_t s);
+
+/* ---- Lovasz-Softmax loss (csrc/lovasz.hip, train_utils/lovasz_loss.py)
+ * Berman, Triki, Blaschko, "The Lovasz-Softmax loss" (CVPR 2018): the convex extension of the Jaccard loss.
+ * logits fp32 [N][C][H][W], C <= 16; target int64 [N][H][W], valid(p) = target(p) != ignore_index; classes = a HOST array of K distinct
+ * ids in [0, C), 1 <= K <= 16.  per_image = 0: one segment, the batch (S = 1, L = N H W); else S = N segments of L = H W.  N H W < 2^31.
+ * egm_lovasz_errors: per class k and pixel p, fg = [target(p) == id_k], e = |fg - softmax(x)[id_k]| in fp32 (0 at an ignored pixel);
+ *   keys [K][N][H][W] = (~bits(e) & 0x3FFFFFFF) | fg << 30 | valid << 31, vals = the pixel's flat index (n, h, w) within its segment,
+ *   e_out (may be NULL) the fp32 e plane [K][N][H][W].  One launch.
+ * egm_lovasz_coefs: the errors, their stable sort over key bits [0, 30) (descending e, ties by ascending pixel index), and along the
+ *   sorted order of each (class, segment) the inclusive counts F_j of valid foreground and V_j of valid elements (exact uint32), G = the
+ *   segment's foreground.  J(F, V) = 1 - (G - F) / (G + V - F); for a valid element g_j = J(F_j, V_j) - J(F_j - fg_j, V_j - 1), the
+ *   second term 0 when V_j == 1, in double, rounded once to fp32; g = 0 for an ignored element.  coef [K][N][H][W] fp32, every element
+ *   written at the pixel's own place: sign(p_c - fg) g (0 where e == 0).  4 * 3 + 4 launches whatever N, K, the content and per_image.
+ * egm_lovasz_fwd: the same, then L_{s,k} = sum_j e_j g_j (one double partial per workgroup, summed in a fixed order in double),
+ *   L_s = (1 / P_s) sum over the counted classes (present != 0: those with G_{s,k} > 0, decided on the device; else all K), 0 when
+ *   P_s = 0, L = (1 / S) sum_s L_s.  out2 = {w L, L} with w = w_dev[0] read on the DEVICE.  4 * 3 + 5 launches.
+ *   workspace: egm_lovasz_workspace(N, C, H, W, K, per_image) bytes, 16-byte aligned, kept for the backward (it holds, per class and
+ *   segment, 1 / (S P_s) where the class is counted and 0 where it is not).
+ * egm_lovasz_bwd: dlogits[n][j][p] = grad_out[0] (1 when NULL) * w * sum_k scale_{k,s} coef_k(p) p_{id_k} ([id_k == j] - p_j), exactly
+ *   0 at an ignored pixel; every element written (non-temporal stores).  One launch.
+ * Nothing waits for the device or for another workgroup; no atomics on global memory; capturable on one stream.  A null pointer,
+ * C > 16, K outside 1..16, an id outside [0, C), a repeated id, N H W >= 2^31, N > 65535 or a misaligned workspace: EGM_ERR_ARG with a
+ * message before any launch. */
+long long egm_lovasz_workspace(int N, int C, int H, int W, int K, int per_image);
+int egm_lovasz_errors(const float* logits, const long long* target, const int* classes, int K, int N, int C, int H, int W,
+                      long long ignore_index, int per_image, unsigned int* keys, unsigned int* vals, float* e_out, egm_stream_t s);
+int egm_lovasz_coefs(const float* logits, const long long* target, const int* classes, int K, int N, int C, int H, int W,
+                     long long ignore_index, int per_image, void* workspace, float* e_out, float* coef, egm_stream_t s);
+int egm_lovasz_fwd(const float* logits, const long long* target, const int* classes, int K, int N, int C, int H, int W,
+                   long long ignore_index, int per_image, int present, const float* w_dev, void* workspace, float* coef, float* out2,
+                   egm_stream_t s);
+int egm_lovasz_bwd(const float* logits, const float* coef, const int* classes, int K, int N, int C, int H, int W, int per_image,
+                   const void* workspace, const float* grad_out, const float* w_dev, float* dlogits, egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
