@@ -135,7 +135,8 @@ class CLIPDenseBase(nn.Module):
         prompt k)[0][0, 0] in train mode, differentiable in the decoder parameters (their gradients equal those of the repeat form, the
         image fed once per prompt); the conditionals are constants.  The frozen backbone runs once per image under no_grad and stops
         after the last layer the decoder reads; the decoder's dropout draws its masks for the B*K sequences.  In eval mode or with
-        autograd off this is forward_multi.  Loss: clip.train_ops.bce_with_logits(out, target [B, K, H', W'])."""
+        autograd off this is forward_multi.  Loss: clip.train_ops.bce_with_logits(out, target [B, K, H', W']), to which
+        train_utils.LovaszHinge().loss(out, target) adds the IoU surrogate of every (b, k) map."""
         if not (self.training and torch.is_grad_enabled()):
             return self.forward_multi(inp_image, conditionals)
         dev = self.model.positional_embedding.device

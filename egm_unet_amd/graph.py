@@ -62,7 +62,7 @@ class GraphedTrainStep:
         self.model, self.opt, self.reducer = model, optimizer, reducer
         self.lw, self.nc, self.ign = loss_weight, num_classes, ignore_index
         self.boundary = boundary                      # a BoundaryLoss added to the criterion; its weight is read from device memory
-        self.lovasz = lovasz                          # a LovaszSoftmax added to the criterion, likewise
+        self.lovasz = lovasz                          # a LovaszSoftmax or LovaszHinge added to the criterion, likewise
         self.x = example_image.clone()
         self.t = example_target.clone()
         self.trace = []                               # host-order log of the last call (tests assert the overlap structure on it)

@@ -9,7 +9,8 @@ def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool
               lovasz=None):
     """Five-term loss of the reference (CE + Dice + Laplace + Lap + Sobel); `out` (+0.5*`aux`) convention kept.
     boundary: a boundary_loss.BoundaryLoss; every head's loss then gets w * L_B added (the distance maps of the target are made once).
-    lovasz: a lovasz_loss.LovaszSoftmax; every head's loss then gets w * L added, after the boundary term."""
+    lovasz: a lovasz_loss.LovaszSoftmax, or a lovasz_loss.LovaszHinge with channels=(c_pos, c_neg); every head's loss then gets w * L
+    added, after the boundary term."""
     losses = {}
     sdf = boundary.sdf(target) if boundary is not None and target.is_cuda else None
     for name, x in inputs.items():
@@ -64,7 +65,8 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
 
     boundary: a boundary_loss.BoundaryLoss added to the criterion of every step; its weight is a device scalar, so
     boundary.set_weight(...) between epochs is followed by the replayed step.
-    lovasz: a lovasz_loss.LovaszSoftmax, added the same way (under data parallel each rank takes the loss of its own batch)."""
+    lovasz: a lovasz_loss.LovaszSoftmax or LovaszHinge(channels=...), added the same way (under data parallel each rank takes the loss
+    of its own batch)."""
     model.train()
     metric_logger = utils.MetricLogger(delimiter="  ")
     metric_logger.add_meter("lr", utils.SmoothedValue(window_size=1, fmt="{value:.6f}"))

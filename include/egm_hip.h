@@ -1139,6 +1139,43 @@ int egm_lovasz_fwd(const float* logits, const long long* target, const int* clas
 int egm_lovasz_bwd(const float* logits, const float* coef, const int* classes, int K, int N, int C, int H, int W, int per_image,
                    const void* workspace, const float* grad_out, const float* w_dev, float* dlogits, egm_stream_t s);
 
+/* ---- Lovasz hinge loss (csrc/lovasz_hinge.hip, train_utils/lovasz_loss.py)
+ * The same paper's lovasz_hinge: the convex extension of the Jaccard loss of one binary score map per image.
+ * Scores as for egm_sweep_hist.  C == 1: logits fp32 [N][H][W], s = x[n][p] (c_pos, c_neg ignored; a [N][K][H][W] tensor is N K
+ * images).  C >= 2: logits fp32 [N][C][H][W], s = x[n][c_pos][p] - x[n][c_neg][p], one fp32 subtraction, 0 <= c_pos != c_neg < C.
+ * target, of the score's shape [N][H][W]: target_f32 != 0: fp32, ignored iff t == (float)ignore_index (tested first), else positive
+ * iff t > 0.5; target_f32 == 0: int64, ignored iff t == ignore_index, positive iff t == positive, every other value negative.
+ * use_ignore == 0: nothing is ignored.  per_image = 0: one segment of all images (S = 1, L = N H W); else S = N segments of L = H W.
+ * N H W < 2^31, N <= 65535.
+ * egm_lovasz_hinge_errors: sigma = +1 at a positive pixel, -1 otherwise; e = 1 - s sigma in fp32 (one rounding); r = e where the pixel
+ *   is valid and e > 0, else +0; keys [N][H][W] = (~bits(r) & 0x7FFFFFFF) | fg << 31 with fg = valid and positive, vals = the pixel's
+ *   flat index within its segment, e_out (may be NULL) the fp32 plane of e, of every pixel, ignored ones included.  One launch.
+ * egm_lovasz_hinge_coefs: the errors, their stable sort over key bits [0, 31) (descending r, ties by ascending pixel index), and along
+ *   the sorted order of each segment F_j, the inclusive count of fg; G = the segment's fg; J(F, V) = 1 - (G - F) / (G + V - F);
+ *   g_j = J(F_j, j) - J(F_j - fg_j, j - 1), the second term 0 at j = 1, in double, rounded once to fp32.  coef [N][H][W] fp32, every
+ *   element written at the pixel's own place: -sigma g where r > 0, else 0.  4 * 3 + 4 launches whatever N, the content and per_image.
+ * egm_lovasz_hinge_fwd: the same, then L_s = sum_j r_j g_j (one double partial per workgroup, summed in a fixed order in double; 0 for
+ *   a segment with no valid pixel, which still counts), L = (1 / S) sum_s L_s.  out2 = {w L, L} with w = w_dev[0] read on the DEVICE.
+ *   4 * 3 + 5 launches.  workspace: egm_lovasz_hinge_workspace(N, H, W, per_image) bytes, 16-byte aligned; the backward does not need it.
+ * egm_lovasz_hinge_bwd: m = (grad_out[0] (1 when NULL) * w) * (1.0f / S), fp32 products in this order.  C == 1: dlogits[n][p] =
+ *   m coef[n][p]; C >= 2: dlogits[n][c_pos] = m coef, dlogits[n][c_neg] = -(m coef), every other channel +0.  Every element written
+ *   (non-temporal stores); no additions.  One launch.
+ * Nothing waits for the device or for another workgroup; no atomics on global memory; capturable on one stream.  A null pointer, a bad
+ * shape, N H W >= 2^31, N > 65535, equal or out-of-range channels (C >= 2) or a misaligned workspace: EGM_ERR_ARG with a message before
+ * any launch. */
+long long egm_lovasz_hinge_workspace(int N, int H, int W, int per_image);
+int egm_lovasz_hinge_errors(const float* logits, const void* target, int target_f32, int N, int C, int c_pos, int c_neg, int H, int W,
+                            long long positive, long long ignore_index, int use_ignore, int per_image, unsigned int* keys,
+                            unsigned int* vals, float* e_out, egm_stream_t s);
+int egm_lovasz_hinge_coefs(const float* logits, const void* target, int target_f32, int N, int C, int c_pos, int c_neg, int H, int W,
+                           long long positive, long long ignore_index, int use_ignore, int per_image, void* workspace, float* e_out,
+                           float* coef, egm_stream_t s);
+int egm_lovasz_hinge_fwd(const float* logits, const void* target, int target_f32, int N, int C, int c_pos, int c_neg, int H, int W,
+                         long long positive, long long ignore_index, int use_ignore, int per_image, const float* w_dev, void* workspace,
+                         float* coef, float* out2, egm_stream_t s);
+int egm_lovasz_hinge_bwd(const float* coef, int N, int C, int c_pos, int c_neg, int H, int W, int per_image, const float* grad_out,
+                         const float* w_dev, float* dlogits, egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
