@@ -353,7 +353,12 @@ static int gemm_dma_nt(const GemmDmaArgs& a) {
                                                                        // text fc2, K = 2048: 57.1 -> 59.5 us)
     return 0;                                                          // a handful of tiles: the 128-wide register-staged kernels spread them better
 }
-int egm_gemm_dma_ok(const GemmDmaArgs& a) { return gemm_dma_nt(a) != 0; }
+GemmDmaPlan egm_gemm_dma_plan(const GemmDmaArgs& a) {
+    GemmDmaPlan pl;
+    pl.nt = gemm_dma_nt(a);
+    pl.nw = (egm_gemm_dma_mode(-1) == 2 && pl.nt >= 3) ? 4 : 8;         // the 4-wave form (128-row wave tiles)
+    return pl;
+}
 
 template <int NT, bool HAS_R, int ACT, int NW>
 static int launch_dma(const Params& p, int grid, hipStream_t st) {
@@ -379,14 +384,15 @@ static int launch_dma_nt(const Params& p, int grid, bool r, int act, hipStream_t
 }
 
 int egm_gemm_dma_launch(const GemmDmaArgs& a, hipStream_t st) {
-    const int nt = gemm_dma_nt(a);
+    const GemmDmaPlan pl = egm_gemm_dma_plan(a);
+    const int nt = pl.nt;
     EGM_REQUIRE(nt != 0, "gemm_dma: shape not supported (egm_gemm_dma_ok)");
     Params p;
     p.A = (const bf16_t*)a.A; p.B = (const bf16_t*)a.B; p.C = (bf16_t*)a.C; p.bias = a.bias; p.R = (const bf16_t*)a.R;
     p.lda = a.lda; p.ldb = a.ldb; p.ldc = a.ldc; p.ldr = a.ldr; p.M = a.M; p.N = a.N; p.K = a.K; p.act = a.act; p.alpha = a.alpha;
     p.tiles_m = egm_cdiv(a.M, BM); p.tiles_n = egm_cdiv(a.N, 64 * nt);
     const int grid = 256;                                             // one workgroup per CU, 32 per XCD; each walks its XCD's tile list
-    if (egm_gemm_dma_mode(-1) == 2 && nt >= 3)                         // the 4-wave form (128-row wave tiles)
+    if (pl.nw == 4)
         return nt == 4 ? launch_dma_nt<4, 4>(p, grid, a.R != nullptr, a.act, st) : launch_dma_nt<3, 4>(p, grid, a.R != nullptr, a.act, st);
     switch (nt) {
         case 4: return launch_dma_nt<4, 8>(p, grid, a.R != nullptr, a.act, st);

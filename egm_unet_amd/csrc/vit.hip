@@ -629,20 +629,35 @@ __global__ void cast_f32_kernel(const float* __restrict__ src, T* __restrict__ d
 
 inline int sgrid(long long total) { long long b = (total + 255) / 256; if (b > 4096) b = 4096; return (int)(b < 1 ? 1 : b); }
 
-template <typename T>
-int launch_gemm(const GemmParams& p, int transB, int batch, hipStream_t st) {
-    using M_ = GMma<T>;
-    if (sizeof(T) == 2 && transB && batch == 1 && !p.c_f32) {      // the products that fill the chip with 256 x 256 tiles: csrc/gemm_dma.hip
-        GemmDmaArgs a;
+// Which kernel a product takes: the ONE decision, read by launch_gemm and by the planner query egm_gemm_kernel_name.
+enum { GEMM_PLAIN = 0, GEMM_NT128_22, GEMM_NT128_24, GEMM_DMA };
+struct GemmPlan { int form; GemmDmaArgs dma; GemmDmaPlan dp; };
+GemmPlan gemm_plan(bool bf16, const GemmParams& p, int transB, int batch) {
+    GemmPlan pl;
+    pl.form = GEMM_PLAIN; pl.dp.nt = 0; pl.dp.nw = 8;
+    if (bf16 && transB && batch == 1 && !p.c_f32) {                // the products that fill the chip with 256 x 256 tiles: csrc/gemm_dma.hip
+        GemmDmaArgs& a = pl.dma;
         a.A = p.A; a.B = p.B; a.C = p.C; a.bias = p.bias; a.R = p.R;
         a.lda = p.lda; a.ldb = p.ldb; a.ldc = p.ldc; a.ldr = p.ldr; a.M = p.M; a.N = p.N; a.K = p.K; a.act = p.act; a.alpha = p.alpha;
-        if (egm_gemm_dma_ok(a)) return egm_gemm_dma_launch(a, st);
+        pl.dp = egm_gemm_dma_plan(a);
+        if (pl.dp.nt != 0) { pl.form = GEMM_DMA; return pl; }
     }
-    if (sizeof(T) == 2 && transB && p.M >= 128 && p.N >= 48 && p.K % 8 == 0) {          // the large A * B^T products (N >= 48: the 768 -> 64 reduce projections of CLIPSeg at 15 520 rows run 24 synchronous 32-deep chunks in gemm_kernel, 38 us for 24 MB of reading; here 12 prefetched 64-deep chunks on a half-empty 128-wide tile)
+    if (bf16 && transB && p.M >= 128 && p.N >= 48 && p.K % 8 == 0) {          // the large A * B^T products (N >= 48: the 768 -> 64 reduce projections of CLIPSeg at 15 520 rows run 24 synchronous 32-deep chunks in gemm_kernel, 38 us for 24 MB of reading; here 12 prefetched 64-deep chunks on a half-empty 128-wide tile)
         // 128 x 256 tiles (32 MFMAs per wave between barriers) when they still give every CU a few workgroups, else 128 x 128
         // 256 x 128 tiles (8 waves; 1/170 staged byte per FLOP instead of 1/128) when they still give every CU two workgroups
         const long long wg256 = (long long)((p.N + 127) / 128) * ((p.M + 255) / 256) * batch;
-        if (p.M >= 256 && wg256 >= 512) {
+        pl.form = (p.M >= 256 && wg256 >= 512) ? GEMM_NT128_24 : GEMM_NT128_22;
+    }
+    return pl;
+}
+
+template <typename T>
+int launch_gemm(const GemmParams& p, int transB, int batch, hipStream_t st) {
+    using M_ = GMma<T>;
+    const GemmPlan pl = gemm_plan(sizeof(T) == 2, p, transB, batch);
+    if (pl.form == GEMM_DMA) return egm_gemm_dma_launch(pl.dma, st);
+    if (pl.form == GEMM_NT128_24 || pl.form == GEMM_NT128_22) {
+        if (pl.form == GEMM_NT128_24) {
             dim3 grid2((p.N + 127) / 128, (p.M + 255) / 256, batch);
             hipLaunchKernelGGL((gemm_nt128_kernel<2, 4>), grid2, dim3(512), (size_t)(256 + 128) * (64 * 2 + 16), st, p);
         } else {
@@ -678,6 +693,27 @@ extern "C" int egm_gemm(int dtype, const void* A, int lda, const void* B, int ld
     if (dtype == EGM_BF16) return launch_gemm<bf16_t>(p, transB, nb1 * nb2, (hipStream_t)s);
     if (dtype == EGM_F32) return launch_gemm<float>(p, transB, nb1 * nb2, (hipStream_t)s);
     EGM_FAIL(EGM_ERR_ARG, "gemm: unknown dtype %d", dtype);
+}
+
+// The name of the kernel egm_gemm launches for a product, as a kernel trace spells it (the planner query of the GEMM, like
+// egm_conv_kernel_name): host only, no device needed.  Pointers count as 16-byte aligned; ldr = 0: no residual.
+extern "C" int egm_gemm_kernel_name(int dtype, int transB, int c_is_f32, int M, int N, int K, int lda, int ldb, int ldc, int ldr, int batch,
+                                    char* buf, int buflen) {
+    EGM_REQUIRE((dtype == EGM_BF16 || dtype == EGM_F32) && M > 0 && N > 0 && K > 0 && batch > 0, "gemm_kernel_name: bad args");
+    void* const al = reinterpret_cast<void*>(uintptr_t(4096));           // stands for any 16-byte aligned pointer; never dereferenced
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = al; p.B = al; p.C = al; p.bias = nullptr; p.R = ldr ? al : nullptr;
+    p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.M = M; p.N = N; p.K = K; p.nb2 = 1; p.act = 0; p.c_f32 = c_is_f32; p.alpha = 1.f;
+    const GemmPlan pl = gemm_plan(dtype == EGM_BF16, p, transB, batch);
+    char tmp[96];
+    if (pl.form == GEMM_DMA) snprintf(tmp, sizeof(tmp), "gemm_dma_kernel<%d, %d>", pl.dp.nt, pl.dp.nw);
+    else if (pl.form == GEMM_NT128_24) snprintf(tmp, sizeof(tmp), "gemm_nt128_kernel<2, 4>");
+    else if (pl.form == GEMM_NT128_22) snprintf(tmp, sizeof(tmp), "gemm_nt128_kernel<2, 2>");
+    else snprintf(tmp, sizeof(tmp), "gemm_kernel<%s, %s>", dtype == EGM_BF16 ? "bf16_t" : "float", transB ? "true" : "false");
+    const int n = (int)strlen(tmp);
+    if (buf != nullptr && buflen > 0) { strncpy(buf, tmp, (size_t)buflen - 1); buf[buflen - 1] = 0; }
+    return n;
 }
 
 extern "C" int egm_attention_fused(int dtype, const void* qkv, int ld, int B, int L, int H, int head_dim, int mode, void* out, int ldo,

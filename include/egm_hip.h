@@ -477,6 +477,15 @@ int egm_gemm(int dtype, const void* A, int lda, const void* B, int ldb, int tran
              const float* bias, int act, const void* R, int ldr, float alpha, int M, int N, int K, int nb1, int nb2,
              long long sA1, long long sA2, long long sB1, long long sB2, long long sC1, long long sC2, long long sR1,
              long long sR2, egm_stream_t s);
+/* Name of the kernel egm_gemm launches for a product, spelled like the rows of a kernel trace; returns its length, copies at most
+ * buflen-1 characters into buf (may be NULL).  Host only, needs no device (as egm_conv_kernel_name).  ldr = 0: no residual; batch =
+ * nb1 * nb2; every pointer counts as 16-byte aligned; honours egm_gemm_dma_mode.  One of
+ *   gemm_kernel<bf16_t, true>  gemm_kernel<bf16_t, false>  gemm_kernel<float, true>  gemm_kernel<float, false>
+ *   gemm_nt128_kernel<2, 2>  gemm_nt128_kernel<2, 4>
+ *   gemm_dma_kernel<NT, NW>   NT 1..4 with NW 8; NT 3, 4 with NW 4 under mode 2.  The two middle template arguments of the trace
+ *                             (<NT, HAS_R, ACT, NW>: residual and activation, which do not move the plan) are left out of the name. */
+int egm_gemm_kernel_name(int dtype, int transB, int c_is_f32, int M, int N, int K, int lda, int ldb, int ldc, int ldr, int batch,
+                         char* buf, int buflen);
 /* Large bf16 A * B^T products (M >= 512, N >= 256, K a multiple of 64, one batch, >= 128 tiles of 256 x 256) run on the 8-wave LDS-DMA
  * kernel (csrc/gemm_dma.hip), bit-identical to the register-staged one.  mode 1 / 0: on / off, 2: its 4-wave form (128-row wave tiles),
  * 3: on without the 256 x 128 tile rule, 4: 256-wide tiles whatever N (both for A/B runs, profiles/r04_ab_runs.md), -1: query; returns the
