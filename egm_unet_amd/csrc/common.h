@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include "../../include/egm_hip.h"
 
 // ---------------------------------------------------------------- error handling
@@ -15,6 +17,31 @@ void egm_set_error(const char* fmt, ...);
 
 static inline bool egm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int egm_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// start value of a mode switch that also has a setter (egm_conv_tile_mode, egm_conv_c7_mode, egm_gemm_dma_mode)
+static inline int egm_env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+
+// ---------------------------------------------------------------- launch idioms (host)
+// More than 64 KiB of dynamic LDS needs an opt-in per kernel: done once per instantiation (the kernel IS the template argument).
+//     if (int rc = egm_allow_max_lds<kern>("conv_igemm")) return rc;
+template <auto Kernel> int egm_allow_max_lds(const char* what, int bytes = 160 * 1024) {
+    static bool done = false;
+    if (!done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+        done = true;
+    }
+    return EGM_OK;
+}
+// Run-time epilogue activation (EGM_ACT_*) -> the instantiation: f(std::integral_constant<int, ACT>()).  Anything but RELU / SIGMOID /
+// SILU takes the plain form (the entry points have checked the range).
+template <typename F> auto egm_with_act(int act, F&& f) {
+    switch (act) {
+        case EGM_ACT_RELU: return f(std::integral_constant<int, EGM_ACT_RELU>());
+        case EGM_ACT_SIGMOID: return f(std::integral_constant<int, EGM_ACT_SIGMOID>());
+        case EGM_ACT_SILU: return f(std::integral_constant<int, EGM_ACT_SILU>());
+        default: return f(std::integral_constant<int, EGM_ACT_NONE>());
+    }
+}
 
 // ---------------------------------------------------------------- conv weight operand images
 // Element offset of (tap, co, c) inside a packed weight image with Cout x Cin (padded) entries per tap:

@@ -303,17 +303,6 @@ int waves_for(long long ntiles, int cap) {
     if (w < 1) w = 1;
     return (int)w;
 }
-template <typename K> int set_smem(K kernel, int smem) {
-    (void)smem;
-    static const void* done[64];
-    static int ndone = 0;
-    const void* f = reinterpret_cast<const void*>(kernel);
-    for (int i = 0; i < ndone; ++i) if (done[i] == f) return EGM_OK;
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv1x1_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    if (ndone < 64) done[ndone++] = f;
-    return EGM_OK;
-}
 
 // vectors per lane of a tile of `nc` channels
 template <typename T> int cv_of(int nc) { return (32 * (nc / Pw<T>::VEC) + 63) / 64; }
@@ -358,7 +347,7 @@ int conv1x1_bwd_t(const egm_conv1x1_bwd_desc* d, int n, egm_stream_t s) {
         ni = std::max(ni, r32(q.Cout) / 32);
         gy = std::max(gy, (q.Cin + 63) / 64);
     }
-#define C1_LAUNCH(KV, NIV) do { if (int rc = set_smem(conv1x1_bwd_kernel<T, KV, NIV>, smem)) return rc; \
+#define C1_LAUNCH(KV, NIV) do { if (int rc = egm_allow_max_lds<conv1x1_bwd_kernel<T, KV, NIV>>("conv1x1_bwd")) return rc; \
         hipLaunchKernelGGL((conv1x1_bwd_kernel<T, KV, NIV>), dim3(blk, gy), dim3(64 * L.nw), smem, (hipStream_t)s, L); } while (0)
     if (ni <= 2) { if (kk <= 4) C1_LAUNCH(4, 2); else if (kk <= 8) C1_LAUNCH(8, 2); else C1_LAUNCH(16, 2); }
     else { if (kk <= 8) C1_LAUNCH(8, 4); else C1_LAUNCH(16, 4); }

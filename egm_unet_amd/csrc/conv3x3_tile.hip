@@ -27,9 +27,10 @@
 //     tile -> whole 16-byte channel vectors -> coalesced stores (+bias), BatchNorm partial sums in registers over all tiles.
 //   * XCD-aware block -> (pixel group, cout tile) map as in conv_igemm.hip.
 #include "common.h"
+#include "conv_plan.h"
+#include "lds_dma.h"
 #include "group.h"
 #include "bn_elem.h"
-#include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
@@ -67,24 +68,6 @@ template <int R, int NT, int WR, int WC, int NBUF> struct TileGeom {
     static_assert(9 * NC * 32 + 64 * 32 < 65536, "ds_read immediate offsets");
 };
 
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-// two fp32 -> one dword of two bf16 (round to nearest even): ONE v_cvt_pk_bf16_f32 (the scalar casts were paired crosswise by the
-// vectoriser and re-shuffled with and / shift / or: 6 instructions per 4 values instead of 2)
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-    f32x2_t v; v.x = lo; v.y = hi;
-    const bf16x2_t b = __builtin_convertvector(v, bf16x2_t);
-    return *reinterpret_cast<const uint32_t*>(&b);
-}
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_byte_addr) {
-    // LDS-DMA from inline asm: through the builtin the compiler orders it against every ds_read (vmcnt(0) in front of the first
-    // fragment read).  M0 = wave-uniform LDS base; lane l lands at base + 16 l.  Ordering is ours: counted vmcnt + s_barrier.
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr));
-}
-
 template <int R, int NT, int WR, int WC, int NBUF>
 __global__ __launch_bounds__(512, 2) void conv3x3_tile_kernel(TileParams p) {
     constexpr int ACT = EGM_ACT_NONE;
@@ -103,13 +86,7 @@ int launch_tile(const TileParams& p, hipStream_t st) {
         if constexpr (ACT == EGM_ACT_NONE) return &conv3x3_tile_kernel<R, NT, WR, WC, NBUF>;
         else return &conv3x3_tile_act_kernel<R, NT, WR, WC, NBUF, ACT>;
     }();
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv3x3_tile: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
+    if (int rc = egm_allow_max_lds<kern>("conv3x3_tile")) return rc;
     const int grid = ((p.G + 7) / 8) * 8 * p.nct;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), Gm::SMEM, st, p);
     EGM_CHECK_LAUNCH("conv3x3_tile");
@@ -132,7 +109,7 @@ constexpr TileCfg kCfgs[] = {
 // registers kernel for the 32 -> 32 layers (conv3x3_wreg.hip).  -1: not read yet (env EGM_CONV_TILE, default 5); 0 = 4-wave kernel only
 static int g_tile_mode = -1;
 extern "C" int egm_conv_tile_mode(int mode) {
-    if (g_tile_mode < 0) g_tile_mode = getenv("EGM_CONV_TILE") ? atoi(getenv("EGM_CONV_TILE")) : 5;
+    if (g_tile_mode < 0) g_tile_mode = egm_env_int("EGM_CONV_TILE", 5);
     const int old = g_tile_mode;
     if (mode >= 0) g_tile_mode = mode;
     return old;
@@ -150,9 +127,7 @@ int egm_conv_tile_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH
     if (Cout % 32 != 0) return 0;
     if (egm_group_recording()) return 0;                     // merged launches of small sibling convs stay on the 4-wave kernel
     if (!(egm_conv_tile_mode(-1) & 1)) return 0;
-    static int min_cin = -1;
-    if (min_cin < 0) min_cin = getenv("EGM_TILE_MIN_CIN") ? atoi(getenv("EGM_TILE_MIN_CIN")) : 16;
-    if (Cin < min_cin) return 0;
+    if (Cin < 16) return 0;              // (r04: 32-channel inputs on the 4-wave kernel instead, i.e. 64 here: step 12.07 -> 12.11 ms, not kept)
     const int tx = egm_cdiv(W, TW);
     int best = -1, best_nct = 0, best_npt = 0;
     long long best_score = -1;
@@ -202,28 +177,23 @@ int egm_conv_tile_launch(const void* x, int ldx, const void* wf, const float* bi
     p.tiles_y = egm_cdiv(H, rows); p.tiles_x = egm_cdiv(W, TW); p.npt = N * p.tiles_y * p.tiles_x; p.nct = nct; p.G = G;
     EGM_REQUIRE((long long)(rows + 2) * W * ldx < (1LL << 31), "conv3x3_tile: halo window offsets exceed 32 bits");
     hipStream_t st = (hipStream_t)s;
-    if (act != EGM_ACT_NONE) {
-        // egm_conv_fwd_act: the configurations the default plan selects (>= 64-cout tiles; the 32-cout ones are an A/B mode only)
-        EGM_REQUIRE(cfg <= 3 && y2 == nullptr, "conv3x3_tile: no activation instantiation for tile configuration %d", cfg);
-        switch (cfg * 4 + act) {
-#define EGM_TILE_ACT(c, R_, NT_, WR_, WC_) \
-            case c * 4 + EGM_ACT_RELU: return launch_tile<R_, NT_, WR_, WC_, 2, EGM_ACT_RELU>(p, st); \
-            case c * 4 + EGM_ACT_SIGMOID: return launch_tile<R_, NT_, WR_, WC_, 2, EGM_ACT_SIGMOID>(p, st); \
-            case c * 4 + EGM_ACT_SILU: return launch_tile<R_, NT_, WR_, WC_, 2, EGM_ACT_SILU>(p, st);
-            EGM_TILE_ACT(0, 4, 2, 4, 2)
-            EGM_TILE_ACT(1, 2, 2, 4, 2)
-            EGM_TILE_ACT(2, 4, 2, 8, 1)
-            EGM_TILE_ACT(3, 2, 2, 8, 1)
-#undef EGM_TILE_ACT
-            default: EGM_FAIL(EGM_ERR_ARG, "conv3x3_tile: unknown activation %d", act);
+    // configurations 0..3, the ones the default plan selects (>= 64-cout tiles), have an instantiation per activation
+    auto wide = [&](auto a) {
+        constexpr int ACT = decltype(a)::value;
+        switch (cfg) {
+            case 0: return launch_tile<4, 2, 4, 2, 2, ACT>(p, st);
+            case 1: return launch_tile<2, 2, 4, 2, 2, ACT>(p, st);
+            case 2: return launch_tile<4, 2, 8, 1, 2, ACT>(p, st);
+            default: return launch_tile<2, 2, 8, 1, 2, ACT>(p, st);
         }
+    };
+    if (act != EGM_ACT_NONE) {
+        // egm_conv_fwd_act: the 32-cout configurations are an A/B mode only
+        EGM_REQUIRE(cfg <= 3 && y2 == nullptr, "conv3x3_tile: no activation instantiation for tile configuration %d", cfg);
+        EGM_REQUIRE(act >= EGM_ACT_RELU && act <= EGM_ACT_SILU, "conv3x3_tile: unknown activation %d", act);
+        return egm_with_act(act, wide);
     }
-    switch (cfg) {
-        case 0: return launch_tile<4, 2, 4, 2, 2>(p, st);
-        case 1: return launch_tile<2, 2, 4, 2, 2>(p, st);
-        case 2: return launch_tile<4, 2, 8, 1, 2>(p, st);
-        case 3: return launch_tile<2, 2, 8, 1, 2>(p, st);
-        case 4: return launch_tile<4, 1, 8, 1, 2>(p, st);
-        default: return launch_tile<2, 1, 8, 1, 2>(p, st);
-    }
+    if (cfg == 4) return launch_tile<4, 1, 8, 1, 2>(p, st);
+    if (cfg >= 5) return launch_tile<2, 1, 8, 1, 2>(p, st);
+    return wide(std::integral_constant<int, EGM_ACT_NONE>());
 }

@@ -22,14 +22,13 @@
 //     tile i's epilogue overlaps tile i+1's first stages").
 //   * zero page for out-of-image lanes, XCD-aware block map, epilogue and BatchNorm partial sums as in conv3x3_tile.hip.
 #include "common.h"
+#include "conv_plan.h"
+#include "lds_dma.h"
 #include "group.h"
 #include "bn_elem.h"
-#include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
 __device__ uint4 egm_dump_wreg[64];                   // where the stores of lanes outside the image go (never read)
 __device__ uint4 egm_zero_page_wreg[4];               // zero-initialised: source of DMA lanes outside the image (device symbols are per code object)
@@ -52,18 +51,7 @@ struct WregParams {
     int tiles_y, tiles_x, npt, G;
 };
 
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-    f32x2_t v; v.x = lo; v.y = hi;
-    const bf16x2_t b = __builtin_convertvector(v, bf16x2_t);
-    return *reinterpret_cast<const uint32_t*>(&b);
-}
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr));
-}
-
-template <int CH>          // CH = Cin / 32 (only 1 is offered: Cin = 64 needs 144 weight registers)
+template <int CH>         // CH = Cin / 32 (only 1 is offered: Cin = 64 needs 144 weight registers)
 __global__ __launch_bounds__(512, 2) void conv3x3_wreg_kernel(WregParams p) {
     constexpr int ACT = EGM_ACT_NONE;
 #include "conv3x3_wreg_body.h"
@@ -77,19 +65,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wreg_act_kernel(WregParams p) 
 template <int CH, int ACT = EGM_ACT_NONE>
 int launch_wreg(const WregParams& p, hipStream_t st) {
     constexpr auto kern = [] { if constexpr (ACT == EGM_ACT_NONE) return &conv3x3_wreg_kernel<CH>; else return &conv3x3_wreg_act_kernel<CH, ACT>; }();
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv3x3_wreg: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
+    if (int rc = egm_allow_max_lds<kern>("conv3x3_wreg")) return rc;
     hipLaunchKernelGGL(kern, dim3(p.G), dim3(512), SMEM, st, p);
     EGM_CHECK_LAUNCH("conv3x3_wreg");
     return EGM_OK;
 }
 }  // namespace
-
-int egm_conv_tile_mode(int mode);
 
 // Plan: 1 when the shape takes this kernel (then *G_out = pixel groups = BatchNorm statistics rows)
 int egm_conv_wreg_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int* G_out) {
@@ -110,10 +91,5 @@ int egm_conv_wreg_launch(const void* x, int ldx, const void* wf, const float* bi
     p.ldx = ldx; p.ldy = ldy; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.bias_n = bias ? bias_n : 0;
     p.tiles_y = egm_cdiv(H, TROWS); p.tiles_x = egm_cdiv(W, TW); p.npt = N * p.tiles_y * p.tiles_x; p.G = G;
     EGM_REQUIRE((long long)(PH + 1) * W * ldx < (1LL << 31), "conv3x3_wreg: halo window offsets exceed 32 bits");
-    switch (act) {
-        case EGM_ACT_RELU: return launch_wreg<1, EGM_ACT_RELU>(p, (hipStream_t)s);
-        case EGM_ACT_SIGMOID: return launch_wreg<1, EGM_ACT_SIGMOID>(p, (hipStream_t)s);
-        case EGM_ACT_SILU: return launch_wreg<1, EGM_ACT_SILU>(p, (hipStream_t)s);
-        default: return launch_wreg<1>(p, (hipStream_t)s);
-    }
+    return egm_with_act(act, [&](auto a) { return launch_wreg<1, decltype(a)::value>(p, (hipStream_t)s); });
 }

@@ -132,8 +132,8 @@
                     for (int j = 0; j < 4; ++j) acc[m][gq * 4 + j] = conv_epi_act<ACT, true>(acc[m][gq * 4 + j]);
                 }
                 uint2 v;
-                v.x = pack2(acc[m][gq * 4 + 0], acc[m][gq * 4 + 1]);
-                v.y = pack2(acc[m][gq * 4 + 2], acc[m][gq * 4 + 3]);
+                v.x = pack_bf16x2(acc[m][gq * 4 + 0], acc[m][gq * 4 + 1]);
+                v.y = pack_bf16x2(acc[m][gq * 4 + 2], acc[m][gq * 4 + 3]);
                 *reinterpret_cast<uint2*>(ot + (m * 32 + r31) * OROW + (gq * 8 + h * 4) * 2) = v;
             }
     };

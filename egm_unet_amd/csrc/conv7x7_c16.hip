@@ -17,6 +17,7 @@
 //     image [pixel][half] is conflict-free for this fragment shape: every group holds eight pixel columns of one half and the other
 //     eight of the other half.
 #include "common.h"
+#include "conv_plan.h"
 #include "bn_elem.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -467,7 +468,7 @@ __global__ __launch_bounds__(256) void conv3x3d_c16_act_kernel(CDParams p) { con
 static int g_c7_mode = -1;
 /* 1 = the 16-channel 7x7 convs take this kernel (default; env EGM_CONV_C7=0 or mode 0: the generic pipelined kernel), -1 = query */
 extern "C" int egm_conv_c7_mode(int mode) {
-    if (g_c7_mode < 0) g_c7_mode = getenv("EGM_CONV_C7") ? atoi(getenv("EGM_CONV_C7")) : 1;
+    if (g_c7_mode < 0) g_c7_mode = egm_env_int("EGM_CONV_C7", 1);
     const int old = g_c7_mode;
     if (mode >= 0) g_c7_mode = mode;
     return old;
@@ -486,12 +487,11 @@ int egm_conv_c7_launch(const void* x, int ldx, const void* wf, const float* bias
     p.ldx = ldx; p.ldy = ldy; p.N = N; p.H = H; p.W = W; p.bias_n = bias ? bias_n : 0;
     p.tiles_y = egm_cdiv(H, C7_R); p.tiles_x = egm_cdiv(W, C7_TW);
     const dim3 grid(N * p.tiles_y * p.tiles_x);
-    switch (act) {
-        case EGM_ACT_RELU: hipLaunchKernelGGL(conv7x7_c16_act_kernel<EGM_ACT_RELU>, grid, dim3(256), 0, (hipStream_t)s, p); break;
-        case EGM_ACT_SIGMOID: hipLaunchKernelGGL(conv7x7_c16_act_kernel<EGM_ACT_SIGMOID>, grid, dim3(256), 0, (hipStream_t)s, p); break;
-        case EGM_ACT_SILU: hipLaunchKernelGGL(conv7x7_c16_act_kernel<EGM_ACT_SILU>, grid, dim3(256), 0, (hipStream_t)s, p); break;
-        default: hipLaunchKernelGGL(conv7x7_c16_kernel, grid, dim3(256), 0, (hipStream_t)s, p);
-    }
+    egm_with_act(act, [&](auto a) {
+        constexpr int ACT = decltype(a)::value;
+        if constexpr (ACT == EGM_ACT_NONE) hipLaunchKernelGGL(conv7x7_c16_kernel, grid, dim3(256), 0, (hipStream_t)s, p);
+        else hipLaunchKernelGGL(conv7x7_c16_act_kernel<ACT>, grid, dim3(256), 0, (hipStream_t)s, p);
+    });
     EGM_CHECK_LAUNCH("conv7x7_c16");
     return EGM_OK;
 }
@@ -546,12 +546,11 @@ int egm_conv_c16d_launch(const void* x, int ldx, const void* wf, const float* bi
     p.tiles_y = egm_cdiv(H, WD_RB); p.tiles_x = egm_cdiv(W, WD_TW);
     const dim3 grid(N * p.tiles_y * p.tiles_x);
     EGM_REQUIRE(act == EGM_ACT_NONE || stats == nullptr, "conv3x3d_c16: no statistics with an activation");
-    switch (act) {
-        case EGM_ACT_RELU: hipLaunchKernelGGL(conv3x3d_c16_act_kernel<EGM_ACT_RELU>, grid, dim3(256), 0, (hipStream_t)s, p); break;
-        case EGM_ACT_SIGMOID: hipLaunchKernelGGL(conv3x3d_c16_act_kernel<EGM_ACT_SIGMOID>, grid, dim3(256), 0, (hipStream_t)s, p); break;
-        case EGM_ACT_SILU: hipLaunchKernelGGL(conv3x3d_c16_act_kernel<EGM_ACT_SILU>, grid, dim3(256), 0, (hipStream_t)s, p); break;
-        default: hipLaunchKernelGGL(conv3x3d_c16_kernel, grid, dim3(256), 0, (hipStream_t)s, p);
-    }
+    egm_with_act(act, [&](auto a) {
+        constexpr int ACT = decltype(a)::value;
+        if constexpr (ACT == EGM_ACT_NONE) hipLaunchKernelGGL(conv3x3d_c16_kernel, grid, dim3(256), 0, (hipStream_t)s, p);
+        else hipLaunchKernelGGL(conv3x3d_c16_act_kernel<ACT>, grid, dim3(256), 0, (hipStream_t)s, p);
+    });
     EGM_CHECK_LAUNCH("conv3x3d_c16");
     return EGM_OK;
 }

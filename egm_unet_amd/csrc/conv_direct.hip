@@ -13,6 +13,7 @@
 // HBM-bound for the narrow layers (C <= 64), MFMA-bound for 256 -> 256; algorithmic work as for conv_igemm.hip.
 #include <type_traits>
 #include "common.h"
+#include "conv_plan.h"
 #include "group.h"
 #include "bn_elem.h"
 #include <string.h>
@@ -241,8 +242,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(DirectParams p) {
 struct DirectMulti { DirectParams p[EGM_GROUP_MAX]; int blk0[EGM_GROUP_MAX + 1]; int n; };
 template <int NT, bool K1>
 __global__ __launch_bounds__(256) void conv_direct_multi_kernel(DirectMulti m) {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
+    EGM_GROUP_MEMBER(m, i);
     conv_direct_body<NT, K1, EGM_ACT_NONE>(m.p[i], (int)blockIdx.x - m.blk0[i]);
 }
 // the same with an activation in the epilogue (egm_conv_fwd_act)
@@ -252,8 +252,7 @@ __global__ __launch_bounds__(256) void conv_direct_act_kernel(DirectParams p) {
 }
 template <int NT, bool K1, int ACT>
 __global__ __launch_bounds__(256) void conv_direct_act_multi_kernel(DirectMulti m) {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
+    EGM_GROUP_MEMBER(m, i);
     conv_direct_body<NT, K1, ACT>(m.p[i], (int)blockIdx.x - m.blk0[i]);
 }
 template <int NT, bool K1, int ACT> constexpr auto direct_kernel() {
@@ -274,35 +273,16 @@ int launch_direct_group(const EgmGroupRec* recs, int n, hipStream_t st) {
         EGM_CHECK_LAUNCH("conv_direct");
         return EGM_OK;
     }
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(direct_multi_kernel<NT, K1, ACT>()), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_direct_multi: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
+    if (int rc = egm_allow_max_lds<direct_multi_kernel<NT, K1, ACT>()>("conv_direct_multi")) return rc;
     DirectMulti m;
-    size_t smem = 0;
-    m.n = n; m.blk0[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        memcpy(&m.p[i], recs[i].params, sizeof(DirectParams));
-        m.blk0[i + 1] = m.blk0[i] + recs[i].grid;                      // grids are multiples of 8: every member starts on XCD 0
-        if (recs[i].smem > smem) smem = recs[i].smem;
-    }
-    for (int i = n; i < EGM_GROUP_MAX; ++i) { m.p[i] = m.p[0]; m.blk0[i + 1] = m.blk0[n]; }
+    const size_t smem = egm_group_fill<DirectParams>(m, recs, n, [](int, const EgmGroupRec*) {});
     hipLaunchKernelGGL((direct_multi_kernel<NT, K1, ACT>()), dim3(m.blk0[n]), dim3(256), smem, st, m);
     EGM_CHECK_LAUNCH("conv_direct_multi");
     return EGM_OK;
 }
 template <int NT, bool K1, int ACT>
 int launch_direct_k(const DirectParams& p, size_t smem, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(direct_kernel<NT, K1, ACT>()), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_direct: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
+    if (int rc = egm_allow_max_lds<direct_kernel<NT, K1, ACT>()>("conv_direct")) return rc;
     EGM_REQUIRE(smem <= 160 * 1024, "conv_direct: LDS budget exceeded (%zu)", smem);
     const int grid = ((p.G + 7) / 8) * 8 * p.nct;
     if (egm_group_recording()) {                                       // launched by egm_group_end(), merged with its siblings
@@ -324,12 +304,7 @@ int launch_direct(const DirectParams& p, size_t smem, hipStream_t st) {
 }
 template <int NT>
 int launch_direct_act(const DirectParams& p, size_t smem, hipStream_t st, int act) {
-    switch (act) {
-        case EGM_ACT_RELU: return launch_direct<NT, EGM_ACT_RELU>(p, smem, st);
-        case EGM_ACT_SIGMOID: return launch_direct<NT, EGM_ACT_SIGMOID>(p, smem, st);
-        case EGM_ACT_SILU: return launch_direct<NT, EGM_ACT_SILU>(p, smem, st);
-        default: return launch_direct<NT, EGM_ACT_NONE>(p, smem, st);
-    }
+    return egm_with_act(act, [&](auto a) { return launch_direct<NT, decltype(a)::value>(p, smem, st); });
 }
 
 }  // namespace
@@ -340,8 +315,6 @@ int egm_conv_direct_plan(int dtype, int N, int H, int W, int Cin, int Cout, int 
                          size_t* smem_out) {
     if (dtype != EGM_BF16 || KH != KW) return 0;
     if (!((KH == 1) || (KH == 3 && dil > 1))) return 0;
-    static const int mode = getenv("EGM_CONV_DIRECT") ? atoi(getenv("EGM_CONV_DIRECT")) : 3;   // debug knob: bit0 = 1x1, bit1 = dilated
-    if (!(mode & (KH == 1 ? 1 : 2))) return 0;
     // Measured per shape against the LDS-tiled kernel (tools/conv_shapes_bench.py under rocprofv3): this kernel wins for the
     // dilated convs (no tap shares a tile anyway) and for wide-in / narrow-out 1x1 (64->16, 112->16); square 1x1 layers
     // (64->64 ... 256->256) stay with the tiled kernel, whose 64-byte-per-4-lanes loads coalesce better.

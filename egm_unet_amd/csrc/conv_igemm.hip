@@ -23,6 +23,7 @@
 // bf16: v_mfma_f32_32x32x16_bf16 (A = pixels x k, B = k x couts, fp32 accumulate)
 // f32 : v_mfma_f32_32x32x2_f32   (exact fp32 FMA chain; the parity path)
 #include "common.h"
+#include "conv_plan.h"
 #include "group.h"
 #include "bn_elem.h"
 #include <string.h>
@@ -31,32 +32,6 @@
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(2))) unsigned short u16x2_t;
-
-// conv_direct.hip: 1x1 / dilated convolutions without an LDS activation tile
-int egm_conv_direct_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int* NT_out, int* nct_out, int* G_out,
-                         size_t* smem_out);
-int egm_conv_direct_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy,
-                           float* stats, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int NT, int nct, int G, size_t smem,
-                           egm_stream_t s, int act = EGM_ACT_NONE);
-
-// conv3x3_tile.hip: 8-wave LDS-DMA 3x3 kernel (the throughput path of the 3x3 stacks)
-int egm_conv_tile_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int* cfg_out, int* nct_out, int* G_out);
-const char* egm_conv_tile_name(int cfg);
-// conv3x3_wreg.hip: weights-in-registers 3x3 kernel for the 32-cout layers
-int egm_conv_wreg_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int* G_out);
-const char* egm_conv_wreg_name(int Cin);
-int egm_conv_wreg_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, float* stats, int N, int H,
-                         int W, int Cin, int Cout, int G, egm_stream_t s, int act = EGM_ACT_NONE);
-int egm_conv_tile_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, float* stats, int N, int H,
-                         int W, int Cin, int Cout, int cfg, int nct, int G, egm_stream_t s, void* y2 = nullptr, int ldy2 = 0, int csplit = 0,
-                         int act = EGM_ACT_NONE);
-// conv7x7_c16.hip: weights-in-registers 7x7 kernel for 16 -> 16 channels (FusionConv's merged multi-scale conv at the 64-channel level)
-int egm_conv_c7_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil);
-int egm_conv_c7_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, int N, int H, int W,
-                       egm_stream_t s, int act = EGM_ACT_NONE);
-int egm_conv_c16d_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil);
-int egm_conv_c16d_launch(const void* x, int ldx, const void* wf, const float* bias, int bias_n, void* y, int ldy, float* stats, int N, int H,
-                         int W, int dil, egm_stream_t s, int act = EGM_ACT_NONE);
 
 namespace {
 
@@ -483,8 +458,7 @@ __global__ __launch_bounds__(256, (R * NT >= 8) ? 1 : 2) void conv_igemm_pipe_ke
 struct PipeMulti { ConvParams p[EGM_GROUP_MAX]; int G[EGM_GROUP_MAX]; int blk0[EGM_GROUP_MAX + 1]; int n; };
 template <int NT, int WH, int WW, int R>
 __global__ __launch_bounds__(256, (R * NT >= 8) ? 1 : 2) void conv_igemm_pipe_multi_kernel(PipeMulti m) {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
+    EGM_GROUP_MEMBER(m, i);
     conv_igemm_pipe_body<NT, WH, WW, R, EGM_ACT_NONE>(m.p[i], m.G[i], (int)blockIdx.x - m.blk0[i]);
 }
 // the same with an activation in the epilogue (egm_conv_fwd_act)
@@ -494,8 +468,7 @@ __global__ __launch_bounds__(256, (R * NT >= 8) ? 1 : 2) void conv_igemm_pipe_ac
 }
 template <int NT, int WH, int WW, int R, int ACT>
 __global__ __launch_bounds__(256, (R * NT >= 8) ? 1 : 2) void conv_igemm_pipe_act_multi_kernel(PipeMulti m) {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
+    EGM_GROUP_MEMBER(m, i);
     conv_igemm_pipe_body<NT, WH, WW, R, ACT>(m.p[i], m.G[i], (int)blockIdx.x - m.blk0[i]);
 }
 // kernel of an instantiation: the training kernels for ACT = NONE, the *_act_* ones otherwise
@@ -564,19 +537,12 @@ __global__ __launch_bounds__(256) void conv_pack_multi_kernel(const PackEntry* _
 template <typename T, int NT, int ACT = EGM_ACT_NONE>
 int launch_conv(const ConvParams& p, size_t smem, hipStream_t st) {
     constexpr auto kern = [] { if constexpr (ACT == EGM_ACT_NONE) return &conv_igemm_kernel<T, NT>; else return &conv_igemm_act_kernel<T, NT, ACT>; }();
-    static bool attr_done = false;      // >64 KiB dynamic LDS needs an opt-in; done once per instantiation
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_igemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
+    if (int rc = egm_allow_max_lds<kern>("conv_igemm")) return rc;
     const int grid = ((p.npt + 7) / 8) * 8 * p.nct;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, p);
     EGM_CHECK_LAUNCH("conv_igemm");
     return EGM_OK;
 }
-
 
 // couts per workgroup = 32*NT: 64-wide tiles halve the patch traffic, 32-wide tiles double the workgroup count; take the
 // narrow tile when the wide one would leave CUs idle (small feature maps)
@@ -609,23 +575,9 @@ int launch_pipe_group(const EgmGroupRec* recs, int n, hipStream_t st) {
         EGM_CHECK_LAUNCH("conv_igemm_pipe");
         return EGM_OK;
     }
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pipe_multi_kernel<NT, WH, WW, R, ACT>()),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_igemm_pipe_multi: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
+    if (int rc = egm_allow_max_lds<pipe_multi_kernel<NT, WH, WW, R, ACT>()>("conv_igemm_pipe_multi")) return rc;
     PipeMulti m;
-    size_t smem = 0;
-    m.n = n; m.blk0[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        memcpy(&m.p[i], recs[i].params, sizeof(ConvParams));
-        m.G[i] = recs[i].G;
-        m.blk0[i + 1] = m.blk0[i] + recs[i].grid;                      // grids are multiples of 8: every member starts on XCD 0
-        if (recs[i].smem > smem) smem = recs[i].smem;
-    }
-    for (int i = n; i < EGM_GROUP_MAX; ++i) { m.p[i] = m.p[0]; m.G[i] = 0; m.blk0[i + 1] = m.blk0[n]; }
+    const size_t smem = egm_group_fill<ConvParams>(m, recs, n, [&](int i, const EgmGroupRec* r) { m.G[i] = r ? r->G : 0; });
     hipLaunchKernelGGL((pipe_multi_kernel<NT, WH, WW, R, ACT>()), dim3(m.blk0[n]), dim3(256), smem, st, m);
     EGM_CHECK_LAUNCH("conv_igemm_pipe_multi");
     return EGM_OK;
@@ -633,13 +585,7 @@ int launch_pipe_group(const EgmGroupRec* recs, int n, hipStream_t st) {
 template <int NT, int WH, int WW, int R, int ACT = EGM_ACT_NONE>
 int launch_pipe(ConvParams& p, int G, hipStream_t st) {
     using Gm = PipeGeom<WH, WW, R>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pipe_kernel<NT, WH, WW, R, ACT>()),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_igemm_pipe: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
+    if (int rc = egm_allow_max_lds<pipe_kernel<NT, WH, WW, R, ACT>()>("conv_igemm_pipe")) return rc;
     p.patch_bytes = (Gm::PH * Gm::PW * 80 + 15) / 16 * 16;
     const size_t smem = pipe_base_bytes<WH, WW, R>(NT);                                    // patch | weights | per-lane dump slots
     static_assert((size_t)4 * 32 * (NT * 64 + 16) <= (size_t)Gm::PH * Gm::PW * 80, "epilogue out tiles must fit inside the patch region");
@@ -662,60 +608,58 @@ int launch_pipe(ConvParams& p, int G, hipStream_t st) {
 // runtime activation -> instantiation (egm_conv_fwd_act)
 template <int NT, int WH, int WW, int R>
 int launch_pipe_act(ConvParams& p, int G, hipStream_t st, int act) {
-    switch (act) {
-        case EGM_ACT_RELU: return launch_pipe<NT, WH, WW, R, EGM_ACT_RELU>(p, G, st);
-        case EGM_ACT_SIGMOID: return launch_pipe<NT, WH, WW, R, EGM_ACT_SIGMOID>(p, G, st);
-        case EGM_ACT_SILU: return launch_pipe<NT, WH, WW, R, EGM_ACT_SILU>(p, G, st);
-        default: return launch_pipe<NT, WH, WW, R>(p, G, st);
-    }
+    return egm_with_act(act, [&](auto a) { return launch_pipe<NT, WH, WW, R, decltype(a)::value>(p, G, st); });
 }
 template <typename T, int NT>
 int launch_conv_act(const ConvParams& p, size_t smem, hipStream_t st, int act) {
-    switch (act) {
-        case EGM_ACT_RELU: return launch_conv<T, NT, EGM_ACT_RELU>(p, smem, st);
-        case EGM_ACT_SIGMOID: return launch_conv<T, NT, EGM_ACT_SIGMOID>(p, smem, st);
-        case EGM_ACT_SILU: return launch_conv<T, NT, EGM_ACT_SILU>(p, smem, st);
-        default: return launch_conv<T, NT>(p, smem, st);
-    }
+    return egm_with_act(act, [&](auto a) { return launch_conv<T, NT, decltype(a)::value>(p, smem, st); });
 }
 
 // One place decides kernel, tile shape and grouping, so the stats-tile count the caller allocates always matches the launch.
-struct ConvPlan { bool pipe, direct, tile, wreg, c7, c16d = false; int tile_cfg; int R, NT, tiles_y, tiles_x, npt, nct, G; size_t smem; };
+enum class ConvKernel { igemm, pipe, direct, tile, wreg, c16d };
+struct ConvPlan {
+    ConvKernel kernel = ConvKernel::igemm;
+    // The 7x7 16 -> 16 channel kernel (conv7x7_c16.hip) has no statistics epilogue: a launch takes it only when no BatchNorm statistics
+    // are asked for.  Everything else in the plan, the statistics-tile count G above all, stays that of `kernel` (the pipelined
+    // kernel), so the count a caller allocates does not depend on whether the launch will ask for statistics.
+    bool c7_without_stats = false;
+    int tile_cfg = 0;                 // tile: configuration of conv3x3_tile.hip
+    int R = 0, NT = 1;                // igemm / pipe: tile rows per wave; igemm / pipe / direct: 32-cout blocks per workgroup
+    int tiles_y = 0, tiles_x = 0, npt = 0, nct = 1;
+    int G = 0;                        // pixel groups = statistics tiles, every kernel
+    size_t smem = 0;                  // direct: dynamic LDS bytes
+    static ConvPlan of(ConvKernel k) { ConvPlan c; c.kernel = k; return c; }
+};
 ConvPlan conv_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil) {
-    ConvPlan c;
     if (KH == 1 && KW == 1) dil = 1;
-    c.tile_cfg = 0;
-    // taken at launch when no BatchNorm statistics are asked for (the kernel has no statistics epilogue); the rest of the plan stays
-    // that of the generic kernel, so a caller's statistics-tile count does not depend on it
-    c.c7 = !egm_group_recording() && egm_conv_c7_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil) != 0;
     // dilated 3x3 on 16 channels (conv7x7_c16.hip): launched at once, also inside a launch group (it has no merged form)
-    const int c16d = egm_conv_c16d_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil);
-    if (c16d > 0) { c.c16d = true; c.pipe = c.direct = c.tile = c.wreg = false; c.R = 0; c.NT = 1; c.nct = 1; c.tiles_y = c.tiles_x = c.npt = 0; c.smem = 0; c.G = c16d; return c; }
-    c.wreg = egm_conv_wreg_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil, &c.G) != 0;
-    if (c.wreg) { c.pipe = c.direct = c.tile = false; c.R = 2; c.NT = 1; c.nct = 1; c.tiles_y = c.tiles_x = c.npt = 0; c.smem = 0; return c; }
-    c.tile = egm_conv_tile_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil, &c.tile_cfg, &c.nct, &c.G) != 0;
-    if (c.tile) { c.pipe = c.direct = false; c.R = 2; c.NT = 2; c.tiles_y = c.tiles_x = c.npt = 0; c.smem = 0; return c; }
-    c.direct = Cin > 0 && egm_conv_direct_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil, &c.NT, &c.nct, &c.G, &c.smem) != 0;
-    if (c.direct) { c.pipe = false; c.R = 0; c.tiles_y = c.tiles_x = c.npt = 0; return c; }
-    c.pipe = pipe_eligible(dtype, KH, KW, dil);
+    if (ConvPlan c = ConvPlan::of(ConvKernel::c16d); (c.G = egm_conv_c16d_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil)) > 0) return c;
+    if (ConvPlan c = ConvPlan::of(ConvKernel::wreg); egm_conv_wreg_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil, &c.G)) return c;
+    if (ConvPlan c = ConvPlan::of(ConvKernel::tile); egm_conv_tile_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil, &c.tile_cfg, &c.nct, &c.G)) return c;
+    if (ConvPlan c = ConvPlan::of(ConvKernel::direct);
+        Cin > 0 && egm_conv_direct_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil, &c.NT, &c.nct, &c.G, &c.smem))
+        return c;
+    const bool pipe = pipe_eligible(dtype, KH, KW, dil);
+    ConvPlan c = ConvPlan::of(pipe ? ConvKernel::pipe : ConvKernel::igemm);
+    c.c7_without_stats = !egm_group_recording() && egm_conv_c7_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil) != 0;
     c.R = 2;
-    if (c.pipe && KH == 3 && dil == 1 && Cout <= 32) {
+    if (pipe && KH == 3 && dil == 1 && Cout <= 32) {
         // tall tiles (16 x 32 pixels, 4 rows per wave) for the narrow layers when they still fill the chip: 0.75 instead of
         // 1.5 LDS fragment reads per MFMA and half the weight re-staging.  (Measured: with 64-cout tiles the taller tile
         // needs one workgroup per CU and is no faster than two 8-row workgroups, so those keep R = 2.)
         const long long npt4 = (long long)N * egm_cdiv(H, 16) * egm_cdiv(W, TW);
         if (npt4 >= 256) c.R = 4;
     }
-    static const int r1_on = getenv("EGM_PIPE_R1") ? atoi(getenv("EGM_PIPE_R1")) : 1;   // (r04: 20.1 -> 18.7 us per bottleneck conv)
-    if (r1_on && c.pipe && KH == 3 && dil == 1 && c.R == 2 && Cout > 32 && Cin >= 128) {
+    if (pipe && KH == 3 && dil == 1 && c.R == 2 && Cout > 32 && Cin >= 128) {
         // the bottleneck (256 -> 256 at 32^2: 32 tiles of 8 x 32 pixels x 8 cout tiles = 256 workgroups, one per CU): 4-row tiles, 512
+        // (r04: 20.1 -> 18.7 us per bottleneck conv)
         const long long wgs2 = (long long)N * egm_cdiv(H, 8) * egm_cdiv(W, TW) * egm_cdiv(Cout, 32);
         if (wgs2 <= 256) c.R = 1;
     }
     c.tiles_y = egm_cdiv(H, 4 * c.R); c.tiles_x = egm_cdiv(W, TW); c.npt = N * c.tiles_y * c.tiles_x;
     c.NT = (c.R == 4) ? (Cout <= 32 ? 1 : 2) : (c.R == 1 ? 1 : conv_nt(c.npt, Cout));
     c.nct = egm_cdiv(Cout, 32 * c.NT);
-    if (!c.pipe) { c.G = c.npt; return c; }
+    if (!pipe) { c.G = c.npt; return c; }
     if (c.R == 4) {
         const int per_cu = (c.NT == 2) ? 1 : 2;                 // resident workgroups per CU (LDS / register budget)
         int g = (256 * per_cu / c.nct) / 8 * 8;
@@ -735,14 +679,16 @@ extern "C" int egm_conv_kernel_name(int dtype, int N, int H, int W, int Cin, int
     if (KH == 1 && KW == 1) dil = 1;
     const ConvPlan c = conv_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil);
     char tmp[96];
-    if (c.c16d) snprintf(tmp, sizeof(tmp), "conv3x3d_c16_kernel");
-    else if (c.c7) snprintf(tmp, sizeof(tmp), "conv7x7_c16_kernel");
-    else if (c.wreg) snprintf(tmp, sizeof(tmp), "%s", egm_conv_wreg_name(Cin));
-    else if (c.tile) snprintf(tmp, sizeof(tmp), "%s", egm_conv_tile_name(c.tile_cfg));
-    else if (c.direct) snprintf(tmp, sizeof(tmp), "conv_direct_kernel<%d, %s>", c.NT, KH == 1 ? "true" : "false");
-    else if (c.pipe) snprintf(tmp, sizeof(tmp), "conv_igemm_pipe_kernel<%d, %d, %d, %d>", c.NT, (KH == 3 && dil == 1) ? 3 : 1,
-                              (KH == 3 && dil == 1) ? 3 : (KH == 7 ? 7 : 1), c.R);
-    else snprintf(tmp, sizeof(tmp), "conv_igemm_kernel<%s, %d>", dtype == EGM_BF16 ? "bf16_t" : "float", c.NT);
+    if (c.c7_without_stats) snprintf(tmp, sizeof(tmp), "conv7x7_c16_kernel");
+    else switch (c.kernel) {
+        case ConvKernel::c16d: snprintf(tmp, sizeof(tmp), "conv3x3d_c16_kernel"); break;
+        case ConvKernel::wreg: snprintf(tmp, sizeof(tmp), "%s", egm_conv_wreg_name(Cin)); break;
+        case ConvKernel::tile: snprintf(tmp, sizeof(tmp), "%s", egm_conv_tile_name(c.tile_cfg)); break;
+        case ConvKernel::direct: snprintf(tmp, sizeof(tmp), "conv_direct_kernel<%d, %s>", c.NT, KH == 1 ? "true" : "false"); break;
+        case ConvKernel::pipe: snprintf(tmp, sizeof(tmp), "conv_igemm_pipe_kernel<%d, %d, %d, %d>", c.NT, (KH == 3 && dil == 1) ? 3 : 1,
+                                        (KH == 3 && dil == 1) ? 3 : (KH == 7 ? 7 : 1), c.R); break;
+        case ConvKernel::igemm: snprintf(tmp, sizeof(tmp), "conv_igemm_kernel<%s, %d>", dtype == EGM_BF16 ? "bf16_t" : "float", c.NT); break;
+    }
     const int n = (int)strlen(tmp);
     if (buf != nullptr && buflen > 0) { strncpy(buf, tmp, (size_t)buflen - 1); buf[buflen - 1] = 0; }
     return n;
@@ -778,8 +724,7 @@ extern "C" int egm_conv_pack_multi(int dtype, const void* table_dev, int n, long
 /* 1 when egm_conv_fwd_split takes this shape (the 8-wave 3x3 tile kernel does, with the split on an 8-channel boundary) */
 extern "C" int egm_conv_split_ok(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, int csplit) {
     if (csplit <= 0 || csplit >= Cout || csplit % 8 || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % 8 || Cout % 8) return 0;
-    const ConvPlan c = conv_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil);
-    return (!c.c7 && !c.wreg && c.tile) ? 1 : 0;
+    return conv_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil).kernel == ConvKernel::tile ? 1 : 0;
 }
 extern "C" int egm_conv_fwd_split(int dtype, const void* x, int ldx, const void* wf, void* y, int ldy, void* y2, int ldy2, int csplit, int N,
                                   int H, int W, int Cin, int Cout, int KH, int KW, int dil, egm_stream_t s) {
@@ -808,26 +753,27 @@ static int conv_fwd_impl(int dtype, const void* x, int ldx, const void* wf, cons
     p.ldx = ldx; p.ldy = ldy; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.dil = dil; p.bias_n = bias ? bias_n : 0;
     p.wl = egm_w_layout(dtype, KH, KW, Cin, Cout);
     const ConvPlan c = conv_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil);
-    if (c.c16d) return egm_conv_c16d_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, dil, s, act);
-    if (c.c7 && stats == nullptr) return egm_conv_c7_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, N, H, W, s, act);
-    if (c.wreg) return egm_conv_wreg_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, c.G, s, act);
-    if (c.tile)
-        return egm_conv_tile_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, c.tile_cfg, c.nct, c.G, s,
-                                    nullptr, 0, 0, act);
-    if (c.direct)
-        return egm_conv_direct_launch(x, ldx, wf, (const float*)bias, bias_n, y, ldy, stats, N, H, W, Cin, Cout, KH, KW, dil, c.NT,
-                                      c.nct, c.G, c.smem, s, act);
+    const float* b = (const float*)bias;
+    hipStream_t st = (hipStream_t)s;
+    if (c.c7_without_stats && stats == nullptr) return egm_conv_c7_launch(x, ldx, wf, b, bias_n, y, ldy, N, H, W, s, act);
     p.tiles_y = c.tiles_y; p.tiles_x = c.tiles_x; p.npt = c.npt; p.nct = c.nct;
     const int NT = c.NT;
-    if (c.pipe) {
-        hipStream_t st = (hipStream_t)s;
-        if (KH == 3 && dil == 1) {
-            if (c.R == 4) return launch_pipe_act<1, 3, 3, 4>(p, c.G, st, act);             // tall tiles: Cout <= 32 only (conv_plan)
-            if (c.R == 1) return launch_pipe_act<1, 3, 3, 1>(p, c.G, st, act);
-            return NT == 2 ? launch_pipe_act<2, 3, 3, 2>(p, c.G, st, act) : launch_pipe_act<1, 3, 3, 2>(p, c.G, st, act);
-        }
-        if (KH == 7) return NT == 2 ? launch_pipe_act<2, 1, 7, 2>(p, c.G, st, act) : launch_pipe_act<1, 1, 7, 2>(p, c.G, st, act);
-        return NT == 2 ? launch_pipe_act<2, 1, 1, 2>(p, c.G, st, act) : launch_pipe_act<1, 1, 1, 2>(p, c.G, st, act);
+    switch (c.kernel) {
+        case ConvKernel::c16d: return egm_conv_c16d_launch(x, ldx, wf, b, bias_n, y, ldy, stats, N, H, W, dil, s, act);
+        case ConvKernel::wreg: return egm_conv_wreg_launch(x, ldx, wf, b, bias_n, y, ldy, stats, N, H, W, Cin, Cout, c.G, s, act);
+        case ConvKernel::tile:
+            return egm_conv_tile_launch(x, ldx, wf, b, bias_n, y, ldy, stats, N, H, W, Cin, Cout, c.tile_cfg, c.nct, c.G, s, nullptr, 0, 0, act);
+        case ConvKernel::direct:
+            return egm_conv_direct_launch(x, ldx, wf, b, bias_n, y, ldy, stats, N, H, W, Cin, Cout, KH, KW, dil, c.NT, c.nct, c.G, c.smem, s, act);
+        case ConvKernel::pipe:
+            if (KH == 3 && dil == 1) {
+                if (c.R == 4) return launch_pipe_act<1, 3, 3, 4>(p, c.G, st, act);             // tall tiles: Cout <= 32 only (conv_plan)
+                if (c.R == 1) return launch_pipe_act<1, 3, 3, 1>(p, c.G, st, act);
+                return NT == 2 ? launch_pipe_act<2, 3, 3, 2>(p, c.G, st, act) : launch_pipe_act<1, 3, 3, 2>(p, c.G, st, act);
+            }
+            if (KH == 7) return NT == 2 ? launch_pipe_act<2, 1, 7, 2>(p, c.G, st, act) : launch_pipe_act<1, 1, 7, 2>(p, c.G, st, act);
+            return NT == 2 ? launch_pipe_act<2, 1, 1, 2>(p, c.G, st, act) : launch_pipe_act<1, 1, 1, 2>(p, c.G, st, act);
+        case ConvKernel::igemm: break;
     }
     const int ps = (dtype == EGM_BF16) ? Mma<bf16_t>::kPixStride : Mma<float>::kPixStride;
     const bool halo = (dil == 1);
@@ -842,7 +788,6 @@ static int conv_fwd_impl(int dtype, const void* x, int ldx, const void* wf, cons
     const size_t red_bytes = 4 * 2 * NT * 32 * sizeof(float);
     if (smem < red_bytes) smem = red_bytes;
     EGM_REQUIRE(smem <= 160 * 1024, "conv_fwd: LDS budget exceeded (%zu)", smem);
-    hipStream_t st = (hipStream_t)s;
     if (dtype == EGM_BF16) return NT == 2 ? launch_conv_act<bf16_t, 2>(p, smem, st, act) : launch_conv_act<bf16_t, 1>(p, smem, st, act);
     if (dtype == EGM_F32) return NT == 2 ? launch_conv_act<float, 2>(p, smem, st, act) : launch_conv_act<float, 1>(p, smem, st, act);
     EGM_FAIL(EGM_ERR_ARG, "conv_fwd: unknown dtype %d", dtype);

@@ -21,24 +21,16 @@
 //   * the C waves sharing a dW block are summed through LDS; partial blocks go to a slab [split][tap][CoutP][CinP] with plain stores; a second kernel sums the slabs in
 //     fixed order (bitwise reproducible) and scatters into the fp32 OIHW gradient.
 #include "common.h"
+#include "conv_plan.h"
 #include "group.h"
 #include <string.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
-// conv7x7_c16.hip: weight gradient of the 16 -> 16 channel 7x7 conv (transposed 16x16x32 MFMA operands, all taps in one wave)
-int egm_conv_c7_wgrad_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil);
-int egm_conv_c7_wgrad_launch(const void* x, int ldx, const void* dy, int lddy, float* slab, int nslab, int N, int H, int W, egm_stream_t s);
-int egm_conv_c16d_wgrad_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil);
-int egm_conv_c16d_wgrad_launch(const void* x, int ldx, const void* dy, int lddy, float* slab, int nslab, int N, int H, int W, int dil,
-                               egm_stream_t s);
 
 namespace {
 
@@ -83,7 +75,10 @@ struct WgradParams {
     int A, B, C;                 // wave split: couts x cins x pixel rows
     int nci_tiles;               // ceil(Cin / (32*B))
     int ngroups;                 // tap groups
-    int dma;                     // bf16: stage through LDS-DMA into two LDS images (no VGPR staging, one barrier per tile)
+    // bf16: stage through LDS-DMA into two LDS images (no VGPR staging, one barrier per tile).  Always 0: the planner sends every layer
+    // that took this path (9 taps, Cin, Cout > 32; 9 % faster than register staging) to the wave-specialised kernel, which is faster
+    // still.  Field and branch stay because the 3-tap merged kernel spills 20 bytes per lane more when the branch is cut out.
+    int dma;
 };
 
 // ---- epilogue shared by the slab kernels: per wave NTAPS accumulator blocks in the MFMA D layout
@@ -425,8 +420,7 @@ __global__ __launch_bounds__(256, (NTAPS <= 3 && sizeof(T) == 2) ? 2 : 1) void c
 // [blk0[i], blk0[i+1]) = its (nx, ny, nz) grid in x-fastest order
 struct WgradMulti { WgradParams p[EGM_GROUP_MAX]; int blk0[EGM_GROUP_MAX + 1]; int nx[EGM_GROUP_MAX], ny[EGM_GROUP_MAX]; int n; };
 __device__ __forceinline__ int wgrad_multi_member(const WgradMulti& m, int& bx, int& by, int& bz) {
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
+    EGM_GROUP_MEMBER(m, i);
     const int b = (int)blockIdx.x - m.blk0[i];
     bx = b % m.nx[i];
     const int r = b / m.nx[i];
@@ -451,7 +445,7 @@ __global__ __launch_bounds__(256, (NTAPS <= 3 && sizeof(T) == 2) ? 2 : 1) void c
 //   barrier per tile.
 // CC: 1, 2, 4 = the row-rotation consumer loop of the 9-tap layers with C = CC pixel-row waves per (cout, cin) block pair (one
 // instantiation each: a kernel that carries two consumer loops spills, 660-5 000 bytes per lane); 0 = the plain loop, C at run time
-// (5- and 7-tap rows; the 9-tap layers with EGM_WGRAD_ROT=0, for A/B runs)
+// (5- and 7-tap rows)
 // ---- the producers' global loads, written out so that their completion is counted here and not by the compiler (see the body)
 __device__ __forceinline__ u32x4_t ws_rsrc(const void* base, unsigned num_records) {       // raw buffer descriptor, byte offsets
     const unsigned long long a = reinterpret_cast<unsigned long long>(base);
@@ -896,27 +890,33 @@ __global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(const WredEntry
     }
 }
 
-struct WgradPlan { int A, B, C, ntaps, ngroups, nsplit, nco_tiles, nci_tiles, npt, tiles_y, tiles_x, dma, ws, c7; size_t smem; long long slab_bytes; };
+// generic_4w / ws: conv_wgrad_kernel / conv_wgrad_ws_kernel below; c7 / c16d: the 16 -> 16 channel kernels of conv7x7_c16.hip (7x7, dilated
+// 3x3), which have their own slab count and use nothing else of the plan
+enum class WgradKind { generic_4w, ws, c7, c16d };
+struct WgradPlan {
+    WgradKind kind = WgradKind::generic_4w;
+    int A = 1, B = 1, C = 4, ntaps = 0, ngroups = 0, nsplit = 0, nco_tiles = 0, nci_tiles = 0, npt = 0, tiles_y = 0, tiles_x = 0;
+    size_t smem = 0;
+    long long slab_bytes = 0;
+    // a kernel of conv7x7_c16.hip with `ns` slabs
+    static WgradPlan c16(WgradKind k, int ntaps, int ns, long long slab_floats) {
+        WgradPlan pl;
+        pl.kind = k; pl.ntaps = pl.ngroups = ntaps; pl.nsplit = ns; pl.slab_bytes = ns * slab_floats * (long long)sizeof(float);
+        return pl;
+    }
+};
 
 int wgrad_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, WgradPlan* pl) {
     if (KH == 1 && KW == 1) dil = 1;
-    pl->c7 = 0;
-    {
-        // 16 -> 16 channels, 7x7 (conv7x7_c16.hip): its own kernel, its own slab count; nothing else of the plan is used
-        const int ns = egm_conv_c7_wgrad_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil);
-        if (ns > 0) {
-            memset(pl, 0, sizeof(*pl));
-            pl->c7 = 1; pl->ntaps = 7; pl->ngroups = 7; pl->nsplit = ns; pl->A = pl->B = 1; pl->C = 4;
-            pl->slab_bytes = (long long)ns * KH * KW * Cout * Cin * (long long)sizeof(float);
-            return EGM_OK;
-        }
-        const int nd = egm_conv_c16d_wgrad_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil);
-        if (nd > 0) {                                       // 16 -> 16 channels, dilated 3x3: likewise
-            memset(pl, 0, sizeof(*pl));
-            pl->c7 = 2; pl->ntaps = 3; pl->ngroups = 3; pl->nsplit = nd; pl->A = pl->B = 1; pl->C = 4;
-            pl->slab_bytes = (long long)nd * KH * KW * Cout * Cin * (long long)sizeof(float);
-            return EGM_OK;
-        }
+    *pl = WgradPlan();
+    const long long slab_floats = (long long)KH * KW * Cout * Cin;
+    if (const int ns = egm_conv_c7_wgrad_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil); ns > 0) {
+        *pl = WgradPlan::c16(WgradKind::c7, 7, ns, slab_floats);
+        return EGM_OK;
+    }
+    if (const int nd = egm_conv_c16d_wgrad_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil); nd > 0) {
+        *pl = WgradPlan::c16(WgradKind::c16d, 3, nd, slab_floats);
+        return EGM_OK;
     }
     if (dil == 1) {
         if (KH == 3 && KW == 3) { pl->ntaps = 9; pl->ngroups = 1; }
@@ -939,20 +939,15 @@ int wgrad_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW
     pl->nco_tiles = egm_cdiv(Cout, 32 * A); pl->nci_tiles = egm_cdiv(Cin, 32 * B);
     pl->tiles_y = egm_cdiv(H, TH); pl->tiles_x = egm_cdiv(W, TW); pl->npt = N * pl->tiles_y * pl->tiles_x;
     const int blocks_per_split = pl->nco_tiles * pl->nci_tiles * pl->ngroups;
-    // ~one workgroup per CU; the 1- and 3-tap kernels are light on registers and stage-latency bound (a stage is two barriers around
-    // a handful of MFMAs), so they get as many co-resident workgroups per CU as EGM_WGRAD_PER_CU says (default 2)
-    static const int per_cu_small = getenv("EGM_WGRAD_PER_CU") ? atoi(getenv("EGM_WGRAD_PER_CU")) : 2;
-    // bf16: the wave-specialised kernel (8 waves, two image pairs, one workgroup per CU); EGM_WGRAD_WS=0 keeps the 4-wave pipelines
-    static const int ws_on = getenv("EGM_WGRAD_WS") ? atoi(getenv("EGM_WGRAD_WS")) : 1;
-    // (measured, profiles/r02_*: the 5-, 7- and 9-tap layers run 10-20 % faster wave-specialised; the 1- and 3-tap ones are
-    //  stage-latency bound and keep the 4-wave kernel with two workgroups per CU)
+    // bf16, 5-, 7- and 9-tap layers: the wave-specialised kernel (8 waves, two image pairs, one workgroup per CU)
+    // (measured, profiles/r02_*: they run 10-20 % faster wave-specialised; the 1- and 3-tap ones are stage-latency bound and keep
+    //  the 4-wave kernel with two workgroups per CU)
     // (r04, with the reworked producers: the 1-tap layers through this kernel 5-25 % faster launch by launch, 0.00 ms in the step)
-    const bool ws_family = dtype == EGM_BF16 && ws_on && pl->ntaps >= 5;
-    pl->ws = ws_family ? 1 : 0;
-    int per_cu = ws_family ? 1 : ((pl->ntaps <= 3 && dtype == EGM_BF16) ? per_cu_small : 1);
-    // the wave-specialised kernel on the narrow layers (one 32 x 32 block, two 38 KB image pairs): EGM_WGRAD_WS_PER_CU workgroups per CU
-    static const int ws_per_cu = getenv("EGM_WGRAD_WS_PER_CU") ? atoi(getenv("EGM_WGRAD_WS_PER_CU")) : 1;
-    if (ws_family && ws_per_cu > 1 && A * B == 1 && pl->ntaps == 9) per_cu = ws_per_cu;
+    const bool ws = dtype == EGM_BF16 && pl->ntaps >= 5;
+    if (ws) pl->kind = WgradKind::ws;
+    // ~one workgroup per CU; the bf16 1- and 3-tap kernels are light on registers and stage-latency bound (a stage is two barriers
+    // around a handful of MFMAs), so they get two co-resident workgroups per CU
+    const int per_cu = (pl->ntaps <= 3 && dtype == EGM_BF16) ? 2 : 1;
     int nsplit = 256 * per_cu / blocks_per_split;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > pl->npt) nsplit = pl->npt;
@@ -961,128 +956,78 @@ int wgrad_plan(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW
     const int wh = pl->ntaps == 9 ? 3 : 1, ww = pl->ntaps == 9 ? 3 : pl->ntaps;
     const int pw = (dil > 1 && pl->ntaps == 3) ? TW + 2 * dil : TW + ww - 1;
     pl->smem = (size_t)A * TH * TW * rb + (size_t)B * (TH + wh - 1) * pw * rb;
-    // bf16: two LDS images filled by LDS-DMA (tile t+1 streams in while tile t is multiplied) when both fit
-    static const int dma_off = getenv("EGM_WGRAD_NO_DMA") != nullptr;
-    // (measured: 9 % faster on the 2 x 2-block layers, i.e. Cin, Cout > 32; slower on the narrow and the dilated ones, which keep
-    //  the register-staged pipeline)
-    pl->dma = (dtype == EGM_BF16 && !pl->ws && !dma_off && A * B == 4 && pl->ntaps == 9 && 2 * pl->smem <= 156 * 1024) ? 1 : 0;
-    if (pl->ws) pl->smem = (size_t)A * TH * TW * rb + (((size_t)B * (TH + wh - 1) * pw * rb + 4095) & ~(size_t)4095);   // whole producer slots
-    if (pl->dma || pl->ws) pl->smem *= 2;
+    if (ws) pl->smem = 2 * ((size_t)A * TH * TW * rb + (((size_t)B * (TH + wh - 1) * pw * rb + 4095) & ~(size_t)4095));   // two image pairs of whole producer slots
     const size_t red_bytes = pl->C > 1 ? (size_t)A * B * (pl->C - 1) * pl->ntaps * 16 * 64 * sizeof(float) : 0;   // wgrad_reduce_rows' parking area
     if (pl->smem < red_bytes) pl->smem = red_bytes;
     pl->slab_bytes = (long long)nsplit * KH * KW * Cout * Cin * (long long)sizeof(float);
     return EGM_OK;
 }
 
-// group.h: launch recs[0..n) of one instantiation; KERNEL / MULTI = the plain and the merged kernel, THREADS per workgroup
-template <typename Single, typename Multi>
-int launch_wgrad_group_impl(const EgmGroupRec* recs, int n, hipStream_t st, Single single, Multi multi, int threads, const char* what) {
+// Launchers of one instantiation: Single / Multi = its plain and its merged kernel, conv_wgrad_kernel<T, NTAPS> / conv_wgrad_multi_kernel<T, NTAPS>
+// with THREADS = 256 or the conv_wgrad_ws_* pair with 512.
+// group.h: launch recs[0..n); a record carries the member's (nx, ny, nz) grid behind its parameters
+template <auto Single, auto Multi, int THREADS>
+int launch_wgrad_group(const EgmGroupRec* recs, int n, hipStream_t st) {
+    constexpr bool ws = THREADS == 512;
+    if (int rc = egm_allow_max_lds<Multi>(ws ? "conv_wgrad_ws_multi" : "conv_wgrad_multi")) return rc;
+    auto g3 = [](const EgmGroupRec& r) { return reinterpret_cast<const int*>(r.params + sizeof(WgradParams)); };
     if (n == 1) {
         WgradParams first;
         memcpy(&first, recs[0].params, sizeof(WgradParams));
-        const int* g3 = reinterpret_cast<const int*>(recs[0].params + sizeof(WgradParams));
-        hipLaunchKernelGGL(single, dim3(g3[0], g3[1], g3[2]), dim3(threads), recs[0].smem, st, first);
-        EGM_CHECK_LAUNCH(what);
+        hipLaunchKernelGGL(Single, dim3(g3(recs[0])[0], g3(recs[0])[1], g3(recs[0])[2]), dim3(THREADS), recs[0].smem, st, first);
+    } else {
+        WgradMulti m;
+        const size_t smem = egm_group_fill<WgradParams>(m, recs, n, [&](int i, const EgmGroupRec* r) {
+            m.nx[i] = r ? g3(*r)[0] : 1; m.ny[i] = r ? g3(*r)[1] : 1;
+        });
+        hipLaunchKernelGGL(Multi, dim3(m.blk0[n]), dim3(THREADS), smem, st, m);
+    }
+    EGM_CHECK_LAUNCH(ws ? "conv_wgrad_ws (group)" : "conv_wgrad (group)");
+    return EGM_OK;
+}
+// one weight gradient: recorded when a group is open on this thread, launched otherwise
+template <auto Single, auto Multi, int THREADS>
+int launch_wgrad_kernel(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
+    constexpr const char* what = THREADS == 512 ? "conv_wgrad_ws" : "conv_wgrad";
+    if (int rc = egm_allow_max_lds<Single>(what)) return rc;
+    const dim3 grid(pl.nsplit, pl.nco_tiles * pl.nci_tiles, pl.ngroups);
+    if (egm_group_recording()) {
+        static_assert(sizeof(WgradParams) + 3 * sizeof(int) <= sizeof(EgmGroupRec::params), "group record too small");
+        EgmGroupRec r;
+        r.launch = &launch_wgrad_group<Single, Multi, THREADS>;
+        memcpy(r.params, &p, sizeof(WgradParams));
+        const int g3[3] = {(int)grid.x, (int)grid.y, (int)grid.z};
+        memcpy(r.params + sizeof(WgradParams), g3, sizeof(g3));
+        r.G = 0; r.grid = (int)(grid.x * grid.y * grid.z); r.smem = pl.smem;
+        egm_group_push(r);
         return EGM_OK;
     }
-    WgradMulti m;
-    size_t smem = 0;
-    m.n = n; m.blk0[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        memcpy(&m.p[i], recs[i].params, sizeof(WgradParams));
-        const int* g3 = reinterpret_cast<const int*>(recs[i].params + sizeof(WgradParams));
-        m.nx[i] = g3[0]; m.ny[i] = g3[1];
-        m.blk0[i + 1] = m.blk0[i] + g3[0] * g3[1] * g3[2];
-        if (recs[i].smem > smem) smem = recs[i].smem;
-    }
-    for (int i = n; i < EGM_GROUP_MAX; ++i) { m.p[i] = m.p[0]; m.nx[i] = m.ny[i] = 1; m.blk0[i + 1] = m.blk0[n]; }
-    hipLaunchKernelGGL(multi, dim3(m.blk0[n]), dim3(threads), smem, st, m);
+    hipLaunchKernelGGL(Single, grid, dim3(THREADS), pl.smem, st, p);
     EGM_CHECK_LAUNCH(what);
     return EGM_OK;
 }
 template <typename T, int NTAPS>
-int launch_wgrad_group(const EgmGroupRec* recs, int n, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_multi_kernel<T, NTAPS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_wgrad_multi: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
-    return launch_wgrad_group_impl(recs, n, st, conv_wgrad_kernel<T, NTAPS>, conv_wgrad_multi_kernel<T, NTAPS>, 256, "conv_wgrad (group)");
-}
-template <int NTAPS, int CC>
-int launch_wgrad_ws_group(const EgmGroupRec* recs, int n, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_ws_multi_kernel<NTAPS, CC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_wgrad_ws_multi: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
-    return launch_wgrad_group_impl(recs, n, st, conv_wgrad_ws_kernel<NTAPS, CC>, conv_wgrad_ws_multi_kernel<NTAPS, CC>, 512, "conv_wgrad_ws (group)");
-}
-// records the launch when a group is open on this thread
-inline bool wgrad_record(int (*fn)(const EgmGroupRec*, int, hipStream_t), const WgradParams& p, dim3 grid, size_t smem) {
-    if (!egm_group_recording()) return false;
-    static_assert(sizeof(WgradParams) + 3 * sizeof(int) <= sizeof(EgmGroupRec::params), "group record too small");
-    EgmGroupRec r;
-    r.launch = fn;
-    memcpy(r.params, &p, sizeof(WgradParams));
-    const int g3[3] = {(int)grid.x, (int)grid.y, (int)grid.z};
-    memcpy(r.params + sizeof(WgradParams), g3, sizeof(g3));
-    r.G = 0; r.grid = (int)(grid.x * grid.y * grid.z); r.smem = smem;
-    egm_group_push(r);
-    return true;
-}
-template <typename T, int NTAPS>
 int launch_wgrad_4w(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<T, NTAPS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
-    dim3 grid(pl.nsplit, pl.nco_tiles * pl.nci_tiles, pl.ngroups);
-    if (wgrad_record(&launch_wgrad_group<T, NTAPS>, p, grid, pl.smem)) return EGM_OK;
-    hipLaunchKernelGGL((conv_wgrad_kernel<T, NTAPS>), grid, dim3(256), pl.smem, st, p);
-    EGM_CHECK_LAUNCH("conv_wgrad");
-    return EGM_OK;
+    return launch_wgrad_kernel<conv_wgrad_kernel<T, NTAPS>, conv_wgrad_multi_kernel<T, NTAPS>, 256>(p, pl, st);
 }
 template <int NTAPS, int CC>
-int launch_wgrad_ws_rot(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_ws_kernel<NTAPS, CC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "conv_wgrad_ws: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
-    dim3 grid(pl.nsplit, pl.nco_tiles * pl.nci_tiles, pl.ngroups);
-    if (wgrad_record(&launch_wgrad_ws_group<NTAPS, CC>, p, grid, pl.smem)) return EGM_OK;
-    hipLaunchKernelGGL((conv_wgrad_ws_kernel<NTAPS, CC>), grid, dim3(512), pl.smem, st, p);
-    EGM_CHECK_LAUNCH("conv_wgrad_ws");
-    return EGM_OK;
-}
-template <int NTAPS>
 int launch_wgrad_ws(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
-    if constexpr (NTAPS == 9) {
-        static const bool rot_on = getenv("EGM_WGRAD_ROT") ? atoi(getenv("EGM_WGRAD_ROT")) != 0 : true;
-        if (rot_on) {
-            if (pl.C == 1) return launch_wgrad_ws_rot<NTAPS, 1>(p, pl, st);
-            if (pl.C == 2) return launch_wgrad_ws_rot<NTAPS, 2>(p, pl, st);
-            return launch_wgrad_ws_rot<NTAPS, 4>(p, pl, st);
-        }
-    }
-    return launch_wgrad_ws_rot<NTAPS, 0>(p, pl, st);
+    return launch_wgrad_kernel<conv_wgrad_ws_kernel<NTAPS, CC>, conv_wgrad_ws_multi_kernel<NTAPS, CC>, 512>(p, pl, st);
 }
+// bf16 with 5, 7 or 9 taps is WgradKind::ws (wgrad_plan), everything else generic_4w; the 9-tap layers take the row-rotation consumer
+// loop of their C (ws_cc names the instantiation for egm_conv_wgrad_kernel_name too)
+int ws_cc(const WgradPlan& pl) { return pl.ntaps == 9 ? pl.C : 0; }
 template <typename T, int NTAPS>
 int launch_wgrad(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
-    if constexpr (sizeof(T) == 2 && NTAPS >= 5) {
-        if (pl.ws) return launch_wgrad_ws<NTAPS>(p, pl, st);
+    if constexpr (sizeof(T) == 2 && NTAPS == 9) {
+        if (pl.C == 1) return launch_wgrad_ws<NTAPS, 1>(p, pl, st);
+        if (pl.C == 2) return launch_wgrad_ws<NTAPS, 2>(p, pl, st);
+        return launch_wgrad_ws<NTAPS, 4>(p, pl, st);
+    } else if constexpr (sizeof(T) == 2 && NTAPS >= 5) {
+        return launch_wgrad_ws<NTAPS, 0>(p, pl, st);
+    } else {
+        return launch_wgrad_4w<T, NTAPS>(p, pl, st);
     }
-    return launch_wgrad_4w<T, NTAPS>(p, pl, st);
 }
 
 template <typename T>
@@ -1119,12 +1064,12 @@ extern "C" int egm_conv_wgrad_kernel_name(int dtype, int N, int H, int W, int Ci
     if (KH == 1 && KW == 1) dil = 1;
     if (wgrad_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil, &pl) != EGM_OK) return -1;
     char tmp[96];
-    static const bool rot_on = getenv("EGM_WGRAD_ROT") ? atoi(getenv("EGM_WGRAD_ROT")) != 0 : true;
-    if (pl.c7) snprintf(tmp, sizeof(tmp), pl.c7 == 1 ? "conv7x7_c16_wgrad_kernel" : "conv3x3d_c16_wgrad_kernel");
-    else if (dtype == EGM_BF16 && pl.ws)
-        snprintf(tmp, sizeof(tmp), "conv_wgrad_ws_kernel<%d, %d>", pl.ntaps, (pl.ntaps == 9 && rot_on) ? pl.C : 0);
-    else
-        snprintf(tmp, sizeof(tmp), "conv_wgrad_kernel<%s, %d>", dtype == EGM_BF16 ? "bf16_t" : "float", pl.ntaps);
+    switch (pl.kind) {
+        case WgradKind::c7: snprintf(tmp, sizeof(tmp), "conv7x7_c16_wgrad_kernel"); break;
+        case WgradKind::c16d: snprintf(tmp, sizeof(tmp), "conv3x3d_c16_wgrad_kernel"); break;
+        case WgradKind::ws: snprintf(tmp, sizeof(tmp), "conv_wgrad_ws_kernel<%d, %d>", pl.ntaps, ws_cc(pl)); break;
+        case WgradKind::generic_4w: snprintf(tmp, sizeof(tmp), "conv_wgrad_kernel<%s, %d>", dtype == EGM_BF16 ? "bf16_t" : "float", pl.ntaps); break;
+    }
     const int n = (int)strlen(tmp);
     if (buf != nullptr && buflen > 0) { strncpy(buf, tmp, (size_t)buflen - 1); buf[buflen - 1] = 0; }
     return n;
@@ -1164,17 +1109,20 @@ extern "C" int egm_conv_wgrad(int dtype, const void* x, int ldx, const void* dy,
     p.x = x; p.dy = dy; p.slab = (float*)workspace; p.ldx = ldx; p.lddy = lddy; p.N = N; p.H = H; p.W = W;
     p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.dil = dil; p.tiles_y = pl.tiles_y; p.tiles_x = pl.tiles_x;
     p.npt = pl.npt; p.nsplit = pl.nsplit; p.A = pl.A; p.B = pl.B; p.C = pl.C; p.nci_tiles = pl.nci_tiles; p.ngroups = pl.ngroups;
-    p.dma = pl.dma;
+    p.dma = 0;
     hipStream_t st = (hipStream_t)s;
     int rc;
     // inside a launch group only the slab-only form is recorded: with dw the reduction below needs the slabs at once
     const bool paused = dw != nullptr && egm_group_recording();
     if (paused) egm_group_set_recording(false);
-    if (pl.c7 == 1) rc = egm_conv_c7_wgrad_launch(x, ldx, dy, lddy, (float*)workspace, pl.nsplit, N, H, W, s);
-    else if (pl.c7 == 2) rc = egm_conv_c16d_wgrad_launch(x, ldx, dy, lddy, (float*)workspace, pl.nsplit, N, H, W, dil, s);
-    else if (dtype == EGM_BF16) rc = dispatch_wgrad<bf16_t>(p, pl, st);
-    else if (dtype == EGM_F32) rc = dispatch_wgrad<float>(p, pl, st);
-    else rc = EGM_ERR_ARG;
+    switch (pl.kind) {
+        case WgradKind::c7: rc = egm_conv_c7_wgrad_launch(x, ldx, dy, lddy, (float*)workspace, pl.nsplit, N, H, W, s); break;
+        case WgradKind::c16d: rc = egm_conv_c16d_wgrad_launch(x, ldx, dy, lddy, (float*)workspace, pl.nsplit, N, H, W, dil, s); break;
+        default:                                         // generic_4w / ws: launch_wgrad<T, NTAPS> picks between them
+            if (dtype == EGM_BF16) rc = dispatch_wgrad<bf16_t>(p, pl, st);
+            else if (dtype == EGM_F32) rc = dispatch_wgrad<float>(p, pl, st);
+            else rc = EGM_ERR_ARG;
+    }
     if (paused) egm_group_set_recording(true);
     if (rc == EGM_ERR_ARG && dtype != EGM_BF16 && dtype != EGM_F32) EGM_FAIL(EGM_ERR_ARG, "conv_wgrad: unknown dtype %d", dtype);
     if (rc != EGM_OK) return rc;

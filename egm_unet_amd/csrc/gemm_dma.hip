@@ -19,12 +19,10 @@
 //   * XCD-aware tile order: the workgroups of one XCD walk the m-tiles congruent to the XCD index, n fastest, so an A row panel is read
 //     from HBM by one XCD and shared by the n-tiles through its L2.
 #include "gemm_dma.h"
-#include <stdlib.h>
+#include "lds_dma.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
 __device__ uint4 egm_gemm_zero_page[4];
 #ifdef EGM_GEMM_TIMING
@@ -59,16 +57,6 @@ __device__ __forceinline__ float act_of(float v) {                     // gemm_a
     if (ACT == 1) return v > 0.f ? v : 0.f;
     if (ACT == 2) return v * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.4554669595930157f * v));   // QuickGELU, bf16 output: gemm_act(fast)
     return v;
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-    f32x2_t v; v.x = lo; v.y = hi;
-    const bf16x2_t b = __builtin_convertvector(v, bf16x2_t);
-    return *reinterpret_cast<const uint32_t*>(&b);
-}
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr));
 }
 
 template <int NT, bool HAS_R, int ACT, int NW>
@@ -246,7 +234,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void gemm_dma_kernel(Para
                     v[6] += __uint_as_float(r4.w << 16); v[7] += __uint_as_float(r4.w & 0xffff0000u);
                 }
                 uint4 o;
-                o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]); o.z = pack2(v[4], v[5]); o.w = pack2(v[6], v[7]);
+                o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]); o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
                 const int mr = mb + it2 * 8;
                 if (mr < p.M && n < p.N && nin) *reinterpret_cast<uint4*>(p.C + (long long)mr * p.ldc + n) = o;
             }
@@ -317,7 +305,7 @@ int g_gemm_dma = -1;
 }  // namespace
 
 extern "C" int egm_gemm_dma_mode(int mode) {
-    if (g_gemm_dma < 0) g_gemm_dma = getenv("EGM_GEMM_DMA") ? atoi(getenv("EGM_GEMM_DMA")) : 1;
+    if (g_gemm_dma < 0) g_gemm_dma = egm_env_int("EGM_GEMM_DMA", 1);
     const int old = g_gemm_dma;
     if (mode >= 0) g_gemm_dma = mode;
     return old;
@@ -362,14 +350,8 @@ GemmDmaPlan egm_gemm_dma_plan(const GemmDmaArgs& a) {
 
 template <int NT, bool HAS_R, int ACT, int NW>
 static int launch_dma(const Params& p, int grid, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_kernel<NT, HAS_R, ACT, NW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (Geom<NT, NW>::SMEM));
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "gemm_dma: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
     constexpr int smem_bytes = Geom<NT, NW>::SMEM;
+    if (int rc = egm_allow_max_lds<gemm_dma_kernel<NT, HAS_R, ACT, NW>>("gemm_dma", smem_bytes)) return rc;
     hipLaunchKernelGGL((gemm_dma_kernel<NT, HAS_R, ACT, NW>), dim3(grid), dim3(64 * NW), smem_bytes, st, p);
     EGM_CHECK_LAUNCH("gemm_dma");
     return EGM_OK;

@@ -798,12 +798,7 @@ extern "C" int egm_mca_gates_bwd(const float* dG, const float* stats, const floa
     EGM_REQ_SHAPE("mca_gates_bwd");
     const size_t lds = (size_t)4 * N * (H + W + C) * sizeof(float);
     if (lds <= 140 * 1024) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mca_gates_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-            if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "mca_gates_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr_done = true;
-        }
+        if (int rc = egm_allow_max_lds<mca_gates_bwd_kernel<true>>("mca_gates_bwd", 140 * 1024)) return rc;
         hipLaunchKernelGGL(mca_gates_bwd_kernel<true>, dim3(1), dim3(1024), lds, (hipStream_t)s, dG, stats, o, gates, gp, dz_scratch, coef, dwts, dks, N,
                            H, W, C);
     } else {
@@ -845,13 +840,7 @@ template <typename T>
 static int launch_mca_fused(const void* x, int ldx, const float* gates, void* xo, int ldxo, void* out, int ldo, unsigned char* codes, int N, int H,
                             int W, int C, float inv, hipStream_t st) {
     const size_t smem = (size_t)(MF_PY * MF_PX + MF_UY * MF_UX) * MF_CB * sizeof(T);
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mca_fused_fwd_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)smem);
-        if (e != hipSuccess) EGM_FAIL(EGM_ERR_LAUNCH, "mca_fused_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done = true;
-    }
+    if (int rc = egm_allow_max_lds<mca_fused_fwd_kernel<T>>("mca_fused_fwd", (int)smem)) return rc;
     const int tiles_x = (W + MF_TX - 1) / MF_TX, tiles_y = (H + MF_TY - 1) / MF_TY, nchunk = (C + MF_CB - 1) / MF_CB;
     const long long grid = (long long)N * tiles_x * tiles_y * nchunk;
     EGM_REQUIRE(grid < (1LL << 31), "mca_fused_fwd: grid too large");

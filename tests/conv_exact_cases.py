@@ -365,6 +365,75 @@ def wgrad_split(L, c):
     return slabs, c.N * ((c.H + 7) // 8) * ((c.W + 31) // 32)
 
 
+# ---- the planner table (tests/golden/conv_planner.json.gz, written by tools/conv_planner_table.py) ------------------------------
+# A row key is (dtype code, N, H, W, Cin, Cout, k, dil) with PADDED channel counts.  Its record is one tuple per setting that can
+# change the answer -- (tile mode, c7 mode): tile modes 0 / 5 / 7 for the bf16 3x3 convs at dilation 1, c7 modes 0 / 1 for bf16
+# 16 -> 16 channels, (5, 1) alone otherwise -- holding, in this order: the two modes; kernel name and statistics tiles of the forward
+# call and of the data gradient (Cin / Cout swapped); egm_conv_split_ok at the 8-aligned split nearest the middle; the same four
+# forward answers inside an open launch group; weight-gradient kernel name, slab count and workspace bytes.
+def planner_settings(key):
+    dt, _, _, _, Cin, Cout, k, dil = key
+    tiles = (0, 5, 7) if (dt == 1 and k == 3 and dil == 1) else (5,)
+    c7s = (0, 1) if (dt == 1 and Cin == 16 and Cout == 16) else (1,)
+    return [(t, c) for t in tiles for c in c7s]
+
+
+def planner_record(L, key):
+    """The planner's answers for a row key under every setting of planner_settings(key); touches no device."""
+    import ctypes
+    dt, N, H, W, Cin, Cout, k, dil = key
+    buf = ctypes.create_string_buffer(96)
+
+    def name(fn, ci, co):
+        n = getattr(L.cdll, fn)(dt, N, H, W, ci, co, k, k, dil, ctypes.cast(buf, ctypes.c_void_p), 96)
+        return buf.value.decode() if n >= 0 else ""
+
+    def fwd4():
+        return [name("egm_conv_kernel_name", Cin, Cout), L.cdll.egm_conv_stats_tiles(dt, N, H, W, Cin, Cout, k, k, dil),
+                name("egm_conv_kernel_name", Cout, Cin), L.cdll.egm_conv_stats_tiles(dt, N, H, W, Cout, Cin, k, k, dil)]
+
+    out = []
+    old_t, old_c = L.cdll.egm_conv_tile_mode(-1), L.cdll.egm_conv_c7_mode(-1)
+    try:
+        for t, c in planner_settings(key):
+            L.cdll.egm_conv_tile_mode(t)
+            L.cdll.egm_conv_c7_mode(c)
+            rec = [t, c] + fwd4() + [L.cdll.egm_conv_split_ok(dt, N, H, W, Cin, Cout, k, k, dil, Cout // 16 * 8)]
+            L.call("egm_group_begin")
+            try:
+                rec += fwd4()
+            finally:
+                L.call("egm_group_abort")
+            rec += [name("egm_conv_wgrad_kernel_name", Cin, Cout), L.cdll.egm_conv_wgrad_slabs(dt, N, H, W, Cin, Cout, k, k, dil),
+                    L.cdll.egm_conv_wgrad_workspace(N, H, W, Cin, Cout, k, k)]
+            out.append(rec)
+    finally:
+        L.cdll.egm_conv_tile_mode(old_t)
+        L.cdll.egm_conv_c7_mode(old_c)
+    return out
+
+
+def planner_case_keys():
+    """Row keys of every shape in the tables above (the product grid and the training step's shapes are the generator's)."""
+    cases = FWD_CASES + GROUP_LAUNCH + WGRAD_CASES + [c1_case(s) for s in C1_SHAPES + C1_MULTI]
+    return sorted({(0 if c.dtype == "f32" else 1, c.N, c.H, c.W, pad8(c.Cin), pad8(c.Cout), c.k, c.dil) for c in cases})
+
+
+def load_planner_table(path):
+    """-> (parent commit, {key: record}) of the stored table; kernel names are stored once and referred to by index."""
+    import gzip
+    import json
+    with gzip.open(path, "rt") as f:
+        doc = json.load(f)
+    names = doc["names"]
+    pos = [2, 4, 7, 9, 11]                                     # the name fields of a setting's record
+
+    def expand(rec):
+        return [names[v] if i in pos else v for i, v in enumerate(rec)]
+
+    return doc["parent"], {tuple(r[:8]): [expand(rec) for rec in r[8]] for r in doc["rows"]}
+
+
 # ---- what the exact comparison reports ----------------------------------------------------------------------------------------
 def mismatch_report(got_nhwc, want_nhwc, th=8, tw=32):
     """'' when equal; else the count of wrong elements, the first few (n, h, w, c) with got / want, and whether they sit on the last

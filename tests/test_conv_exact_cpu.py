@@ -107,6 +107,23 @@ def test_planner_gives_every_case_the_kernel_it_is_listed_under(planner):
     assert L.cdll.egm_conv_split_ok(1, *X.SPLIT_SHAPE[:3], 32, 64, 3, 3, 1, X.SPLIT_AT)
 
 
+def test_planner_answers_equal_the_recorded_table(planner):
+    """Every planner query (kernel names, statistics tiles, split support, weight-gradient slabs and workspace; as called, with the
+    channel counts swapped, under the tile / c7 modes and inside an open launch group) equals what the commit named in
+    tests/golden/conv_planner.json.gz answered, row by row: the tables above, the conv shapes of the benchmarked training step and a
+    product grid (tools/conv_planner_table.py)."""
+    import os
+    parent, table = X.load_planner_table(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_planner.json.gz"))
+    assert len(parent) == 40 and len(table) > 5000
+    assert set(X.planner_case_keys()) <= set(table), "a case table has a shape the planner table lacks: regenerate it from a known-good commit"
+    wrong = []
+    for key, want in table.items():
+        assert [r[:2] for r in want] == [list(s) for s in X.planner_settings(key)], key
+        got = X.planner_record(planner, key)
+        wrong += [(key, g, w) for g, w in zip(got, want) if g != w]
+    assert not wrong, f"{len(wrong)} of {sum(len(v) for v in table.values())} records differ from commit {parent[:12]}; first: {wrong[:3]}"
+
+
 def test_build_raises_when_the_bound_fails(monkeypatch):
     """build() on a case whose sums leave the range: 512 -> 512 channels with EVERY weight nonzero (density forced to 1) has sums of
     standard deviation sqrt(2.5 * 4608) ~ 107 over 150 000 outputs."""
