@@ -238,12 +238,19 @@ class ThresholdSweep:
         return sweep_report(self.hist(), self.thresholds)
 
 
-def evaluate_clipseg(model, batches, sweep=None):
+def _with_rank(report, rank):
+    if rank is not None:
+        report["rank"] = rank.report()
+    return report
+
+
+def evaluate_clipseg(model, batches, sweep=None, rank=None):
     """The sweep of a CLIPSeg model (CLIPDensePredT, CLIPDenseBaseline) over batches of (images, conditionals, target), in eval mode
     under no_grad; the model's training flag is put back.  target [B, 1, H, W]: conditionals is what forward takes for the B images
     (one per image) and the B maps model(images, conditionals)[0] are scored; target [B, K, H, W], K >= 2: conditionals is what
     forward_multi takes for K prompts and the B K maps of model.forward_multi(images, conditionals) are scored, sample b K + k against
-    target[b, k].  Targets as for sweep_counts.  -> sweep_report's report (sweep: a ThresholdSweep to add to; default a fresh one)."""
+    target[b, k].  Targets as for sweep_counts.  -> sweep_report's report (sweep: a ThresholdSweep to add to; default a fresh one).
+    rank: a rank.RankScores; every batch is added to it as well and the report gains report["rank"] = rank.report()."""
     sweep = ThresholdSweep() if sweep is None else sweep
     was_training = model.training
     model.eval()
@@ -257,19 +264,24 @@ def evaluate_clipseg(model, batches, sweep=None):
                     raise ValueError(f"evaluate_clipseg: logits {tuple(out.shape)} and target {tuple(target.shape)} differ")
                 H, W = out.shape[-2:]
                 sweep.add(out.reshape(-1, H, W), target.to(out.device).reshape(-1, H, W))
+                if rank is not None:
+                    rank.add(out.reshape(-1, H, W), target.to(out.device).reshape(-1, H, W))
     finally:
         model.train(was_training)
-    return sweep.report()
+    return _with_rank(sweep.report(), rank)
 
 
-def evaluate_binary(predictor, data_loader, device, c_pos=1, c_neg=0, sweep=None):
+def evaluate_binary(predictor, data_loader, device, c_pos=1, c_neg=0, sweep=None, rank=None):
     """infer.evaluate's loop for the sweep of one class against another: predictor is an infer.Predictor, tiled.TiledPredictor or
     tta.TTAPredictor; every batch's score is out[:, c_pos] - out[:, c_neg] of predictor(image)["out"], scored against the loader's
-    targets with class c_pos positive, class c_neg negative and every other value (255 = ignore) dropped.  -> the report."""
+    targets with class c_pos positive, class c_neg negative and every other value (255 = ignore) dropped.  -> the report.  rank: as
+    for evaluate_clipseg."""
     sweep = ThresholdSweep() if sweep is None else sweep
     with torch.no_grad():
         for image, target in data_loader:
             image, target = image.to(device), target.to(device)
             out = predictor(image)["out"]                      # consumed on the stream before the next replay overwrites it
             sweep.add(out, target, channels=(c_pos, c_neg), target_values=(c_neg, c_pos))
-    return sweep.report()
+            if rank is not None:
+                rank.add(out, target, channels=(c_pos, c_neg), target_values=(c_neg, c_pos))
+    return _with_rank(sweep.report(), rank)

@@ -1185,6 +1185,35 @@ int egm_lovasz_hinge_fwd(const float* logits, const void* target, int target_f32
 int egm_lovasz_hinge_bwd(const float* coef, int N, int C, int c_pos, int c_neg, int H, int W, int per_image, const float* grad_out,
                          const float* w_dev, float* dlogits, egm_stream_t s);
 
+/* ---- Exact ranking scores of binary logits (csrc/rank.hip, egm_unet_amd/rank.py)
+ * Step-wise average precision with one threshold per distinct score, the exact AUROC numerator and the best foreground IoU over every
+ * distinct score, of S segments (an evaluation set, or one image each) of L elements.
+ * egm_rank_keys: scores, target, target_f32 and target_cls exactly as for egm_sweep_hist (C == 1 or the fp32 difference of two
+ *   channels; uint8 through target_cls or fp32 cut at 0.5; odd HW, samples at any 4-byte offset); 1 <= N <= 65535, 1 <= HW < 2^31.
+ *   With s' = the score, NaN replaced by -inf and -0 by +0, and b its bits: key = b where s' is negative, ~b & 0x7FFFFFFF otherwise
+ *   (the complement of the order-preserving map), so ascending keys are descending scores, equal keys are scores that compare equal in
+ *   fp32, and every kept key is <= 0xFF800000; a dropped pixel gets key 0xFFFFFFFF.  val = positive | kept << 1.  keys, vals: uint32,
+ *   element (n, i) written at [offset + n HW + i] (offset >= 0: a batch's place in a larger plane).  One launch.
+ * egm_rank_scores: keys, vals uint32 [S][L] as egm_rank_keys makes them (a kept element's key below every dropped one's).  Their
+ *   stable sort over all 32 key bits; along the sorted order of a segment F_j = the inclusive count of positives, V_j = j + 1 (kept
+ *   elements come first); an element is a group end when it is kept and its successor is missing, not kept or has another key.  Over
+ *   the group ends g = 1..Gd in order, with TP_g = F, FP_g = V - F there and TP_0 = FP_0 = 0, P and Nn the kept positives / negatives:
+ *     ap_sum = sum_g (TP_g - TP_{g-1}) TP_g / (TP_g + FP_g) in double (one partial per workgroup, summed in a fixed order);
+ *     auc2 = sum_g (FP_g - FP_{g-1}) (TP_{g-1} + TP_g), exact uint64 (AUROC = auc2 / (2 P Nn));
+ *     best = the g maximising TP_g / (P + FP_g), compared exactly by uint64 cross-multiplication, the first (highest score) on a tie.
+ *   out_u64 [S][8] = {P, Nn, Gd, auc2, best_tp, best_fp, best_key, 0} (best_* all 0 when P == 0), out_f64 [S] = ap_sum / P (0 when
+ *   P == 0).  A segment with nothing kept gives zeros.  skeys_out, tp_out: uint32 [S][L] or NULL: the sorted keys and F_j of every
+ *   element (stage outputs for tests).  workspace: egm_rank_workspace(S, L) bytes, 16-byte aligned (about 16 bytes per element).
+ *   4 * 3 + 4 launches whatever S, L and the content: the sort, then tile counts, a scan per segment, apply, finalize.
+ * Nothing waits for the device or for another workgroup; no atomics on global memory; capturable on one stream.  1 <= S <= 65535,
+ * 1 <= L < 2^31.  A null pointer (other than skeys_out, tp_out), a bad shape, equal or out-of-range channels (C >= 2), a negative offset
+ * or a misaligned workspace: EGM_ERR_ARG with a message before any launch. */
+int egm_rank_keys(const float* scores, int N, int C, int c_pos, int c_neg, long long HW, const void* target, int target_f32,
+                  const unsigned char* target_cls, unsigned int* keys, unsigned int* vals, long long offset, egm_stream_t s);
+long long egm_rank_workspace(int S, long long L);
+int egm_rank_scores(const unsigned int* keys, const unsigned int* vals, int S, long long L, void* workspace, unsigned long long* out_u64,
+                    double* out_f64, unsigned int* skeys_out, unsigned int* tp_out, egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
