@@ -7,6 +7,7 @@
 // One lane = 8 channels of one pixel (16 B bf16 / 32 B fp32); per-pixel cross-channel sums use lane shuffles inside the
 // group of lanes that shares a pixel; per-channel sums over pixels are two-stage with plain stores (deterministic).
 #include "common.h"
+#include "derived_pack.h"
 
 namespace {
 
@@ -736,20 +737,13 @@ __global__ __launch_bounds__(256) void rows_dup_kernel(const float* __restrict__
 
 // fold2 / merge357 with the operand packs of the derived weight written by the same launch (layouts of egm_conv_pack: wf [tap][CoutP][CinP],
 // wd [tap flipped][CinP][CoutP], zeros in the padding): the derived weights of FusionConv are rebuilt every step, and as separate
-// launches (derive, then pack) they were four tiny kernels per block in front of its two convolutions.
+// launches (derive, then pack) they were four tiny kernels per block in front of its two convolutions.  The per-element expressions
+// live in derived_pack.h, which the model-wide prepack (egm_conv_pack_multi) shares.
 template <typename T>
 __global__ void fold2_pack_kernel(const float* __restrict__ w, float* __restrict__ out, T* __restrict__ wf, T* __restrict__ wd, int rows, int K,
                                   int CoutP, int CinP) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < CoutP * CinP; i += gridDim.x * blockDim.x) {
-        const int co = i / CinP, ci = i - co * CinP;
-        float v = 0.f;
-        if (co < rows && ci < K) {
-            v = w[(long long)co * 2 * K + ci] + w[(long long)co * 2 * K + K + ci];
-            out[co * K + ci] = v;
-        }
-        wf[i] = from_f32<T>(v);
-        wd[(long long)ci * CoutP + co] = from_f32<T>(v);
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < CoutP * CinP; i += gridDim.x * blockDim.x)
+        fold2_pack_elem<T>(i, w, out, wf, wd, rows, K, CoutP, CinP);
 }
 template <typename T>
 __global__ void merge357_pack_kernel(const float* __restrict__ w3, const float* __restrict__ w5, const float* __restrict__ w7,
@@ -757,20 +751,8 @@ __global__ void merge357_pack_kernel(const float* __restrict__ w3, const float* 
                                      float* __restrict__ w, float* __restrict__ b, T* __restrict__ wf, T* __restrict__ wd, int Co, int Ci,
                                      int CoutP, int CinP) {
     const int total = 49 * CoutP * CinP;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int ci = i % CinP, co = (i / CinP) % CoutP, t = i / (CinP * CoutP), r = t / 7, sx = t % 7;
-        float v = 0.f;
-        if (co < Co && ci < Ci) {
-            const int oc = co * Ci + ci;
-            v = w7[oc * 49 + t];
-            if (r >= 1 && r <= 5 && sx >= 1 && sx <= 5) v += w5[oc * 25 + (r - 1) * 5 + (sx - 1)];
-            if (r >= 2 && r <= 4 && sx >= 2 && sx <= 4) v += w3[oc * 9 + (r - 2) * 3 + (sx - 2)];
-            w[oc * 49 + t] = v;
-        }
-        wf[i] = from_f32<T>(v);
-        wd[((long long)(48 - t) * CinP + ci) * CoutP + co] = from_f32<T>(v);
-        if (i < Co) b[i] = b3[i] + b5[i] + b7[i];
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
+        merge357_pack_elem<T>(i, w3, w5, w7, b3, b5, b7, w, b, wf, wd, Co, Ci, CoutP, CinP);
 }
 
 }  // namespace

@@ -26,6 +26,7 @@
 #include "conv_plan.h"
 #include "group.h"
 #include "bn_elem.h"
+#include "derived_pack.h"
 #include <string.h>
 #include <stdio.h>
 
@@ -508,7 +509,14 @@ __global__ void conv_pack_kernel(const float* __restrict__ w, T* __restrict__ wf
 
 
 // all convolution weights of a model in ONE launch: table of descriptors, block -> (conv, chunk) by a scan of the chunk counts
-struct PackEntry { const float* w; void* wf; void* wd; int Cout, Cin, CoutP, CinP, KH, KW, groups, chunk0; };
+// kind 0: w is the OIHW parameter itself.  The derived FusionConv weights are built from their real parameters on the way
+// (derived_pack.h), the fp32 derived weight `out` (and the summed bias `bout`) written next to the packs:
+// kind 1 (fold2): w = the real [Cout][2*Cin] 1x1 weight;  kind 2 (merge357): w / w5 / w3 = the 7x7 / 5x5 / 3x3 weights, b7 / b5 / b3 their biases.
+struct PackEntry {
+    const float* w; void* wf; void* wd; const float* w5; const float* w3; const float* b7; const float* b5; const float* b3; float* out; float* bout;
+    int Cout, Cin, CoutP, CinP, KH, KW, groups, chunk0, kind, pad;
+};
+static_assert(sizeof(PackEntry) == 120, "egm_conv_pack_multi entry layout");
 constexpr int kPackChunk = 1024;
 template <typename T>
 __global__ __launch_bounds__(256) void conv_pack_multi_kernel(const PackEntry* __restrict__ tab, int n) {
@@ -522,6 +530,11 @@ __global__ __launch_bounds__(256) void conv_pack_multi_kernel(const PackEntry* _
     for (int k = 0; k < kPackChunk / 256; ++k) {
         const long long i = (long long)s_c * kPackChunk + k * 256 + threadIdx.x;
         if (i >= total) break;
+        if (e.kind == 1) { fold2_pack_elem<T>((int)i, e.w, e.out, wf, wd, e.Cout, e.Cin, e.CoutP, e.CinP); continue; }
+        if (e.kind == 2) {
+            merge357_pack_elem<T>((int)i, e.w3, e.w5, e.w, e.b3, e.b5, e.b7, e.out, e.bout, wf, wd, e.Cout, e.Cin, e.CoutP, e.CinP);
+            continue;
+        }
         const int ci = (int)(i % e.CinP), co = (int)((i / e.CinP) % e.CoutP), tap = (int)(i / ((long long)e.CinP * e.CoutP));
         float v = 0.f;
         if (co < e.Cout && ci < e.Cin && (co / cout_g) == (ci / cin_g)) {

@@ -842,12 +842,45 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_wide_kernel(const float* __
     }
 }
 
-// deferred reduction of MANY convolutions' slabs in one launch (end of backward): block -> (conv, 64-element chunk)
-struct WredEntry { const float* slab; float* dw; int nslab, taps, CoutP, CinP, CoutR, CinR, groups, accumulate, chunk0, pad; };
+// which of the two kernels above reduces one convolution's slabs (egm_wgrad_reduce): the wide one for many slabs of a small gradient
+static inline bool wgrad_reduce_wide(int nslab, long long total) { return nslab >= 256 && (total + 63) / 64 < 1024; }
+
+// deferred reduction of MANY convolutions' slabs in one launch (end of backward): block -> (conv, chunk of packed elements)
+// mode & 3 says where a reduced element goes:
+//   kWredPlain     dw = the fp32 OIHW gradient (real, possibly grouped, shape), as wgrad_reduce_kernel
+//   kWredFold2     a 1x1 gradient [CoutR][CinR] of a weight derived by fold2: written to dw[co][ci] and dw[co][CinR + ci] of the real
+//                  [CoutR][2*CinR] parameter (fold2_bwd_kernel's scatter)
+//   kWredMerge357  the 7x7 gradient of a weight derived by merge357: (co, ci, tap) to dw (the 7x7 parameter), and where the tap lies in
+//                  the centre 5x5 / 3x3 window to dw2 / dw3 (merge357_bwd_kernel's index maps); a NULL destination is skipped
+// mode & kWredWide: the summation order of wgrad_reduce_wide_kernel (16 slab lanes, balanced tree) instead of wgrad_reduce_kernel's,
+// for the layers whose stand-alone reduction is the wide kernel; such an entry takes chunks of kWredElemsWide elements.
+struct WredEntry { const float* slab; float* dw; float* dw2; float* dw3; int nslab, taps, CoutP, CinP, CoutR, CinR, groups, accumulate, chunk0, mode; };
+static_assert(sizeof(WredEntry) == 72, "egm_wgrad_reduce_multi entry layout");
+enum { kWredPlain = 0, kWredFold2 = 1, kWredMerge357 = 2, kWredWide = 4 };
 // block = kWredElems consecutive packed elements of one conv: 64 float4 columns x 4 slab lanes, two slabs per lane in flight.  (One
 // float per lane left 8 KiB in flight per CU: 1 GB of slabs per step read at 2.6 TB/s.)  Summation order per element is fixed:
-// lane sl adds slabs sl, sl+4, ... in order, the four lanes are combined as (0+1)+(2+3).
-constexpr int kWredElems = 256;
+// lane sl adds slabs sl, sl+4, ... in order, the four lanes are combined as (0+1)+(2+3).  Wide entries: 16 float4 columns x 16 slab
+// lanes, lane sl adds slabs sl, sl+16, ..., the lanes are combined by the balanced tree of wgrad_reduce_wide_kernel.
+constexpr int kWredElems = 256, kWredElemsWide = 64;
+__device__ __forceinline__ void wred_store(const WredEntry& w, long long i, float v, int cin_g, int cout_g) {
+    const int ci = (int)(i % w.CinP), co = (int)((i / w.CinP) % w.CoutP), tap = (int)(i / ((long long)w.CinP * w.CoutP));
+    if (!(co < w.CoutR && ci < w.CinR && (co / cout_g) == (ci / cin_g))) return;
+    const int dst = w.mode & 3;
+    if (dst == kWredPlain) {
+        const long long o = ((long long)co * cin_g + (ci % cin_g)) * w.taps + tap;
+        w.dw[o] = w.accumulate ? w.dw[o] + v : v;
+    } else if (dst == kWredFold2) {
+        float* row = w.dw + (long long)co * 2 * w.CinR;
+        row[ci] = v; row[w.CinR + ci] = v;
+    } else {
+        const long long oc = (long long)co * w.CinR + ci;
+        const int r = tap / 7, sx = tap % 7;
+        if (w.dw != nullptr) w.dw[oc * 49 + tap] = v;
+        if (w.dw2 != nullptr && r >= 1 && r <= 5 && sx >= 1 && sx <= 5) w.dw2[oc * 25 + (r - 1) * 5 + (sx - 1)] = v;
+        if (w.dw3 != nullptr && r >= 2 && r <= 4 && sx >= 2 && sx <= 4) w.dw3[oc * 9 + (r - 2) * 3 + (sx - 2)] = v;
+    }
+}
+__device__ __forceinline__ void wred_add(float4& s, const float4& a) { s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w; }
 __global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(const WredEntry* __restrict__ tab, int n) {
     __shared__ float4 red[256];
     const int s_t = egm_find_entry(tab, n, (long long)blockIdx.x);
@@ -855,38 +888,40 @@ __global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(const WredEntry
     const WredEntry w = tab[s_t];
     const long long total = (long long)w.taps * w.CoutP * w.CinP;           // multiple of 8 (CinP is)
     const int cin_g = w.CinR / w.groups, cout_g = w.CoutR / w.groups;
-    const int e = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const long long i0 = (long long)s_c * kWredElems + e * 4;
+    const bool wide = (w.mode & kWredWide) != 0;                            // uniform over the block
+    const int cols = wide ? kWredElemsWide / 4 : kWredElems / 4, lanes = 256 / cols;
+    const int e = threadIdx.x & (cols - 1), sl = threadIdx.x >> (wide ? 4 : 6);
+    const long long i0 = (long long)s_c * (cols * 4) + e * 4;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     if (i0 < total) {
         const float* src = w.slab + i0;
         int k = sl;
-        for (; k + 4 < w.nslab; k += 8) {
+        for (; k + lanes < w.nslab; k += 2 * lanes) {
             const float4 a = *reinterpret_cast<const float4*>(src + (long long)k * total);
-            const float4 c = *reinterpret_cast<const float4*>(src + (long long)(k + 4) * total);
-            s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
-            s.x += c.x; s.y += c.y; s.z += c.z; s.w += c.w;
+            const float4 c = *reinterpret_cast<const float4*>(src + (long long)(k + lanes) * total);
+            wred_add(s, a);
+            wred_add(s, c);
         }
-        if (k < w.nslab) {
-            const float4 a = *reinterpret_cast<const float4*>(src + (long long)k * total);
-            s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
-        }
+        if (k < w.nslab) wred_add(s, *reinterpret_cast<const float4*>(src + (long long)k * total));
     }
     red[threadIdx.x] = s;
     __syncthreads();
-    if (sl == 0 && i0 < total) {
-        const float4 r0 = red[e], r1 = red[64 + e], r2 = red[128 + e], r3 = red[192 + e];
-        const float v[4] = {(r0.x + r1.x) + (r2.x + r3.x), (r0.y + r1.y) + (r2.y + r3.y), (r0.z + r1.z) + (r2.z + r3.z),
-                            (r0.w + r1.w) + (r2.w + r3.w)};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long long i = i0 + j;
-            const int ci = (int)(i % w.CinP), co = (int)((i / w.CinP) % w.CoutP), tap = (int)(i / ((long long)w.CinP * w.CoutP));
-            if (co < w.CoutR && ci < w.CinR && (co / cout_g) == (ci / cin_g)) {
-                const long long o = ((long long)co * cin_g + (ci % cin_g)) * w.taps + tap;
-                w.dw[o] = w.accumulate ? w.dw[o] + v[j] : v[j];
-            }
+    float4 v4;
+    if (wide) {
+        for (int h = 8; h > 0; h >>= 1) {
+            if (sl < h) wred_add(red[threadIdx.x], red[threadIdx.x + h * cols]);
+            __syncthreads();
         }
+        v4 = red[e];
+    } else {
+        const float4 r0 = red[e], r1 = red[64 + e], r2 = red[128 + e], r3 = red[192 + e];
+        v4 = make_float4((r0.x + r1.x) + (r2.x + r3.x), (r0.y + r1.y) + (r2.y + r3.y), (r0.z + r1.z) + (r2.z + r3.z),
+                         (r0.w + r1.w) + (r2.w + r3.w));
+    }
+    if (sl == 0 && i0 < total) {
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wred_store(w, i0 + j, v[j], cin_g, cout_g);
     }
 }
 
@@ -1080,8 +1115,10 @@ extern "C" int egm_conv_wgrad_slabs(int dtype, int N, int H, int W, int Cin, int
     if (wgrad_plan(dtype, N, H, W, Cin, Cout, KH, KW, dil, &pl) != EGM_OK) return -1;
     return pl.nsplit;
 }
-/* table: device array of {const float* slab; float* dw; int nslab, taps, CoutP, CinP, CoutR, CinR, groups, accumulate;} (48 bytes) */
+/* table: device array of WredEntry (72 bytes, include/egm_hip.h) */
 extern "C" int egm_wgrad_reduce_chunk(void) { return kWredElems; }
+extern "C" int egm_wgrad_reduce_chunk_wide(void) { return kWredElemsWide; }
+extern "C" int egm_wgrad_reduce_is_wide(int nslab, int taps, int CoutP, int CinP) { return wgrad_reduce_wide(nslab, (long long)taps * CoutP * CinP); }
 extern "C" int egm_wgrad_reduce_multi(const void* table_dev, int n, long long total_chunks, egm_stream_t s) {
     EGM_REQUIRE(table_dev && n > 0 && total_chunks > 0 && total_chunks < (1LL << 30), "wgrad_reduce_multi: bad args");
     hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const WredEntry*)table_dev, n);
@@ -1154,7 +1191,7 @@ extern "C" int egm_wgrad_reduce(const float* slabs, float* dw, int nslab, int ta
     hipStream_t st = (hipStream_t)s;
     const long long total = (long long)taps * CoutP * CinP;
     const int grid = (int)((total + 63) / 64);
-    if (nslab >= 256 && grid < 1024)                   // many slabs of a small gradient: more slab lanes per element
+    if (wgrad_reduce_wide(nslab, total))               // many slabs of a small gradient: more slab lanes per element
         hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3(grid), dim3(1024), 0, st, slabs, dw, nslab, taps, CoutP, CinP, CoutR, CinR, groups, accumulate);
     else
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid), dim3(256), 0, st, slabs, dw, nslab, taps, CoutP, CinP, CoutR, CinR, groups, accumulate);

@@ -144,6 +144,13 @@ class FusionConv(nn.Module):
         for m in (self.down, self.conv_3x3, self.conv_5x5, self.conv_7x7):
             m._egm_no_prepack = True                            # consumed through fold2 / merge357
 
+    def _egm_derived_weights(self):
+        """What ops.prepack_model builds for this module inside its one launch: the weights forward() derives with ops.fold2 /
+        ops.merge357, named by kind and real parameters (the argument order of those two)."""
+        return [("fold2", (self.down.weight,)),
+                ("merge357", (self.conv_3x3.weight, self.conv_5x5.weight, self.conv_7x7.weight, self.conv_3x3.bias, self.conv_5x5.bias,
+                              self.conv_7x7.bias))]
+
     def forward(self, x1, x2=None):
         """x2 is None (or x1 itself) == the reference call fusion_conv(concat, concat): cat([x, x]) is never built, the two
         halves of `down.weight` are summed instead; conv3+conv5+conv7 run as one 7x7 conv with the summed kernels."""

@@ -283,8 +283,27 @@ def _packed_weights(weight, groups, dtype):
     return wf, wd
 
 
+_PACK_ENTRY = struct.Struct("<10Q10i")     # the table entry of egm_conv_pack_multi (include/egm_hip.h)
+_derived_packs = {}                         # id(first real parameter) -> (stamp, weak reference to it, out, bout, wf, wd): see _prepacked
+
+
+def _derived_stamp(reals, dtype):
+    return (_weight_generation[0], dtype, tuple(p._version for p in reals), tuple(p.data_ptr() for p in reals))
+
+
+def _prepacked(reals, dtype):
+    """(out, bout, wf, wd) when the model-wide prepack has built the weight derived from `reals` for `dtype` and none of them has changed
+    since (weight generation, versions, addresses), else None.  The buffers belong to the prepack state: callers hand out aliases."""
+    hit = _derived_packs.get(id(reals[0]))
+    if hit is None or hit[1]() is not reals[0] or hit[0] != _derived_stamp(reals, dtype):
+        return None
+    return hit[2:]
+
+
 def prepack_model(model, dtype):
-    """Pack every nn.Conv2d weight of `model` (except holders flagged _egm_no_prepack) in ONE kernel launch."""
+    """Pack every nn.Conv2d weight of `model` (except holders flagged _egm_no_prepack) in ONE kernel launch.  The same launch builds
+    the derived weights of the modules that name them (a method _egm_derived_weights() -> [(kind, real parameters)], kind "fold2":
+    (weight,), "merge357": (w3, w5, w7, b3, b5, b7)) and their packs: ops.fold2 / ops.merge357 then launch nothing."""
     st = getattr(model, "_egm_prepack", None)
     if st is None or st["dtype"] != dtype:
         convs = [m for m in model.modules() if isinstance(m, torch.nn.Conv2d) and not getattr(m, "_egm_no_prepack", False)
@@ -295,11 +314,28 @@ def prepack_model(model, dtype):
             Cin = Cin_g * m.groups
             bufs.append((torch.empty((KH * KW, pad8(Cout), pad8(Cin)), dtype=dtype, device=m.weight.device),
                          torch.empty((KH * KW, pad8(Cin), pad8(Cout)), dtype=dtype, device=m.weight.device)))
-        st = model._egm_prepack = {"dtype": dtype, "convs": convs, "bufs": bufs, "table": DeviceTable(), "stamp": None}
-    convs, bufs = st["convs"], st["bufs"]
-    if not convs:
+        derived = []
+        for m in (model.modules() if isinstance(model, torch.nn.Module) else ()):
+            for kind, reals in (m._egm_derived_weights() if hasattr(m, "_egm_derived_weights") else ()):
+                if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in reals):
+                    continue
+                dev = reals[0].device
+                if kind == "fold2":
+                    Co, Ci, taps = reals[0].shape[0], reals[0].shape[1] // 2, 1
+                    out, bout = torch.empty((Co, Ci, 1, 1), dtype=torch.float32, device=dev), None
+                else:
+                    Co, Ci, taps = reals[2].shape[0], reals[2].shape[1], 49
+                    out = torch.empty((Co, Ci, 7, 7), dtype=torch.float32, device=dev)
+                    bout = torch.empty((Co,), dtype=torch.float32, device=dev)
+                derived.append((kind, tuple(reals), Co, Ci, taps, out, bout,
+                                torch.empty((taps, pad8(Co), pad8(Ci)), dtype=dtype, device=dev),
+                                torch.empty((taps, pad8(Ci), pad8(Co)), dtype=dtype, device=dev)))
+        st = model._egm_prepack = {"dtype": dtype, "convs": convs, "bufs": bufs, "derived": derived, "table": DeviceTable(), "stamp": None}
+    convs, bufs, derived = st["convs"], st["bufs"], st.get("derived", ())
+    if not convs and not derived:
         return
-    stamp = (_weight_generation[0], tuple(m.weight._version for m in convs), tuple(m.weight.data_ptr() for m in convs))
+    held = [m.weight for m in convs] + [p for d in derived for p in d[1]]
+    stamp = (_weight_generation[0], tuple(p._version for p in held), tuple(p.data_ptr() for p in held))
     if stamp == st["stamp"]:
         return
     L = lib()
@@ -308,16 +344,30 @@ def prepack_model(model, dtype):
     for m, (wf, wd) in zip(convs, bufs):
         Cout, Cin_g, KH, KW = m.weight.shape
         Cin = Cin_g * m.groups
-        blob += struct.pack("<QQQiiiiiiii", m.weight.data_ptr(), wf.data_ptr(), wd.data_ptr(), Cout, Cin, pad8(Cout), pad8(Cin), KH, KW,
-                            m.groups, chunks)                  # last field = index of the entry's first workgroup
+        blob += _PACK_ENTRY.pack(m.weight.data_ptr(), wf.data_ptr(), wd.data_ptr(), 0, 0, 0, 0, 0, 0, 0, Cout, Cin, pad8(Cout), pad8(Cin),
+                                 KH, KW, m.groups, chunks, 0, 0)       # chunks = index of the entry's first workgroup
         chunks += (KH * KW * pad8(Cout) * pad8(Cin) + chunk - 1) // chunk
-    dev = convs[0].weight.device
+    for kind, reals, Co, Ci, taps, out, bout, wf, wd in derived:
+        if kind == "fold2":
+            blob += _PACK_ENTRY.pack(reals[0].data_ptr(), wf.data_ptr(), wd.data_ptr(), 0, 0, 0, 0, 0, out.data_ptr(), 0, Co, Ci, pad8(Co),
+                                     pad8(Ci), 1, 1, 1, chunks, 1, 0)
+        else:
+            w3, w5, w7, b3, b5, b7 = reals
+            blob += _PACK_ENTRY.pack(w7.data_ptr(), wf.data_ptr(), wd.data_ptr(), w5.data_ptr(), w3.data_ptr(), b7.data_ptr(), b5.data_ptr(),
+                                     b3.data_ptr(), out.data_ptr(), bout.data_ptr(), Co, Ci, pad8(Co), pad8(Ci), 7, 7, 1, chunks, 2, 0)
+        chunks += (taps * pad8(Co) * pad8(Ci) + chunk - 1) // chunk
+    dev = held[0].device
     table = st["table"].get(bytes(blob), dev)
-    L.call("egm_conv_pack_multi", dtype_code(dtype), ptr(table), len(convs), chunks, stream())
+    L.call("egm_conv_pack_multi", dtype_code(dtype), ptr(table), len(convs) + len(derived), chunks, stream())
     for m, (wf, wd) in zip(convs, bufs):
         w = m.weight
         key = (w.data_ptr(), w._version, _weight_generation[0], dtype, m.groups, tuple(w.shape))
         _pack_cache[id(w)] = (key, wf, wd, weakref.ref(w))
+    if len(_derived_packs) > 64:                                      # drop the buffers of models that are gone
+        for k in [k for k, v in _derived_packs.items() if v[1]() is None]:
+            del _derived_packs[k]
+    for kind, reals, Co, Ci, taps, out, bout, wf, wd in derived:
+        _derived_packs[id(reals[0])] =(_derived_stamp(reals, dtype), weakref.ref(reals[0]), out, bout, wf, wd)
     st["stamp"] = stamp
 
 
@@ -329,6 +379,7 @@ def prepack_model(model, dtype):
 #   wgrads   the reductions of those slabs, ONE multi-conv launch (egm_wgrad_reduce_multi)
 #   bgrads   db = sum over pixels of dy for every nn.Conv2d bias that no BatchNorm follows, ONE pair of launches (egm_bias_grad_multi)
 #   dz       data gradients that a BatchNorm backward computes itself from a stand-in tensor (csrc/bn_dz_fused.hip)
+# (`derived` holds the open stand-ins of convs on derived weights, whose wgrads / bgrads entries still wait for the real destinations.)
 # Deferring a weight (bias) gradient hands autograd a tensor that is filled later, which is only sound when that tensor is the
 # parameter's ONLY contribution in this backward (autograd would otherwise sum unfilled buffers): _conv_uses counts the conv forwards a
 # weight has taken part in since its gradients were last produced, and a weight used more than once takes the immediate path.  That
@@ -368,6 +419,10 @@ defer_bgrads = _Switch("EGM_DEFER_BGRAD", "1",
 fuse_dz = _Switch("EGM_FUSE_DZ", "1",
                   """Get / set whether BatchNorm backward computes dz on the fly from the classifier / MCALayer behind it (tests compare both
                   ways).""")
+defer_derived = _Switch("EGM_DEFER_DERIVED", "1",
+                        """Get / set whether the gradients of a conv whose weight is derived from real parameters (ops.fold2, ops.merge357)
+                        join the deferred work of the backward run: the end-of-backward reduction then writes the real parameters'
+                        gradients itself (tests compare both ways).""")
 
 
 def _wgrad_deferrable(weight):
@@ -378,11 +433,58 @@ def _wgrad_deferrable(weight):
             and not weight._backward_hooks and not torch.is_grad_enabled())
 
 
+# Derived weights (ops.fold2 / ops.merge357): non-leaf tensors computed from real parameters by an autograd node of this module.  The
+# side table says which, so that the backward of the conv that consumes one can defer like a conv on a leaf weight: its slab reduction
+# (and the merged bias sum) then write the gradients of the REAL parameters, and the node in between launches nothing.
+_Derived = namedtuple("_Derived", "ref kind reals")      # kind: "fold2" | "merge357" | "bias3"; reals in the kernel's destination order
+_derived = {}                                             # id(derived tensor) -> _Derived
+WRED_PLAIN, WRED_FOLD2, WRED_MERGE357, WRED_WIDE = 0, 1, 2, 4     # egm_wgrad_reduce_multi: entry modes
+
+
+def _register_derived(t, kind, reals):
+    """`t` was computed from the parameters `reals`; each of them takes part in one more conv forward that awaits its backward."""
+    if not t.requires_grad:
+        return
+    if len(_derived) > 256:
+        for k in [k for k, v in _derived.items() if v.ref() is None]:
+            del _derived[k]
+    _derived[id(t)] = _Derived(weakref.ref(t), kind, tuple(reals))
+    for p in reals:
+        _note_conv_use(p)
+
+
+def _derived_of(t):
+    d = _derived.get(id(t)) if t is not None else None
+    return d if d is not None and d.ref() is t else None
+
+
+def _fillable(p):
+    """A leaf parameter whose gradient autograd will adopt as it is returned (see _wgrad_deferrable)."""
+    return p.is_leaf and p.requires_grad and p.grad is None and not p._backward_hooks
+
+
+def _wgrad_deferral(weight, bias=None):
+    """The answer of _wgrad_deferrable for the weight of a conv whose backward runs now; for a derived weight the _Derived record
+    instead of True when every real parameter behind it (and behind `bias`, when that is derived too and wanted) would pass on its own
+    terms.  Consumes the use notes of the weight and of the real parameters: call once per backward of a conv."""
+    d = _derived_of(weight)
+    if d is None:
+        return _wgrad_deferrable(weight)
+    db = _derived_of(bias)
+    ok = _sole_conv_use(weight)
+    reals = d.reals + (db.reals if db is not None else ())
+    sole = [_sole_conv_use(p) for p in reals]                        # (a list: every note is consumed)
+    ok = (ok and all(sole) and all(_fillable(p) for p in reals) and _DEFER_WGRAD and defer_derived.on and merge_wgrads.on
+          and (db is None or defer_bgrads.on) and (bias is None or db is not None or bias.is_leaf) and not torch.is_grad_enabled())
+    return d if ok else False
+
+
 # The tables outlive every run on purpose: a captured hipGraph re-uploads their bytes on every replay.  The *_partial twins serve the
 # mid-backward flushes (eager gradient exchange), which must never disturb the bytes a captured graph re-uploads.
 _wgrad_table, _wgrad_table_partial, _bgrad_table, _bgrad_table_partial = DeviceTable(), DeviceTable(), DeviceTable(), DeviceTable()
 _BSUM_ENTRY = struct.Struct("<3Qq6i")       # egm_bsum_entry
 _WGRAD_DESC = struct.Struct("<3Q14i")       # egm_conv_wgrad_desc
+_WRED_ENTRY = struct.Struct("<4Q10i")       # the table entry of egm_wgrad_reduce_multi (include/egm_hip.h)
 _wgrad_names = {}
 
 
@@ -396,32 +498,52 @@ def _wgrad_kernel_of(dt, N, H, W, CinP, CoutP, KH, KW, dil):
     return name
 
 
-# queue entries (they keep the tensors their launch reads alive; `param` is the weight / bias, gref / gptr its unfilled gradient)
+# queue entries (they keep the tensors their launch reads alive).  `dests` lists the gradients the launch writes as (parameter, weak
+# reference to the unfilled tensor backward() returned for it, that tensor's address): one for a leaf weight / bias; for a derived
+# weight or bias `ndest` of them, the real parameters behind it, attached by the backward of the deriving node (_attach_derived) --
+# until then the list is short and the entry is not ready.
 _Slab = namedtuple("_Slab", "dt x ldx gy ldg ws N H W CinP CoutP Cin Cout KH KW dil groups")
-_Wgrad = namedtuple("_Wgrad", "ws param nslab taps CoutP CinP Cout Cin groups gref gptr")
-_Bgrad = namedtuple("_Bgrad", "gy ldg npix C Cout param gref gptr")
+_Wgrad = namedtuple("_Wgrad", "ws nslab taps CoutP CinP Cout Cin groups mode ndest dests")
+_Bgrad = namedtuple("_Bgrad", "gy ldg npix C Cout ndest dests")
+
+
+def _unfilled(shape, device):
+    """A gradient tensor that the end-of-backward launches fill (tests replace this to see an unfilled one)."""
+    return torch.empty(shape, dtype=torch.float32, device=device)
 
 
 def _handed_over(queue, ready_only, name):
     """The hand-over protocol of the deferred weight and bias gradients.  The unfilled tensor backward() returned was handed to autograd
     with no reference kept here, so that it is adopted as param.grad without a copy (backward()) or returned to the caller as is
     (torch.autograd.grad()); it is still reachable through the weak reference or as the storage param.grad now shares.
-    -> the entries to fill now; `queue` keeps those for later (ready_only: autograd has not adopted the tensor yet)."""
+    -> [(entry, destination addresses, None for a discarded one)] to fill now; `queue` keeps the entries for later (ready_only: autograd
+    has not adopted the tensor yet).  An entry with several destinations is taken when ALL of them can be written, and is never dropped
+    while one of them is still to come."""
     todo, later = [], []
     for ent in queue:
-        grad = ent.param.grad
-        if ent.gref() is not None or (grad is not None and grad.data_ptr() == ent.gptr):
-            todo.append(ent)
-        elif ready_only:
+        ptrs, pending = [], len(ent.dests) < ent.ndest             # a derived entry whose stand-in has not reached its node yet
+        for param, gref, gptr in ent.dests:
+            grad = param.grad
+            if gref() is not None or (grad is not None and grad.data_ptr() == gptr):
+                ptrs.append(gptr)
+            elif ready_only:
+                pending = True
+            elif grad is not None:
+                # the unfilled buffer is gone but the parameter HAS a gradient: autograd copied or transformed the buffer instead of
+                # adopting it (a tensor hook returning a new tensor, a non-stealable gradient), so param.grad holds whatever the
+                # uninitialised buffer contained.  The deferring code refuses in the cases it can see; anything else must not train on.
+                raise RuntimeError(f"deferred conv {name} gradient lost its destination: {name}.grad exists but is not the buffer backward() "
+                                   f"returned (tensor hook / gradient copy); set EGM_DEFER_{name[0].upper()}GRAD=0 for this model")
+            else:
+                # nobody holds the gradient and the parameter has none (torch.autograd.grad() result dropped, or the parameter was not
+                # among backward(inputs=...)): it was discarded, nothing to finish
+                ptrs.append(None)
+        if pending:
+            if not ready_only:
+                raise RuntimeError(f"deferred conv {name} gradient of a derived {name} never reached its real parameters")
             later.append(ent)
-        elif grad is not None:
-            # the unfilled buffer is gone but the parameter HAS a gradient: autograd copied or transformed the buffer instead of
-            # adopting it (a tensor hook returning a new tensor, a non-stealable gradient), so param.grad holds whatever the
-            # uninitialised buffer contained.  The deferring code refuses in the cases it can see; anything else must not train on.
-            raise RuntimeError(f"deferred conv {name} gradient lost its destination: {name}.grad exists but is not the buffer backward() "
-                               f"returned (tensor hook / gradient copy); set EGM_DEFER_{name[0].upper()}GRAD=0 for this model")
-        # else: nobody holds the gradient and the parameter has none (torch.autograd.grad() result dropped, or the parameter was not
-        # among backward(inputs=...)): it was discarded, nothing to finish
+        elif any(q is not None for q in ptrs):
+            todo.append((ent, ptrs))
     queue[:] = later
     return todo
 
@@ -438,10 +560,10 @@ class _BackwardRun:
     The DeviceTables are shared by all runs.  Outside a capture that is safe under nesting (uploads are ordered on the stream, a rewrite
     of the pinned bytes waits for the previous upload: upload_pinned); inside a hipGraph capture every distinct content takes one buffer
     pair of DeviceTable.POOL, so nested runs inside a capture are bounded by that pool (exhaustion raises)."""
-    __slots__ = ("id", "slabs", "wgrads", "bgrads", "dz", "__weakref__")
+    __slots__ = ("id", "slabs", "wgrads", "bgrads", "dz", "derived", "__weakref__")
 
     def __init__(self, run_id):
-        self.id, self.slabs, self.wgrads, self.bgrads, self.dz = run_id, [], [], [], {}
+        self.id, self.slabs, self.wgrads, self.bgrads, self.dz, self.derived = run_id, [], [], [], {}, {}
 
     def finish(self):
         _runs.pop(self.id, None)
@@ -450,6 +572,17 @@ class _BackwardRun:
             self.dz.clear()
             raise RuntimeError(f"egm_unet_amd: deferred BatchNorm gradients {kinds} were never consumed (the tensor between the producer and "
                                "its BatchNorm had another consumer); call ops.fuse_dz(False)")
+        if self.derived:
+            # stand-ins whose deriving node never ran in this run: autograd had no use for the derived tensor's gradient (its real
+            # parameters are not among backward(inputs=...): the decoder half of the split data-parallel step runs the encoder's
+            # FusionConv convs for their data gradients only) and dropped it.  Nothing to finish, as for a plain weight whose returned
+            # gradient was discarded.  (A node that DOES run while a stand-in of its own is open, but receives something else, raises
+            # there and then: _no_open_standin.)
+            dead = [v[1] for v in self.derived.values()]
+            self.derived.clear()
+            gone = lambda e: any(e is d for d in dead)
+            self.slabs = [s for s in self.slabs if not any(s.ws is d.ws for d in dead if isinstance(d, _Wgrad))]
+            self.wgrads, self.bgrads = [e for e in self.wgrads if not gone(e)], [e for e in self.bgrads if not gone(e)]
         self.flush()
 
     def flush(self, ready_only=False):
@@ -465,21 +598,26 @@ class _BackwardRun:
             return
         L = lib()
         by_dtype = {}
-        for e in todo:
-            by_dtype.setdefault(e.gy.dtype, []).append(e)
+        for e, ptrs in todo:
+            by_dtype.setdefault(e.gy.dtype, []).append((e, [q for q in ptrs if q is not None]))
         for dtype, ents in by_dtype.items():
-            dev = ents[0].gy.device
-            nblks = [L.query("egm_channel_partials_blocks", e.npix, e.C) for e in ents]
-            ws = torch.empty(sum(nb * 2 * e.C for nb, e in zip(nblks, ents)), dtype=torch.float32, device=dev)
+            dev = ents[0][0].gy.device
+            nblks = [L.query("egm_channel_partials_blocks", e.npix, e.C) for e, _ in ents]
+            ws = torch.empty(sum(nb * 2 * e.C for nb, (e, _) in zip(nblks, ents)), dtype=torch.float32, device=dev)
             blob1, blob2, b1, b2, off = bytearray(), bytearray(), 0, 0, 0
-            for nb, e in zip(nblks, ents):
+            for nb, (e, outs) in zip(nblks, ents):
                 part = ws.data_ptr() + 4 * off
-                blob1 += _BSUM_ENTRY.pack(e.gy.data_ptr(), part, e.gptr, e.npix, e.ldg, e.C, e.Cout, nb, b1, 0)
-                blob2 += _BSUM_ENTRY.pack(e.gy.data_ptr(), part, e.gptr, e.npix, e.ldg, e.C, e.Cout, nb, b2, 0)
-                b1 += nb; b2 += e.C // 8; off += nb * 2 * e.C
+                # one pass over dy per tensor; a sum with several destinations (the merged bias of merge357: the same number for three
+                # parameters) takes one stage-2 entry per destination, all reading the same partials, and as many stage-1 entries, the
+                # extra ones without blocks (the block search never lands on an entry that shares its first block with its successor)
+                for j, out in enumerate(outs):
+                    blob1 += _BSUM_ENTRY.pack(e.gy.data_ptr(), part, out, e.npix, e.ldg, e.C, e.Cout, nb if j == 0 else 0, b1, 0)
+                    blob2 += _BSUM_ENTRY.pack(e.gy.data_ptr(), part, out, e.npix, e.ldg, e.C, e.Cout, nb, b2, 0)
+                    b1 += nb if j == 0 else 0; b2 += e.C // 8
+                off += nb * 2 * e.C
             _bgrad_table.reserve(dev); _bgrad_table_partial.reserve(dev)
             table = (_bgrad_table_partial if ready_only else _bgrad_table).get(bytes(blob1 + blob2), dev)
-            L.call("egm_bias_grad_multi", dtype_code(dtype), ptr(table), len(ents), b1, b2, stream())
+            L.call("egm_bias_grad_multi", dtype_code(dtype), ptr(table), len(blob2) // _BSUM_ENTRY.size, b1, b2, stream())
 
     def launch_slabs(self):
         """The queued slab kernels, in queue order, those of one kernel instantiation four to a launch (egm_conv_wgrad_multi)."""
@@ -503,11 +641,14 @@ class _BackwardRun:
         if not todo:
             return
         blob, chunks = bytearray(), 0
-        per = lib().cdll.egm_wgrad_reduce_chunk()
-        for e in todo:
-            blob += struct.pack("<QQiiiiiiiiii", e.ws.data_ptr(), e.gptr, e.nslab, e.taps, e.CoutP, e.CinP, e.Cout, e.Cin, e.groups, 0, chunks, 0)
-            chunks += (e.taps * e.CoutP * e.CinP + per - 1) // per
-        dev = todo[0].param.device
+        per, per_wide = lib().cdll.egm_wgrad_reduce_chunk(), lib().cdll.egm_wgrad_reduce_chunk_wide()
+        for e, ptrs in todo:
+            d = [q or 0 for q in ptrs] + [0, 0]
+            blob += _WRED_ENTRY.pack(e.ws.data_ptr(), d[0], d[1], d[2], e.nslab, e.taps, e.CoutP, e.CinP, e.Cout, e.Cin, e.groups, 0, chunks,
+                                     e.mode)
+            n = per_wide if e.mode & WRED_WIDE else per
+            chunks += (e.taps * e.CoutP * e.CinP + n - 1) // n
+        dev = todo[0][0].ws.device
         _wgrad_table.reserve(dev); _wgrad_table_partial.reserve(dev)      # both exist before any capture can need them
         table = (_wgrad_table_partial if ready_only else _wgrad_table).get(bytes(blob), dev)
         lib().call("egm_wgrad_reduce_multi", ptr(table), len(todo), chunks, stream())
@@ -532,8 +673,54 @@ def flush_ready_wgrads():
         run.flush(ready_only=True)
 
 
-def _queue_wgrad(ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, gw):
-    _run().wgrads.append(_Wgrad(ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, weakref.ref(gw), gw.data_ptr()))
+def _queue_wgrad(ws, weight, nslab, taps, CoutP, CinP, Cout, Cin, groups, gw, defer=True):
+    """Queue the slab reduction of a conv whose backward returns the unfilled `gw` for `weight`.  defer = the _Derived record of a derived
+    weight (_wgrad_deferral): gw is then a stand-in on its way to the deriving node, which names the real destinations
+    (_attach_derived); a layer whose own reduction is the many-slab kernel keeps that summation order."""
+    run = _run()
+    if defer is True:
+        run.wgrads.append(_Wgrad(ws, nslab, taps, CoutP, CinP, Cout, Cin, groups, WRED_PLAIN, 1, [(weight, weakref.ref(gw), gw.data_ptr())]))
+        return
+    mode, ndest = (WRED_FOLD2, 1) if defer.kind == "fold2" else (WRED_MERGE357, 3)
+    if lib().cdll.egm_wgrad_reduce_is_wide(nslab, taps, CoutP, CinP):
+        mode |= WRED_WIDE
+    ent = _Wgrad(ws, nslab, taps, CoutP, CinP, Cout, Cin, groups, mode, ndest, [])
+    run.wgrads.append(ent)
+    run.derived[gw.data_ptr()] = (gw, ent, defer.reals[0])         # the stand-in stays alive: its address cannot be recycled meanwhile
+
+
+def _queue_derived_bgrad(gy, Cout, derived):
+    """The merged bias of merge357 (`derived`: its _Derived record) behind a conv that defers: one pass over gy at the end of backward
+    writes all three real biases.  -> the stand-in for the derived bias's gradient."""
+    gy, ldg = _nhwc(gy)
+    gb = torch.empty(Cout, dtype=torch.float32, device=gy.device)
+    ent = _Bgrad(gy, ldg, _npix(gy), gy.shape[3], Cout, 3, [])
+    run = _run()
+    run.bgrads.append(ent)
+    run.derived[gb.data_ptr()] = (gb, ent, derived.reals[0])
+    return gb
+
+
+def _take_derived(g):
+    """The queue entry when the incoming gradient `g` is a stand-in registered in this run, else None.  Creates no record."""
+    run = _run(create=False)
+    pend = run.derived.pop(g.data_ptr(), None) if run is not None and run.derived and g is not None else None
+    return None if pend is None else pend[1]
+
+
+def _no_open_standin(reals):
+    """Called by a deriving node whose incoming gradient is NOT a stand-in: no stand-in for a tensor derived from `reals` may be open in
+    this run -- the derived tensor then had a consumer besides its conv, autograd summed the stand-in into something else, and the
+    gradient at hand is garbage."""
+    run = _run(create=False)
+    if run is not None and run.derived and any(v[2] is p for v in run.derived.values() for p in reals):
+        raise RuntimeError("egm_unet_amd: the deferred gradient of a derived weight was never consumed (the derived tensor had a consumer "
+                           "besides its conv); call ops.defer_derived(False)")
+
+
+def _attach_derived(ent, params, grads):
+    """Name the real destinations of a derived entry: `grads` are the unfilled tensors the deriving node returns for `params`."""
+    ent.dests.extend((p, weakref.ref(g), g.data_ptr()) for p, g in zip(params, grads))
 
 
 # deferred dz: the producer's backward (the 1x1 classifier's data gradient; the MCALayer's last step; a conv behind a concat) does not
@@ -559,7 +746,7 @@ def _bias_grad(gy, Cout, bias=None, defer=False):
             and not torch.is_grad_enabled()):
         gy, ldg = _nhwc(gy)
         gb = torch.empty(Cout, dtype=torch.float32, device=gy.device)
-        _run().bgrads.append(_Bgrad(gy, ldg, _npix(gy), gy.shape[3], Cout, bias, weakref.ref(gb), gb.data_ptr()))
+        _run().bgrads.append(_Bgrad(gy, ldg, _npix(gy), gy.shape[3], Cout, 1, [(bias, weakref.ref(gb), gb.data_ptr())]))
         return gb
     return _channel_sum(gy)[0, :Cout]
 
@@ -716,7 +903,7 @@ def _conv1x1_bwd(items):
         descs.append(_C1_DESC.pack(x.data_ptr(), dy.data_ptr(), wd.data_ptr(), 0 if gx is None else gx.data_ptr(), ws.data_ptr(), npix, ldx, lddy,
                                    CinP, CinP, CoutP, 0))
         if defer:
-            _queue_wgrad(ws, weight, nslab, 1, CoutP, CinP, Cout, Cin, 1, gw)
+            _queue_wgrad(ws, weight, nslab, 1, CoutP, CinP, Cout, Cin, 1, gw, defer)
         else:
             now.append((ws, gw, nslab, CoutP, CinP, Cout, Cin))
         res.append((gx, gw))
@@ -762,7 +949,7 @@ def _conv_wgrad(x, ldx, gy, ldg, weight, dil, groups, Cin, Cout, defer=None):
                dil, groups, 0, st)
     if defer:
         nslab = L.query("egm_conv_wgrad_slabs", dt, N, H, W, CinP, CoutP, KH, KW, dil)
-        _queue_wgrad(ws, weight, nslab, KH * KW, CoutP, CinP, Cout, Cin, groups, gw)
+        _queue_wgrad(ws, weight, nslab, KH * KW, CoutP, CinP, Cout, Cin, groups, gw, defer)
     return gw
 
 
@@ -807,9 +994,16 @@ class _Conv2d(Function):
         L, dt, st = lib(), dtype_code(x.dtype), stream()
         gx = gw = gb = None
         need_gx, need_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        defer = _wgrad_deferrable(weight) if need_gw else False     # (consumes the weight's use note: asked once per backward)
-        if has_bias and ctx.needs_input_grad[2]:
-            gb = _zero_grad_vec(Cout, x.device) if ctx.bias_grad_zero else _bias_grad(gy, Cout, ctx.bias, defer)
+        want_gb = has_bias and ctx.needs_input_grad[2]
+        # (consumes the weight's use note: asked once per backward.  True, or the _Derived record of a derived weight that defers)
+        defer = _wgrad_deferral(weight, ctx.bias if want_gb and not ctx.bias_grad_zero else None) if need_gw else False
+        if want_gb:
+            if ctx.bias_grad_zero:
+                gb = _zero_grad_vec(Cout, x.device)
+            elif defer is not True and defer and _derived_of(ctx.bias) is not None:
+                gb = _queue_derived_bgrad(gy, Cout, _derived_of(ctx.bias))                  # the merged bias: its three real biases from one pass over gy
+            else:
+                gb = _bias_grad(gy, Cout, ctx.bias, bool(defer))
         if need_gw and not (need_gx and ctx.defer_dgrad and fuse_dz.on) and _c1_shape_ok(x, gy, weight, dil, groups):
             # 1x1: data gradient + weight-gradient slabs from ONE pass over gy and x
             gx, gw = _conv1x1_bwd([(x, ldx, gy, ldg, weight, wd, need_gx, defer)])[0]
@@ -2139,9 +2333,13 @@ def _register_pack(weight, dtype, wf, wd):
 
 class _Fold2(Function):
     @staticmethod
-    def forward(ctx, w, pack_dtype):                       # [rows, 2K, 1, 1] -> [rows, K, 1, 1]
+    def forward(ctx, w, pack_dtype, pre=None):             # [rows, 2K, 1, 1] -> [rows, K, 1, 1]
         rows, K2 = w.shape[0], w.shape[1]
         K = K2 // 2
+        ctx.real = w
+        if pre is not None:                                # built by the model-wide prepack (prepack_model): no launch
+            _Fold2.packs = (pre[2], pre[3])
+            return pre[0].detach()                         # (an alias: every forward returns a tensor object of its own)
         out = torch.empty((rows, K, 1, 1), dtype=torch.float32, device=w.device)
         if pack_dtype is None:
             lib().call("egm_fold2_fwd", ptr(w.detach().contiguous()), ptr(out), rows, K, stream())
@@ -2156,17 +2354,25 @@ class _Fold2(Function):
     @staticmethod
     def backward(ctx, g):
         rows, K = g.shape[0], g.shape[1]
+        pend = _take_derived(g)
+        if pend is not None:                               # a stand-in: the conv's deferred reduction writes both halves itself
+            dw = _unfilled((rows, 2 * K, 1, 1), g.device)
+            _attach_derived(pend, (ctx.real,), (dw,))
+            return dw, None, None
+        _no_open_standin((ctx.real,))
         dw = torch.empty((rows, 2 * K, 1, 1), dtype=torch.float32, device=g.device)
         lib().call("egm_fold2_bwd", ptr(g.contiguous()), ptr(dw), rows, K, stream())
-        return dw, None
+        return dw, None, None
 
 
 def fold2(w, pack_dtype=None):
-    """w[:, :K] + w[:, K:]; pack_dtype: also build the conv operand packs of the result for that activation dtype (one launch)."""
-    out = _Fold2.apply(w, pack_dtype)
+    """w[:, :K] + w[:, K:]; pack_dtype: also build the conv operand packs of the result for that activation dtype (one launch, none
+    when the model-wide prepack has built them already)."""
+    out = _Fold2.apply(w, pack_dtype, _prepacked((w,), pack_dtype) if pack_dtype is not None else None)
     if pack_dtype is not None and _Fold2.packs is not None:
         _register_pack(out, pack_dtype, *_Fold2.packs)
         _Fold2.packs = None
+    _register_derived(out, "fold2", (w,))
     return out
 
 
@@ -2207,8 +2413,13 @@ def spread_cols(w, real):
 
 class _Merge357(Function):
     @staticmethod
-    def forward(ctx, w3, w5, w7, b3, b5, b7, pack_dtype):
+    def forward(ctx, w3, w5, w7, b3, b5, b7, pack_dtype, pre=None):
         Co, Ci = w7.shape[0], w7.shape[1]
+        ctx.shape = (Co, Ci)
+        ctx.real = (w3, w5, w7, b3, b5, b7)
+        if pre is not None:                                # built by the model-wide prepack (prepack_model): no launch
+            _Merge357.packs = (pre[2], pre[3])
+            return pre[0].detach(), pre[1].detach()
         w = torch.empty((Co, Ci, 7, 7), dtype=torch.float32, device=w7.device)
         b = torch.empty((Co,), dtype=torch.float32, device=w7.device)
         args = (ptr(w3.detach().contiguous()), ptr(w5.detach().contiguous()), ptr(w7.detach().contiguous()), ptr(b3.detach()),
@@ -2221,13 +2432,29 @@ class _Merge357(Function):
             wd = torch.empty((49, pad8(Ci), pad8(Co)), dtype=pack_dtype, device=w7.device)
             lib().call("egm_merge357_pack", dtype_code(pack_dtype), *args, ptr(wf), ptr(wd), Co, Ci, stream())
             _Merge357.packs = (wf, wd)
-        ctx.shape = (Co, Ci)
         return w, b
 
     @staticmethod
     def backward(ctx, gw, gb):
         Co, Ci = ctx.shape
         dev = gw.device
+        w3, w5, w7, b3, b5, b7 = ctx.real
+        pw = _take_derived(gw)
+        if pw is not None:
+            # stand-ins: the conv's deferred reduction scatters into the three kernels itself, the deferred bias sum writes all three
+            # biases (the conv defers both or neither, _wgrad_deferral)
+            d3, d5, d7 = _unfilled((Co, Ci, 3, 3), dev), _unfilled((Co, Ci, 5, 5), dev), _unfilled((Co, Ci, 7, 7), dev)
+            _attach_derived(pw, (w7, w5, w3), (d7, d5, d3))           # the order of the reduction's destinations dw, dw2, dw3
+            if gb is None or not any(ctx.needs_input_grad[3:6]):
+                return d3, d5, d7, None, None, None, None, None
+            pb = _take_derived(gb)
+            if pb is None:
+                raise RuntimeError("egm_unet_amd: merge357 received a deferred weight gradient with a bias gradient that is not")
+            gb3 = _unfilled((3, Co), dev)
+            rows = (gb3[0], gb3[1], gb3[2])
+            _attach_derived(pb, (b3, b5, b7), rows)
+            return d3, d5, d7, rows[0], rows[1], rows[2], None, None
+        _no_open_standin(ctx.real)
         d3 = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=dev)
         d5 = torch.empty((Co, Ci, 5, 5), dtype=torch.float32, device=dev)
         d7 = torch.empty((Co, Ci, 7, 7), dtype=torch.float32, device=dev)
@@ -2238,15 +2465,18 @@ class _Merge357(Function):
             gb3 = torch.empty((3, Co), dtype=torch.float32, device=dev)
         lib().call("egm_merge357_bwd", ptr(gw.contiguous()), ptr(d3), ptr(d5), ptr(d7), ptr(gb), ptr(gb3), Co, Ci, stream())
         if gb3 is None:
-            return d3, d5, d7, None, None, None, None
-        return d3, d5, d7, gb3[0], gb3[1], gb3[2], None
+            return d3, d5, d7, None, None, None, None, None
+        return d3, d5, d7, gb3[0], gb3[1], gb3[2], None, None
 
 
 def merge357(w3, w5, w7, b3, b5, b7, pack_dtype=None):
-    w, b = _Merge357.apply(w3, w5, w7, b3, b5, b7, pack_dtype)
+    reals = (w3, w5, w7, b3, b5, b7)
+    w, b = _Merge357.apply(*reals, pack_dtype, _prepacked(reals, pack_dtype) if pack_dtype is not None else None)
     if pack_dtype is not None and _Merge357.packs is not None:
         _register_pack(w, pack_dtype, *_Merge357.packs)
         _Merge357.packs = None
+    _register_derived(w, "merge357", (w7, w5, w3))
+    _register_derived(b, "bias3", (b3, b5, b7))
     return w, b
 
 

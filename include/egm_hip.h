@@ -59,10 +59,16 @@ int egm_nhwc_to_nchw(int dtype, const void* src, int ld, void* dst_f32, int N, i
  * own arguments, callers never see it. */
 int egm_conv_pack(int dtype, const void* w_oihw_f32, void* wf, void* wd, int Cout, int Cin, int KH, int KW, int groups,
                   egm_stream_t s);
-/* Every conv weight of a model in one launch.  table_dev: device array of 56-byte entries
- * {const float* w; void* wf; void* wd; int Cout, Cin, CoutP, CinP, KH, KW, groups, chunk0;}; an entry takes
+/* Every conv weight of a model in one launch.  table_dev: device array of 120-byte entries
+ * {const float* w; void* wf; void* wd; const float* w5, *w3, *b7, *b5, *b3; float* out; float* bout;
+ *  int Cout, Cin, CoutP, CinP, KH, KW, groups, chunk0, kind, pad;}; an entry takes
  * ceil(KH*KW*CoutP*CinP / egm_conv_pack_chunk()) workgroups ("chunks"), chunk0 = the sum of the chunk counts of the entries before
- * it (the kernels of all *_multi entry points find their entry by binary search on chunk0), total_chunks = the sum over all. */
+ * it (the kernels of all *_multi entry points find their entry by binary search on chunk0), total_chunks = the sum over all.
+ * kind 0: egm_conv_pack of the parameter w (the other pointers unused).  The derived FusionConv weights, built from their real
+ * parameters by the same launch, bit for bit what egm_fold2_pack / egm_merge357_pack write:
+ * kind 1 (fold2, KH = KW = groups = 1): w = the real [Cout][2*Cin] weight, out = fp32 [Cout][Cin];
+ * kind 2 (merge357, KH = KW = 7, groups = 1): w / w5 / w3 = the 7x7 / 5x5 / 3x3 weights, b7 / b5 / b3 their biases, out = fp32
+ * [Cout][Cin][7][7], bout = fp32 [Cout]. */
 int egm_conv_pack_chunk(void);
 int egm_conv_pack_multi(int dtype, const void* table_dev, int n, long long total_chunks, egm_stream_t s);
 /* Launch groups: between egm_group_begin() and egm_group_end(s) the egm_conv_fwd* calls of THIS host thread are recorded instead of
@@ -126,9 +132,18 @@ int egm_conv_wgrad(int dtype, const void* x, int ldx, const void* dy, int lddy, 
                    int N, int H, int W, int Cin, int Cout, int CinR, int CoutR, int KH, int KW, int dil, int groups,
                    int accumulate, egm_stream_t s);
 /* Deferred form: egm_conv_wgrad with dw == NULL writes only the partial slabs (egm_conv_wgrad_slabs() of them) into the
- * workspace; egm_wgrad_reduce_multi() then finishes MANY convolutions in one launch.  table_dev: device array of 56-byte
- * entries {const float* slab; float* dw; int nslab, taps, CoutP, CinP, CoutR, CinR, groups, accumulate, chunk0, pad;};
- * chunks per entry = ceil(taps*CoutP*CinP / egm_wgrad_reduce_chunk()), chunk0 / total_chunks as for egm_conv_pack_multi. */
+ * workspace; egm_wgrad_reduce_multi() then finishes MANY convolutions in one launch.  table_dev: device array of 72-byte
+ * entries {const float* slab; float* dw; float* dw2; float* dw3; int nslab, taps, CoutP, CinP, CoutR, CinR, groups, accumulate,
+ * chunk0, mode;}; chunks per entry = ceil(taps*CoutP*CinP / egm_wgrad_reduce_chunk()), chunk0 / total_chunks as for
+ * egm_conv_pack_multi.  mode & 3 = where a reduced element goes:
+ *   0  dw, the fp32 OIHW gradient (dw2, dw3 unused);
+ *   1  fold2: the reduced [CoutR][CinR] 1x1 gradient belongs to a weight derived as W[:, :K] + W[:, K:]; dw is the gradient of the
+ *      real [CoutR][2*CinR] parameter and receives every element twice, at [co][ci] and [co][CinR + ci] (egm_fold2_bwd's result);
+ *   2  merge357: the reduced 7x7 gradient (taps = 49, groups = 1) goes to dw (the 7x7 parameter's gradient) and, where the tap lies in
+ *      the centre 5x5 / 3x3 window, to dw2 / dw3 (the 5x5 / 3x3 parameters', egm_merge357_bwd's result); a NULL destination is skipped.
+ * accumulate applies to mode 0 only.  mode & 4: the entry is summed in the order of egm_wgrad_reduce's kernel for many slabs of a
+ * small gradient (egm_wgrad_reduce_is_wide() tells when egm_wgrad_reduce takes it) and takes chunks of egm_wgrad_reduce_chunk_wide()
+ * elements; without the bit the order is that of egm_wgrad_reduce's other kernel.  Each slab element is read once either way. */
 int egm_conv_wgrad_kernel_name(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW, int dil, char* buf, int buflen);   /* as egm_conv_kernel_name */
 /* egm_conv_wgrad's slab-only form (dw == NULL) for 1..EGM_WGRAD_MULTI_MAX independent convolutions in one call: members that take the
  * same kernel instantiation (egm_conv_wgrad_kernel_name) run as ONE launch.  Arguments per member as egm_conv_wgrad's; slabs =
@@ -145,6 +160,8 @@ int egm_conv_wgrad_slabs(int dtype, int N, int H, int W, int Cin, int Cout, int 
 int egm_wgrad_reduce(const float* slabs, float* dw_oihw_f32, int nslab, int taps, int CoutP, int CinP, int CoutR, int CinR, int groups,
                      int accumulate, egm_stream_t s);
 int egm_wgrad_reduce_chunk(void);   /* packed elements reduced by one workgroup of egm_wgrad_reduce_multi */
+int egm_wgrad_reduce_chunk_wide(void);   /* ... of an entry with mode & 4 */
+int egm_wgrad_reduce_is_wide(int nslab, int taps, int CoutP, int CinP);   /* 1 when egm_wgrad_reduce sums these slabs with its many-slab kernel */
 int egm_wgrad_reduce_multi(const void* table_dev, int n, long long total_chunks, egm_stream_t s);
 /* Depthwise 3x3 (RecursiveGatedAttention.dwconv, src/EGM-UNet.py:507-509): y = (dw3x3(x, w) + b) * scale.
  * w fp32 [C][1][3][3], b fp32 [C], scale fp32 [1] (device). */
