@@ -80,18 +80,15 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__
         float v[CB], mx = -INFINITY;
 #pragma unroll
         for (int c = 0; c < CB; ++c) if (c < C) { v[c] = lg[c * HW + p]; mx = fmaxf(mx, v[c]); }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < CB; ++c) if (c < C) { v[c] = expf(v[c] - mx); se += v[c]; }
-        const float inv = 1.f / se;
         const long long t = tg[p];
         const bool valid = (t != ignore_index);
+        float se = 0.f, dt = 0.f;              // dt = x_t - max: the log-softmax form, finite at any margin (exp(dt) underflows past ~104)
+#pragma unroll
+        for (int c = 0; c < CB; ++c) if (c < C) { const float d = v[c] - mx; dt = (c == (int)t) ? d : dt; v[c] = expf(d); se += v[c]; }
+        const float inv = 1.f / se;
         if (valid && t >= 0 && t < C) {
             const float w = weight ? weight[t] : 1.f;
-            float pt = 0.f;
-#pragma unroll
-            for (int c = 0; c < CB; ++c) if (c < C && c == (int)t) pt = v[c] * inv;
-            acc[0] += -w * logf(pt);
+            acc[0] += -w * (dt - logf(se));
             acc[1] += w;
         }
         if (dice) {
@@ -345,7 +342,7 @@ extern "C" long long egm_loss_workspace(int N, int C) {
     return ((long long)N * kLossBlocksPerImage * (5 + 3 * C) + (long long)N * 3 * C + 1 + 8) * (long long)sizeof(float);
 }
 
-// workspace layout (floats): partials [N][64][K] | stats [N][3][C] + ce_den
+// workspace layout (floats): partials [N][kLossBlocksPerImage = 256][K] | stats [N][3][C] + ce_den
 extern "C" int egm_loss_fwd(const float* logits, const long long* target, const float* class_weight, int N, int C, int H, int W,
                             long long ignore_index, int dice, float* loss6, float* workspace, unsigned char* signs, egm_stream_t s) {
     EGM_REQUIRE(logits && target && loss6 && workspace, "loss_fwd: null pointer");
