@@ -92,6 +92,13 @@ __device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
 #ifndef EGM_LOAD_MODE
 #define EGM_LOAD_MODE 0            // 2: non-temporal 16-byte loads in the bf16 streaming kernels (A/B builds, profiles/r04_ab_runs.md)
 #endif
+// 8 bf16 held in a 16-byte register vector -> floats
+__device__ __forceinline__ void load8(uint4 a, float (&v)[8]) {
+    v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
+    v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
+    v[4] = __uint_as_float(a.z << 16); v[5] = __uint_as_float(a.z & 0xffff0000u);
+    v[6] = __uint_as_float(a.w << 16); v[7] = __uint_as_float(a.w & 0xffff0000u);
+}
 __device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) {
 #if EGM_LOAD_MODE == 2
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_;
@@ -100,10 +107,7 @@ __device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) {
 #else
     uint4 a = *reinterpret_cast<const uint4*>(p);
 #endif
-    v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
-    v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
-    v[4] = __uint_as_float(a.z << 16); v[5] = __uint_as_float(a.z & 0xffff0000u);
-    v[6] = __uint_as_float(a.w << 16); v[7] = __uint_as_float(a.w & 0xffff0000u);
+    load8(a, v);
 }
 // One 16-byte store of a kernel's output tensor, with a cache policy.  A plain store leaves its line dirty in the XCD's L2 until it is
 // evicted or written back when the kernel ends (a serial tail of up to the L2's 4 MB per XCD behind every streaming kernel); the next

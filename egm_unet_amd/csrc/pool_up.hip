@@ -4,6 +4,7 @@
 //   Up.forward (upsample, pad, cat)         src/EGM-UNet.py:937-947, src/unet.py:39-49
 //   RecursiveGatedAttention.dwconv * scale  src/EGM-UNet.py:507-509,527
 #include "common.h"
+#include "lerp.h"
 
 namespace {
 
@@ -112,20 +113,7 @@ __global__ void zero_tail_kernel(T* __restrict__ dx, int lddx, int N, int H, int
     }
 }
 
-// ---- bilinear x2 (align_corners=True) + zero pad + concat after the skip tensor ---------------------
-struct Lerp { int i0, i1; float w0, w1; };
-__device__ __forceinline__ Lerp lerp_coord(int dst, int in_size, int out_size) {
-    // torch upsample_bilinear2d, align_corners=True: scale = (in-1)/(out-1) (0 when out == 1), all in fp32
-    const float scale = out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-    const float src = scale * (float)dst;
-    Lerp l;
-    l.i0 = (int)src;
-    l.i1 = l.i0 + (l.i0 < in_size - 1 ? 1 : 0);
-    l.w1 = src - (float)l.i0;
-    l.w0 = 1.f - l.w1;
-    return l;
-}
-
+// ---- bilinear x2 (align_corners=True) + zero pad + concat after the skip tensor (Lerp, lerp_coord: lerp.h) ---------------------
 template <typename T>
 __global__ void upcat_fwd_kernel(const T* __restrict__ skip, int lds, const T* __restrict__ low, int ldl, T* __restrict__ out,
                                  int ldo, int N, int Hs, int Ws, int Cs, int Hl, int Wl, int Cl) {
@@ -144,7 +132,7 @@ __global__ void upcat_fwd_kernel(const T* __restrict__ skip, int lds, const T* _
             const int uy = y - py, ux = x - px, c = (cv - ncs) * 8;
             zero8(v);
             if (uy >= 0 && uy < Hu && ux >= 0 && ux < Wu) {
-                const Lerp ly = lerp_coord(uy, Hl, Hu), lx = lerp_coord(ux, Wl, Wu);
+                const Lerp ly = lerp_coord<true>(uy, Hl, Hu), lx = lerp_coord<true>(ux, Wl, Wu);
                 const T* b = low + (long long)n * Hl * Wl * ldl + c;
                 float a[8];
                 load8(b + ((long long)ly.i0 * Wl + lx.i0) * ldl, a);

@@ -221,9 +221,11 @@ class EdgeEnhancedGRFB(nn.Module):
             return None
         return ops.cat_slots(N, H, W, [C, i2, i2, i2], dtype, device)
 
-    def forward(self, x, out=None, cat=None, pool=False):
-        """pool=True: -> (result, maxpool2(result)) with the pool fused into the target gate (ops.gate3_pool) where that applies."""
-        edge, x_e2, x_cat, x_sc = ops.fork_highpass3(x, 3)       # highpass3(x) + three aliases: backward sums all four gradients in one pass
+    def forward(self, x, out=None, cat=None, pool=False, x_slot=None):
+        """pool=True: -> (result, maxpool2(result)) with the pool fused into the target gate (ops.gate3_pool) where that applies.
+        x: NHWC tensor, or an ops.Lazy that feeds nothing else: the entry high-pass then writes the tensor itself, into x_slot (view 0
+        of `cat`) when given."""
+        edge, x_e2, x_cat, x_sc = ops.fork_highpass3(x, 3, out=x_slot)   # highpass3(x) + three aliases: backward sums all four gradients in one pass
         xe = self.edge_enhancer(None, x_e2, edge=edge)
         # the three branch tails write straight into their slots of the concat destination (no copy, one tensor write less each)
         N, H, W, C = x.shape
@@ -463,7 +465,11 @@ class DoubleConv1(nn.Sequential):
         grfb = self[6 + o]
         N, H, W = x.shape[0], x.shape[1], x.shape[2]
         cat = grfb.cat_buffer(N, H, W, x.dtype, x.device) if self[3 + o].out_channels == grfb.shortcut.conv.in_channels else None
-        x = ops.conv_bn_act(x, self[3 + o], self[4 + o], ACT_RELU, out=None if cat is None else cat[1][0])
+        slot = None if cat is None else cat[1][0]
+        if ops.bn_hp_fusable(x.dtype):
+            # ... by the GRFB's entry high-pass, which forms the edge map from the tile it has just written (ops.fork_highpass3)
+            return grfb(ops.conv_bn_act(x, self[3 + o], self[4 + o], ACT_RELU, lazy="force"), out, cat, pool=pool, x_slot=slot)
+        x = ops.conv_bn_act(x, self[3 + o], self[4 + o], ACT_RELU, out=slot)
         return grfb(x, out, cat, pool=pool)
 
 
@@ -520,8 +526,10 @@ class GRFBUNet(_SegNetBase):
         if self.ddp_boundary is not None:                 # graph.GraphedTrainStep splits backward at the encoder -> decoder tensors
             self.ddp_boundary.extend([x1s, x2s, x3s, x4s, d4])
         x5 = self.attn1(d4)
-        y = self.up1(x5, x4s, bufs[3])
-        y = self.up2(y, x3s, bufs[2])
-        y = self.up3(y, x2s, bufs[1])
+        # up1..up3 feed only the next Up's upsample, which applies their last BatchNorm+ReLU itself (ops.upcat of a Lazy)
+        lazy_up = "force" if self.bilinear and ops.bn_up_fusable(x5.dtype) else False
+        y = self.up1(x5, x4s, bufs[3], lazy=lazy_up)
+        y = self.up2(y, x3s, bufs[2], lazy=lazy_up)
+        y = self.up3(y, x2s, bufs[1], lazy=lazy_up)
         y = self.up4(y, x1s, bufs[0], lazy="force" if ops.fuse_cls() else False)   # the 1x1 classifier applies up4's last BatchNorm+ReLU itself
         return self._exit(self.out_conv(y, sole_consumer=True))

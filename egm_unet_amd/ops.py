@@ -1746,58 +1746,103 @@ def fork_maxpool2(x):
     return _ForkMaxPool2.apply(x)
 
 
+fuse_bn_up = _Switch("EGM_FUSE_BN_UP", "1",
+                     """Get / set whether the bilinear upsample of an Up block applies the BatchNorm+ReLU of the Up block in front itself
+                     (bf16; egm_bn_act_upcat_fwd), so that block's low-resolution output is never written (tests compare both ways).""")
+
+
+def _upcat_forward(ctx, skip, low, catbuf, low_bn=None):
+    """low_bn = (coef, act): `low` is a Lazy's stand-in and the kernel applies its BatchNorm + activation on the way"""
+    skip, lds = _nhwc(skip)
+    low, ldl = _nhwc(low)
+    N, Hs, Ws, Cs = skip.shape
+    _, Hl, Wl, Cl = low.shape
+    inplace = False
+    if catbuf is not None:
+        # the skip tensor was produced straight into the first Cs channels of the concat destination: only the upsampled half is
+        # written (a tensor write costs about twice a read on this part, and the skip copy was two thirds of this kernel's bytes)
+        cb = catbuf[0]
+        inplace = (cb.is_contiguous() and tuple(cb.shape) == (N, Hs, Ws, Cs + Cl) and cb.dtype == skip.dtype
+                   and cb.data_ptr() == skip.data_ptr() and lds == Cs + Cl)
+    out = cb if inplace else torch.empty((N, Hs, Ws, Cs + Cl), dtype=skip.dtype, device=skip.device)
+    src = None if inplace else ptr(skip)
+    if low_bn is None:
+        lib().call("egm_upcat_fwd", dtype_code(skip.dtype), src, lds, ptr(low), ldl, ptr(out), Cs + Cl, N, Hs, Ws, Cs, Hl, Wl, Cl, stream())
+    else:
+        coef, act = low_bn
+        lib().call("egm_bn_act_upcat_fwd", dtype_code(skip.dtype), src, lds, ptr(low), ldl, ptr(coef[0]), ptr(coef[1]), act, ptr(out), Cs + Cl,
+                   N, Hs, Ws, Cs, Hl, Wl, Cl, stream())
+    ctx.shape = (N, Hs, Ws, Cs, Hl, Wl, Cl)
+    return out
+
+
+def _upcat_backward(ctx, g):
+    """-> (gskip, glow); inputs 0 and 1 of the node are skip and low (or low's stand-in)"""
+    N, Hs, Ws, Cs, Hl, Wl, Cl = ctx.shape
+    pend = _take_dz(g)
+    gskip = glow = None
+    if pend is not None:                           # the conv behind the concat wrote the two halves of its gradient as dense tensors
+        _, ga, gb = pend[1]
+        if ctx.needs_input_grad[0]:
+            gskip = ga
+        if ctx.needs_input_grad[1]:
+            glow = torch.empty((N, Hl, Wl, Cl), dtype=gb.dtype, device=gb.device)
+            lib().call("egm_upcat_bwd_low", dtype_code(gb.dtype), ptr(gb), Cl, ptr(glow), Cl, N, Hs, Ws, 0, Hl, Wl, Cl, stream())
+        return gskip, glow
+    g, ldo = _nhwc(g)
+    if ctx.needs_input_grad[0]:
+        gskip = g[..., :Cs]                        # a view: consumers take (ptr, ld)
+    if ctx.needs_input_grad[1]:
+        glow = torch.empty((N, Hl, Wl, Cl), dtype=g.dtype, device=g.device)
+        lib().call("egm_upcat_bwd_low", dtype_code(g.dtype), ptr(g), ldo, ptr(glow), Cl, N, Hs, Ws, Cs, Hl, Wl, Cl, stream())
+    return gskip, glow
+
+
 class _UpCat(Function):
     """cat([skip, pad(bilinear_x2(low))], channel)"""
 
     @staticmethod
     def forward(ctx, skip, low, catbuf=None):
-        skip, lds = _nhwc(skip)
-        low, ldl = _nhwc(low)
-        N, Hs, Ws, Cs = skip.shape
-        _, Hl, Wl, Cl = low.shape
-        inplace = False
-        if catbuf is not None:
-            # the skip tensor was produced straight into the first Cs channels of the concat destination: only the upsampled half is
-            # written (a tensor write costs about twice a read on this part, and the skip copy was two thirds of this kernel's bytes)
-            cb = catbuf[0]
-            inplace = (cb.is_contiguous() and tuple(cb.shape) == (N, Hs, Ws, Cs + Cl) and cb.dtype == skip.dtype
-                       and cb.data_ptr() == skip.data_ptr() and lds == Cs + Cl)
-        if inplace:
-            out = cb
-            lib().call("egm_upcat_fwd", dtype_code(skip.dtype), None, lds, ptr(low), ldl, ptr(out), Cs + Cl, N, Hs, Ws, Cs,
-                       Hl, Wl, Cl, stream())
-        else:
-            out = torch.empty((N, Hs, Ws, Cs + Cl), dtype=skip.dtype, device=skip.device)
-            lib().call("egm_upcat_fwd", dtype_code(skip.dtype), ptr(skip), lds, ptr(low), ldl, ptr(out), Cs + Cl, N, Hs, Ws, Cs,
-                       Hl, Wl, Cl, stream())
-        ctx.shape = (N, Hs, Ws, Cs, Hl, Wl, Cl)
-        return out
+        return _upcat_forward(ctx, skip, low, catbuf)
 
     @staticmethod
     def backward(ctx, g):
-        N, Hs, Ws, Cs, Hl, Wl, Cl = ctx.shape
-        pend = _take_dz(g)
-        gskip = glow = None
-        if pend is not None:                           # the conv behind the concat wrote the two halves of its gradient as dense tensors
-            _, ga, gb = pend[1]
-            if ctx.needs_input_grad[0]:
-                gskip = ga
-            if ctx.needs_input_grad[1]:
-                glow = torch.empty((N, Hl, Wl, Cl), dtype=gb.dtype, device=gb.device)
-                lib().call("egm_upcat_bwd_low", dtype_code(gb.dtype), ptr(gb), Cl, ptr(glow), Cl, N, Hs, Ws, 0, Hl, Wl, Cl, stream())
-            return gskip, glow, None
-        g, ldo = _nhwc(g)
-        if ctx.needs_input_grad[0]:
-            gskip = g[..., :Cs]                        # a view: consumers take (ptr, ld)
-        if ctx.needs_input_grad[1]:
-            glow = torch.empty((N, Hl, Wl, Cl), dtype=g.dtype, device=g.device)
-            lib().call("egm_upcat_bwd_low", dtype_code(g.dtype), ptr(g), ldo, ptr(glow), Cl, N, Hs, Ws, Cs, Hl, Wl, Cl, stream())
-        return gskip, glow, None
+        return _upcat_backward(ctx, g) + (None,)
+
+
+class _UpCatBn(Function):
+    """_UpCat of low = act(scale*y + shift) given as a Lazy's (y, coef, act): the upsample applies the BatchNorm itself
+    (egm_bn_act_upcat_fwd) and the low-resolution tensor is never written.  backward is _UpCat's: the gradient of the stand-in y is
+    dL/dlow (see Lazy)."""
+
+    @staticmethod
+    def forward(ctx, skip, y, coef, act, catbuf=None):
+        return _upcat_forward(ctx, skip, y, catbuf, (coef, act))
+
+    @staticmethod
+    def backward(ctx, g):
+        return _upcat_backward(ctx, g) + (None, None, None)
+
+
+def _bn_up_ok(dtype):
+    """the fused upsample takes this activation type (switch on, bf16): what ops.upcat itself decides on"""
+    return fuse_bn_up.on and dtype == torch.bfloat16
+
+
+def bn_up_fusable(dtype):
+    """True when an Up block may hand its result to the next Up's ops.upcat as a Lazy (_bn_up_ok and BatchNorm not folded)."""
+    return _bn_up_ok(dtype) and _fold_packs() is None
 
 
 def upcat(skip, low, catbuf=None):
-    """catbuf: the concat destination whose first channels ARE `skip` (see cat_slots), or None for a fresh tensor + copy."""
-    out = _UpCat.apply(skip, low, None if catbuf is None else [catbuf])
+    """catbuf: the concat destination whose first channels ARE `skip` (see cat_slots), or None for a fresh tensor + copy.
+    low: NHWC tensor, or a Lazy this is the only consumer of."""
+    if isinstance(low, Lazy) and not (_bn_up_ok(low.dtype) and skip.dtype == low.dtype):
+        low = low.materialize()
+    if isinstance(low, Lazy):
+        out = _UpCatBn.apply(skip, low.y, low.coef, low.act, None if catbuf is None else [catbuf])
+    else:
+        out = _UpCat.apply(skip, low, None if catbuf is None else [catbuf])
     # a hint for the conv that consumes the concatenation (its only consumer in Up.forward, src/EGM-UNet.py:947-949): the gradient may come
     # back as two dense tensors, split at this channel (ops._conv_dgrad).  Lost -- harmlessly -- if the tensor passes through anything else.
     out._egm_split = skip.shape[3]
@@ -1975,24 +2020,71 @@ class _ForkHighpass(Function):
 
     @staticmethod
     def backward(ctx, ghp, *gs):
-        gs = [g for g in gs if g is not None]
-        if ghp is None:
-            return (_Fork.backward(ctx, *gs)[0] if gs else None), None
-        if not gs:
-            return _hp(ghp), None
-        while len(gs) > 3:                                    # more than three other consumers: pre-sum the tail
-            gs = gs[:2] + [_Fork.backward(ctx, *gs[2:])[0]]
-        a, lda = _nhwc(ghp)
-        N, H, W, C = a.shape
-        ts = [_nhwc(t) for t in gs] + [(None, 0)] * (3 - len(gs))
-        out = torch.empty(a.shape, dtype=a.dtype, device=a.device)
-        lib().call("egm_sum4_hp", dtype_code(a.dtype), ptr(a), lda, ptr(ts[0][0]), ts[0][1], ptr(ts[1][0]), ts[1][1], ptr(ts[2][0]), ts[2][1],
-                   ptr(out), C, N, H, W, C, stream())
-        return out, None
+        return _fork_highpass_backward(ctx, ghp, gs), None
 
 
-def fork_highpass3(x, n):
-    """(highpass3(x), alias_1, ..., alias_n): the edge extractor of EdgeAwareFeatureEnhancer together with x's other consumers."""
+def _fork_highpass_backward(ctx, ghp, gs):
+    """-> highpass3(ghp) + sum(gs): the gradient of the forked tensor"""
+    gs = [g for g in gs if g is not None]
+    if ghp is None:
+        return _Fork.backward(ctx, *gs)[0] if gs else None
+    if not gs:
+        return _hp(ghp)
+    while len(gs) > 3:                                    # more than three other consumers: pre-sum the tail
+        gs = gs[:2] + [_Fork.backward(ctx, *gs[2:])[0]]
+    a, lda = _nhwc(ghp)
+    N, H, W, C = a.shape
+    ts = [_nhwc(t) for t in gs] + [(None, 0)] * (3 - len(gs))
+    out = torch.empty(a.shape, dtype=a.dtype, device=a.device)
+    lib().call("egm_sum4_hp", dtype_code(a.dtype), ptr(a), lda, ptr(ts[0][0]), ts[0][1], ptr(ts[1][0]), ts[1][1], ptr(ts[2][0]), ts[2][1],
+               ptr(out), C, N, H, W, C, stream())
+    return out
+
+
+fuse_bn_hp = _Switch("EGM_FUSE_BN_HP", "1",
+                     """Get / set whether the EdgeEnhancedGRFB's entry high-pass applies the BatchNorm+ReLU of the DoubleConv1 conv in front
+                     itself (bf16; egm_bn_act_hp_fwd): the tensor is written and its edge map formed in one pass (tests compare both ways).""")
+
+
+class _ForkHighpassBn(Function):
+    """_ForkHighpass of z = act(scale*y + shift) given as a Lazy's (y, coef, act): one pass writes z (into the destination view when
+    given) and highpass3(z) (egm_bn_act_hp_fwd).  backward is _ForkHighpass's: the gradient of the stand-in y is dL/dz (see Lazy)."""
+
+    @staticmethod
+    def forward(ctx, y, coef, act, n, out_slot):
+        y, ldy = _nhwc(y)
+        N, H, W, C = y.shape
+        z, ldz = _slot_or_new(out_slot, (N, H, W, C), y.dtype, y.device)
+        edge = torch.empty((N, H, W, C), dtype=y.dtype, device=y.device)
+        lib().call("egm_bn_act_hp_fwd", dtype_code(y.dtype), ptr(y), ldy, ptr(coef[0]), ptr(coef[1]), act, ptr(z), ldz, ptr(edge), C,
+                   N, H, W, C, stream())
+        return (edge,) + tuple(z.view_as(z) for _ in range(n))
+
+    @staticmethod
+    def backward(ctx, ghp, *gs):
+        return _fork_highpass_backward(ctx, ghp, gs), None, None, None, None
+
+
+def _bn_hp_ok(dtype):
+    """the fused high-pass takes this activation type (switch on, bf16): what ops.fork_highpass3 itself decides on"""
+    return fuse_bn_hp.on and dtype == torch.bfloat16
+
+
+def bn_hp_fusable(dtype):
+    """True when DoubleConv1 may hand its result to the GRFB's ops.fork_highpass3 as a Lazy (_bn_hp_ok and BatchNorm not folded)."""
+    return _bn_hp_ok(dtype) and _fold_packs() is None
+
+
+def fork_highpass3(x, n, out=None):
+    """(highpass3(x), alias_1, ..., alias_n): the edge extractor of EdgeAwareFeatureEnhancer together with x's other consumers.
+    x: NHWC tensor, or a Lazy this is the only consumer of; out: optional destination view (a concat slot) the tensor of a Lazy is
+    written into -- the aliases then live there."""
+    if isinstance(x, Lazy):
+        if _bn_hp_ok(x.dtype):
+            return _ForkHighpassBn.apply(x.y, x.coef, x.act, n, None if out is None else [out])
+        x = x.materialize(out)
+    elif out is not None:
+        x = materialize(x, out)
     return _ForkHighpass.apply(x, n)
 
 

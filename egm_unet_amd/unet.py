@@ -64,10 +64,11 @@ class Up(nn.Module):
             self.conv = DoubleConv(in_channels, out_channels)
 
     def forward(self, x1, x2, catbuf=None, lazy=False):
-        """x1: low-res, x2: skip (both NHWC); catbuf: concat destination that already holds x2; lazy: see DoubleConv.forward"""
+        """x1: low-res, x2: skip (both NHWC); catbuf: concat destination that already holds x2; lazy: see DoubleConv.forward.
+        x1 may be the ops.Lazy of the Up block in front (which then feeds nothing else): the upsample applies its BatchNorm+ReLU."""
         if self.bilinear:
             return self.conv(ops.upcat(x2, x1, catbuf), lazy=lazy)
-        x1 = ops.conv_transpose2x2(x1, self.up, (x2.shape[1], x2.shape[2]))
+        x1 = ops.conv_transpose2x2(ops.materialize(x1), self.up, (x2.shape[1], x2.shape[2]))
         return self.conv(ops.cat_channels([x2, x1]), lazy=lazy)
 
 
@@ -163,8 +164,10 @@ class UNet(_SegNetBase):
             x5, x5d = ops.fork2(x5)                              # the decoder-side alias is the boundary tensor
             self.ddp_boundary.extend([x1s, x2s, x3s, x4s, x5d])
             x5 = x5d
-        y = self.up1(x5, x4s)
-        y = self.up2(y, x3s)
-        y = self.up3(y, x2s)
+        # up1..up3 feed only the next Up's upsample, which applies their last BatchNorm+ReLU itself (ops.upcat of a Lazy)
+        lazy_up = "force" if self.bilinear and ops.bn_up_fusable(x5.dtype) else False
+        y = self.up1(x5, x4s, lazy=lazy_up)
+        y = self.up2(y, x3s, lazy=lazy_up)
+        y = self.up3(y, x2s, lazy=lazy_up)
         y = self.up4(y, x1s, lazy="force" if ops.fuse_cls() else False)   # the 1x1 classifier applies up4's last BatchNorm+ReLU itself
         return self._exit(self.out_conv(y, sole_consumer=True))

@@ -331,6 +331,16 @@ int egm_gate3_pool_bwd(int dtype, const void* gskip, int ldgs, const void* gpool
  * skip == NULL: the skip channels were produced straight into out[..., :Cs] by their own kernel; only the Cl upsampled channels are written. */
 int egm_upcat_fwd(int dtype, const void* skip, int lds, const void* low, int ldl, void* out, int ldo, int N, int Hs, int Ws,
                   int Cs, int Hl, int Wl, int Cl, egm_stream_t s);
+/* BatchNorm apply fused into the stencil behind it (csrc/bn_stencil_fused.hip; bf16 only, anything else is EGM_ERR_ARG: callers keep
+ * the two-kernel path).  Bit-identical to the pairs they replace.
+ *   egm_bn_act_hp_fwd   : z = act(y*scale + shift) written to z (ld = ldz >= C: may be a channel slot of a wider buffer) AND
+ *                         edge = z - avgpool3x3(z) (zero pad, divisor 9)                             (egm_bn_act_fwd + egm_highpass3)
+ *   egm_bn_act_upcat_fwd: egm_upcat_fwd of low = act(y_low*scale + shift), which is never written   (egm_bn_act_fwd + egm_upcat_fwd);
+ *                         scale, shift, act belong to `low`; skip == NULL as for egm_upcat_fwd */
+int egm_bn_act_hp_fwd(int dtype, const void* y, int ldy, const float* scale, const float* shift, int act, void* z, int ldz,
+                      void* edge, int lde, int N, int H, int W, int C, egm_stream_t s);
+int egm_bn_act_upcat_fwd(int dtype, const void* skip, int lds, const void* low, int ldl, const float* scale, const float* shift,
+                         int act, void* out, int ldo, int N, int Hs, int Ws, int Cs, int Hl, int Wl, int Cl, egm_stream_t s);
 /* dlow = transposed bilinear of dout[..., Cs:Cs+Cl]; (dskip is dout[..., :Cs], a view). */
 int egm_upcat_bwd_low(int dtype, const void* dout, int ldo, void* dlow, int ldl, int N, int Hs, int Ws, int Cs, int Hl,
                       int Wl, int Cl, egm_stream_t s);
