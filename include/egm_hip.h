@@ -1241,6 +1241,63 @@ long long egm_rank_workspace(int S, long long L);
 int egm_rank_scores(const unsigned int* keys, const unsigned int* vals, int S, long long L, void* workspace, unsigned long long* out_u64,
                     double* out_f64, unsigned int* skeys_out, unsigned int* tp_out, egm_stream_t s);
 
+/* ---- CLIPSeg training batches: object crop, resize, jitter (csrc/clipseg_batch.hip, egm_unet_amd/clipseg_data.py)
+ * B ragged uint8 photos [H_b][W_b][3] with masks [H_b][W_b] (nonzero = object) -> img fp32 [B][3][S][S], seg fp32 [B][1][S][S] of 0 / 1
+ * and choice int32 [B][3] = (off_y, off_x, exceed), the sample recipe of datasets/phrasecut.py:66-111, 263-311.  Each entry point below
+ * is ONE launch whatever B (egm_color_jitter_f32 with stages == 3: two), none waits for the device, none uses atomics.
+ * table_dev: DEVICE memory, B rows of egm_clipseg_batch_desc followed by the int32 / fp32 tables the rows point to; every *_off of a
+ *   row counts 4-byte elements from table_dev itself (one blob, one upload), except prof_off, which counts int32 elements of profile_dev.
+ *   The crop window is win_h x win_w: m x m with m = min(H, W) sliding along axis 1 (x) when W > H, else along axis 0 (y); axis -1:
+ *   no object crop, the window is the photo (win_h = H, win_w = W) and the choice is (0, 0, 0).  With L the photo's side along the axis:
+ *     cand_off  int32 [ncand]   the candidate offsets along the axis, in the order they were drawn
+ *     prof_off  int32 [L] line counts, then [L + 1] their exclusive prefix sums (written by egm_clipseg_choose)
+ *     yi_off int32 [S][2], yl_off fp32 [S]: per output row the two source rows (i0, i1) RELATIVE TO THE WINDOW'S ORIGIN and the weight l1
+ *       of i1 (align_corners=True: scale = (float)(win - 1) / (float)(S - 1), src = scale * dst, i0 = (int)src, i1 = min(i0 + 1, win - 1),
+ *       l1 = src - i0, all fp32); xi_off, xl_off: the same for the columns
+ *     ynn_off, xnn_off int32 [S]: the mask's nearest source row / column, min((int)floor(dst * ((float)win / (float)S)), win - 1)
+ * egm_mask_profile_u8: profile_dev[prof_off + i] = the number of nonzero mask bytes of line i of the axis (column i over all rows for
+ *   axis 1, row i over all columns for axis 0); rows with axis -1 are skipped.  max_units: the largest of ceil(W / 256) (axis 1) and
+ *   ceil(H / 4) (axis 0) over the batch, the work items of one image.
+ * egm_clipseg_choose: window sum of candidate c = prefix[o_c + m] - prefix[o_c] with o_c clamped into [0, L - m]; the first c with
+ *   sum > thresh is taken (exceed 0); if there is none, the c with the largest sum, the earliest on a tie (exceed 1).  choice_b3[b] =
+ *   (o, 0, exceed) for axis 0, (0, o, exceed) for axis 1, (0, 0, 0) for axis -1 or ncand <= 0 (profile_dev may then be NULL).
+ * egm_clipseg_batch_u8: choice_b3 is read on the DEVICE and clamped into [0, L - m].  Per output pixel and channel, from the four bytes
+ *   a, b (row i0; columns i0, i1), c, d (row i1) as floats: l0 = 1 - l1, top = lx0 a + lx1 b, bot = lx0 c + lx1 d, v = (ly0 top + ly1 bot)
+ *   / 255, one fp32 rounding per operation, no FMA.  seg = 1 where the mask byte at the nearest indices is nonzero and negative == 0, else 0.
+ *   order_dev == NULL (then factors_dev == NULL too): img = (v - mean_c) / std_c, finished.  Otherwise order_dev int32 [B][4] is a
+ *   permutation of the operations 0 brightness, 1 contrast, 2 saturation, 3 hue and factors_dev fp32 [B][8] = (r_0 .. r_3, q_0 .. q_3)
+ *   with r = (float)f, q = (float)(1.0 - f) (r_3 = the hue shift): the operations in front of the contrast are applied, img receives the
+ *   values UN-normalised and partials[b][t] (double [B][egm_color_jitter_tiles(S, S)]) the gray sum of tile t of 1024 consecutive pixels;
+ *   egm_color_jitter_f32 with stages == 2 finishes the batch.  mean3 / std3 are HOST pointers.
+ * egm_color_jitter_f32: torchvision's ColorJitter on fp32 [B][3][H][W] in [0, 1], tensor formulas, one fp32 rounding per operation:
+ *   gray g = (0.2989 R + 0.587 G) + 0.114 B; brightness clamp(r x, 0, 1); saturation clamp(r x + q g, 0, 1); contrast clamp(r x + q mean,
+ *   0, 1), mean = the image's mean of g at that point of the chain: per tile ((g0 + g1) + g2) + g3 per lane of 4 consecutive pixels in
+ *   double, the xor butterfly 32, 16 .. 1 over the 64 lanes, the 4 waves in ascending order; the tiles in ascending order; divided by
+ *   H W in double and rounded once; hue: _rgb2hsv, h = remainder(h + r_3, 1), _hsv2rgb (tests/clipseg_batch_oracle.py restates all of it).
+ *   stages & 1: x -> out through the operations in front of the contrast, and the partials (x == out allowed); stages & 2: the contrast
+ *   and what follows in place on out, then (x - mean_c) / std_c when mean3_host / std3_host (HOST pointers, both or neither) are given.
+ * Limits: B <= 65535; H W 3 < 2^31 per photo (the host plan checks it); B 3 S S < 2^31; 2 <= S <= 32767; any number of lines and
+ *   candidates that fits the tables (a slide axis of 8192 lines with 1000 candidates is tested).  Bad scalars and null pointers return
+ *   EGM_ERR_ARG with a message before any launch.  The kernels clamp the device-chosen offset, every candidate, every tap and nearest
+ *   index into its window and the window into the photo, and read an operation id & 3: a wrong row gives wrong pixels, never an access
+ *   outside the buffers it names. */
+typedef struct egm_clipseg_batch_desc {
+    const void* img;            /* uint8 [H][W][3] */
+    const void* mask;           /* uint8 [H][W] */
+    int H, W, win_h, win_w;
+    int axis, ncand, thresh, negative;
+    int cand_off, prof_off;
+    int yi_off, yl_off, xi_off, xl_off, ynn_off, xnn_off;
+} egm_clipseg_batch_desc;       /* 80 bytes */
+int egm_color_jitter_tiles(int H, int W);
+int egm_mask_profile_u8(const egm_clipseg_batch_desc* table_dev, int B, int max_units, int* profile_dev, egm_stream_t s);
+int egm_clipseg_choose(const egm_clipseg_batch_desc* table_dev, int B, int* profile_dev, int* choice_b3, egm_stream_t s);
+int egm_clipseg_batch_u8(const egm_clipseg_batch_desc* table_dev, int B, int S, const int* choice_b3, const int* order_dev,
+                         const float* factors_dev, float* out_img_b3ss, float* out_seg_b1ss, double* partials,
+                         const float* mean3_host, const float* std3_host, egm_stream_t s);
+int egm_color_jitter_f32(const float* x_b3hw, float* out_b3hw, int B, int H, int W, const int* order_dev, const float* factors_dev,
+                         double* partials, const float* mean3_host, const float* std3_host, int stages, egm_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
