@@ -177,23 +177,23 @@ int egm_conv_tile_launch(const void* x, int ldx, const void* wf, const float* bi
     p.tiles_y = egm_cdiv(H, rows); p.tiles_x = egm_cdiv(W, TW); p.npt = N * p.tiles_y * p.tiles_x; p.nct = nct; p.G = G;
     EGM_REQUIRE((long long)(rows + 2) * W * ldx < (1LL << 31), "conv3x3_tile: halo window offsets exceed 32 bits");
     hipStream_t st = (hipStream_t)s;
-    // configurations 0..3, the ones the default plan selects (>= 64-cout tiles), have an instantiation per activation
-    auto wide = [&](auto a) {
+    // every configuration has an instantiation per activation: egm_conv_fwd_act takes the plan of egm_conv_fwd under every tile mode,
+    // the 32-cout configurations of mode bit 2 included (test_gpu_conv_epilogue.py runs them)
+    auto any = [&](auto a) {
         constexpr int ACT = decltype(a)::value;
         switch (cfg) {
             case 0: return launch_tile<4, 2, 4, 2, 2, ACT>(p, st);
             case 1: return launch_tile<2, 2, 4, 2, 2, ACT>(p, st);
             case 2: return launch_tile<4, 2, 8, 1, 2, ACT>(p, st);
-            default: return launch_tile<2, 2, 8, 1, 2, ACT>(p, st);
+            case 3: return launch_tile<2, 2, 8, 1, 2, ACT>(p, st);
+            case 4: return launch_tile<4, 1, 8, 1, 2, ACT>(p, st);
+            default: return launch_tile<2, 1, 8, 1, 2, ACT>(p, st);
         }
     };
     if (act != EGM_ACT_NONE) {
-        // egm_conv_fwd_act: the 32-cout configurations are an A/B mode only
-        EGM_REQUIRE(cfg <= 3 && y2 == nullptr, "conv3x3_tile: no activation instantiation for tile configuration %d", cfg);
+        EGM_REQUIRE(y2 == nullptr, "conv3x3_tile: no activation with a split output");
         EGM_REQUIRE(act >= EGM_ACT_RELU && act <= EGM_ACT_SILU, "conv3x3_tile: unknown activation %d", act);
-        return egm_with_act(act, wide);
+        return egm_with_act(act, any);
     }
-    if (cfg == 4) return launch_tile<4, 1, 8, 1, 2>(p, st);
-    if (cfg >= 5) return launch_tile<2, 1, 8, 1, 2>(p, st);
-    return wide(std::integral_constant<int, EGM_ACT_NONE>());
+    return any(std::integral_constant<int, EGM_ACT_NONE>());
 }

@@ -7,7 +7,10 @@ integer far below 2^24, hence exact in fp32 in ANY summation order, tiling or K-
 reproduce the reference bit for bit, and one wrong, missing or repeated term anywhere is a mismatch.
 
 The reference is torch.nn.functional.conv2d and its autograd on the CPU, in float64 (float32 for the cases flagged `fast`, which
-test_conv_exact_cpu.py shows to agree with float64 exactly)."""
+test_conv_exact_cpu.py shows to agree with float64 exactly).
+
+The section 'the epilogue regimes' scales these operands so that the epilogue has work to do (values that are no bf16 numbers, a
+fractional bias, sigmoid / SiLU) and lists the merged launches; test_gpu_conv_epilogue.py and test_conv_epilogue_cpu.py use it."""
 import functools
 from collections import namedtuple
 
@@ -223,8 +226,11 @@ FWD_CASES = [
     # grouped: the block-diagonal pack (groups = 2; groups = Cin, 1 -> 2 per group)
     _c("bf16", (2, 16, 20, 8, 16, 3, 1), P + "<1, 3, 3, 2>", groups=2),
     _c("bf16", (2, 16, 20, 8, 16, 3, 1), P + "<1, 3, 3, 2>", groups=8, bias=True),
+    # second shapes for the merged launches of the LDS-free kernel (test_gpu_conv_epilogue.py): dilation 24 beside 12, another 64 -> 64
+    _c("bf16", (1, 30, 40, 32, 32, 3, 24), "conv_direct_kernel<1, false>", bias=True),
+    _c("bf16", (1, 35, 65, 64, 64, 3, 12), "conv_direct_kernel<2, false>", bias=True),
 ]
-FWD_CASES = [c._replace(seed=i) for i, c in enumerate(FWD_CASES)]
+FWD_CASES =[c._replace(seed=i) for i, c in enumerate(FWD_CASES)]
 
 
 def fwd_case(dtype, shape, mode=5, groups=1):
@@ -282,6 +288,9 @@ WGRAD_CASES = [
     _w("f32", (1, 30, 40, 16, 16, 3, 12), WG + "<float, 1>", bias=True),
     _w("f32", (1, 129, 130, 16, 16, 3, 12), WG + "<float, 3>"),
     _w("f32", (2, 16, 20, 8, 16, 3, 1), WG + "<float, 9>", groups=2),
+    # an uneven split for <9, 2> (96 tiles over 64 splits), a second <float, 7> shape: members of the merged launches
+    _w("bf16", (6, 57, 33, 32, 256, 3, 1), WS + "<9, 2>", uneven=True, fast=True),
+    _w("f32", (1, 13, 65, 16, 16, 7, 1), WG + "<float, 7>", bias=True),
 ]
 WGRAD_CASES = [c._replace(seed=100 + i) for i, c in enumerate(WGRAD_CASES)]
 
@@ -345,6 +354,184 @@ def dw_ref(x, w, b, dy, scale):
         if not _is_int(t) or float(t.abs().max()) > (VALUE_LIMIT if n in ("y", "dx") else SUM_LIMIT - 1):
             raise ValueError(f"depthwise {tuple(x.shape)} scale {scale}: {n} leaves the exact range")
     return ref
+
+
+# ---- the epilogue regimes (test_gpu_conv_epilogue.py, test_conv_epilogue_cpu.py) -----------------------------------------------
+# The convolution is linear: with x and dy multiplied by mx and w by mw (odd integers, so every operand stays a bf16 number) the exact
+# result is mx * mw times the reference of the table's case.  It stays an integer far below 2^24 -- still exact in fp32 in any order --
+# but most values now lie above 256, where bf16 holds only every 2nd, 4th, ... integer: the epilogue's ONE rounding to bf16 has work to
+# do, much of it on exact ties.
+def bf16_grid(t):
+    """-> (lo, hi) float64 tensors: the bf16 numbers next to t towards zero and away from it (lo == hi == t where t is one).  Plain
+    arithmetic on the binary exponent, no dtype conversion; for values inside bf16's normal range (and 0)."""
+    t = t.detach().double()
+    m, e = torch.frexp(t.abs())                                   # |t| = m * 2^e, m in [0.5, 1): the eight significant bits are m * 256
+    sg = torch.sign(t)
+    return sg * torch.ldexp(torch.floor(m * 256), e - 8), sg * torch.ldexp(torch.ceil(m * 256), e - 8)
+
+
+def round_bf16(t, how="rne"):
+    """t (float64) rounded to a bf16 number, in float64.  how: 'rne' to nearest, ties to the even significand (what the kernels must
+    do) | 'trunc' towards zero | 'away' to nearest, ties away from zero."""
+    t = t.detach().double()
+    lo, hi = bf16_grid(t)
+    if how == "trunc":
+        return lo
+    dl, dh = (t - lo).abs(), (hi - t).abs()
+    if how == "away":
+        return torch.where(dl < dh, lo, hi)
+    m, _ = torch.frexp(lo.abs())
+    lo_even = (m * 256) % 2 == 0                                  # lo's significand as an integer in [128, 256); 0 counts as even
+    return torch.where(dl < dh, lo, torch.where(dl > dh, hi, torch.where(lo_even, lo, hi)))
+
+
+def n_inexact(t):
+    """How many elements of t are no bf16 numbers."""
+    lo, _ = bf16_grid(t)
+    return int((lo != t.double()).sum())
+
+
+def store_round(c, t):
+    """What a kernel of the case's dtype must store for the exact fp32 value t: rne to bf16, or t itself (fp32 holds it)."""
+    return round_bf16(t) if c.dtype == "bf16" else t.double()
+
+
+# A. (mx, mw) of a case, by seed; (5, 3) unless that leaves an output with fewer than 50 elements that are no bf16 numbers, or the case
+# with fewer than 50 elements that truncation / round-half-away would store differently (test_conv_epilogue_cpu.py asserts both):
+# 32 -> 2 channels 1x1: the data gradient sums TWO products, |dx| <= 4, and needs 91 to leave the exact range at all;
+# 2 -> 1 channels 7x7 has 297 + 594 outputs; groups = 8 sums 9 (y) and 18 (dx) products.
+ROUND_MULT = {14: (13, 7), 17: (5, 5), 57: (5, 5)}
+ROUND_CASES = [c for c in FWD_CASES if c.dtype == "bf16"]
+
+
+def round_mult(c):
+    return ROUND_MULT.get(c.seed, (5, 3))
+
+
+def y_nobias(B):
+    """The reference y of a built case without its (integer) bias."""
+    return B.ref["y"] if B.b is None else B.ref["y"] - B.b[None, :, None, None]
+
+
+# The statistics rows hold fp32 sums of stored values and of their squares over a part of the pixels.  They are exact in any order
+# while a row stays below 2^24 units of the coarsest grid its terms share -- and a row of a few hundred pixels whose values lie above
+# 256 cannot: its squares alone pass 2^24.  So the call WITH statistics is made twice where needed: at the case's multipliers (the
+# stored y bit for bit, and the sum row, whose terms stay small), and at the largest of STAT_MULTS whose squares fit, judged as
+# test_conv_exact_cpu.py judges the unscaled tables: a channel's whole sum fits, or its even share over the rows does with a factor 8
+# of headroom.  `unit` is the grid of the stored values: 1 for integers, 1/4 with the fractional bias of B (squares on 1/16).
+STAT_MULTS = [(5, 3), (3, 3), (5, 1), (3, 1), (1, 1)]
+
+
+def squares_fit(exact, rows, unit=1.0):
+    """Judged on the exact values: rounding to bf16 moves a value by at most 2^-8 of itself, its square by less than 1 %."""
+    sq = 1.01 * float((exact ** 2).sum((0, 2, 3)).max()) / (unit * unit)
+    return sq < SUM_LIMIT or 8 * sq / rows < SUM_LIMIT
+
+
+def stat_mult(c, y_exact_of, rows, unit=1.0, sums_only=False):
+    """-> ((mx, mw), True): the first of the case's own multipliers and STAT_MULTS, none above the case's, whose stored squares fit
+    the statistics rows; y_exact_of(mx * mw) -> the exact y at that scale.  Where none does -- with the quarter-grid bias of B the
+    squares lie on a grid of 1/16, and the rows of the large cases pass 2^20 even unscaled -- it raises, or with sums_only returns
+    ((1, 1), False): then the row of sums alone is compared (it stays below 2^22), the squares cannot be exact in fp32."""
+    own = round_mult(c)
+    for m in [own] + [m for m in STAT_MULTS if m[0] * m[1] < own[0] * own[1]]:
+        if squares_fit(y_exact_of(m[0] * m[1]), rows, unit):
+            return m, True
+    if sums_only:
+        return (1, 1), False
+    raise ValueError(f"{case_id(c)}: no multipliers keep the statistics rows exact")
+
+
+# B. a bias on the 0.25 grid in [-3, 3]: acc + bias is exact in fp32 (acc an integer below 2^22), and rounding the accumulator to bf16
+# BEFORE the bias is added gives another stored value in many elements.  Cases: every case of A with a bias and the first case of
+# every other forward kernel name (the bias is drawn apart from the case's operands, so those need no table row of their own).
+def frac_bias(c):
+    g = torch.Generator().manual_seed(7000 + c.seed)
+    whole, quarters = torch.randint(-3, 3, (c.Cout,), generator=g), torch.randint(1, 4, (c.Cout,), generator=g)
+    return whole.double() + quarters.double() / 4                 # never an integer: every channel's bias has a fraction
+
+
+def _bias_cases():
+    out = [c for c in FWD_CASES if c.bias]
+    for name in sorted(ALL_FWD_NAMES - {c.fwd for c in out}):
+        out.append(next(c for c in FWD_CASES if c.fwd == name))
+    return out
+
+
+BIAS_CASES = _bias_cases()
+
+
+# C. sigmoid and SiLU in the epilogue: the integer operands with x * 2^-5 and the bias of B.  v = y / 32 + b is a multiple of 2^-5 of
+# magnitude <= 8.5 (asserted): exact in fp32 in any order, and the float64 reference of act(v) starts from the same v as the kernel.
+# One ragged case per forward kernel name, by index into FWD_CASES.
+ACT_SCALE = 2.0 ** -5
+ACT_VMAX = 8.5
+ACT_DELTA = 1.5e-6             # relative error allowed to the fast bf16 path; derived in test_gpu_conv_epilogue.py, section C
+ACT_F32_REL = 2.0 ** -22       # ... and to the exact forms of the fp32 path
+ACT_CASE_INDEX = [3, 11, 7, 9, 15, 16, 18, 20, 22, 23, 51, 55, 25, 27, 59, 31, 34, 40, 41, 42, 43, 46, 47, 49]
+
+
+def act_ref(v, act):
+    """float64 sigmoid (act 2) / SiLU (act 3) of v, ReLU (1), identity (0)."""
+    v = v.double()
+    if act == 1:
+        return v.clamp_min(0)
+    if act == 2:
+        return 1.0 / (1.0 + torch.exp(-v))
+    if act == 3:
+        return v / (1.0 + torch.exp(-v))
+    return v
+
+
+def act_band(ref, delta):
+    """-> (lo, hi, rne, sure): the bf16 neighbours of the float64 reference (ordered by magnitude), its rne, and where the reference
+    lies farther than delta * |ref| from the midpoint of the two, so that a computation within delta of it must store rne."""
+    lo, hi = bf16_grid(ref)
+    sure = ((ref - (lo + hi) / 2).abs() > delta * ref.abs()) | (lo == hi)
+    return lo, hi, round_bf16(ref), sure
+
+
+# D. merged forward launches (egm_group_begin ... egm_group_end).  A member is (index into FWD_CASES, regime, call):
+#   regime 'int'   the table's operands and integer bias;
+#          'round' the operands of A with the fractional bias of B where the case has a bias (multipliers from stat_mult for a member
+#                  with statistics);
+#   call   'fwd' | 'stats' (forward with the BatchNorm partial sums) | 'dgrad' (dy with wd, counts swapped) | 'relu' (egm_conv_fwd_act
+#          on the integers, exact) | 'silu' (egm_conv_fwd_act on the operands of C, judged by the rule of C).
+# The kernel name a member must get INSIDE the open group is the table's, except 16 -> 16 7x7, which the group moves onto the
+# pipelined kernel (it has a merged form, conv7x7_c16_kernel has none).
+FWD_GROUPS = {
+    # five of one instantiation: egm_group_end batches them 4 + 1
+    "pipe333_2-five-stats": [(0, "round", "stats"), (1, "int", "stats"), (2, "round", "stats"), (3, "round", "stats"), (4, "int", "stats")],
+    "pipe111_2": [(13, "round", "fwd"), (14, "int", "fwd"), (15, "round", "stats")],
+    "pipe117_2-with-c16": [(17, "int", "fwd"), (30, "round", "fwd"), (18, "round", "stats")],
+    "pipe333_1": [(6, "int", "fwd"), (7, "round", "stats")],
+    "pipe333_4": [(8, "round", "fwd"), (9, "int", "stats")],
+    "direct1x1": [(24, "round", "fwd"), (25, "int", "stats")],
+    "direct3x3-dil12-24": [(26, "int", "fwd"), (58, "round", "fwd"), (27, "round", "stats")],
+    "direct3x3-64": [(29, "int", "stats"), (59, "round", "fwd")],
+    # A, B, C, A, D, B, A: two instantiations with merged forms interleaved with two kernels that have none
+    "interleaved": [(0, "int", "fwd"), (13, "int", "stats"), (21, "round", "fwd"), (3, "round", "stats"), (33, "round", "fwd"), (15, "int", "fwd"),
+                    (2, "round", "fwd")],
+    "dgrad-beside-fwd": [(0, "round", "fwd"), (3, "round", "dgrad"), (1, "int", "stats"), (2, "int", "dgrad")],
+    "pipe-act": [(0, "int", "silu"), (1, "int", "relu"), (3, "int", "silu")],
+    "direct-act": [(26, "int", "silu"), (58, "int", "relu"), (27, "int", "silu")],
+}
+IN_GROUP_NAME = {30: P + "<1, 1, 7, 2>"}
+
+# E. merged weight-gradient launches (egm_conv_wgrad_multi): indices into WGRAD_CASES, at most four per call, one dtype per call
+WGRAD_GROUPS = {
+    "ws9_1": [11, 1],                    # 12 tiles over 12 splits beside 70 over 64
+    "ws9_2": [9, 10, 29],                # ... beside 96 over 64
+    "ws9_4": [2, 6, 7, 8],               # 390 over 256, and three of one tile per split with padded channel counts
+    "ws7_0": [4, 13],
+    "ws5_0": [3, 12],
+    "wg1-1x1-beside-dilated": [14, 15],  # ONE z-block beside NINE in one launch
+    "wg3-beside-c16": [16, 17],
+    "f32-9": [21, 22, 23],
+    "f32-7": [24, 30, 25],
+    "three-instantiations-and-c16": [6, 9, 12, 18],
+}
+REDUCE_MULTI = [(8, 0), (19, 1), (20, 1), (6, 0)]         # (index into WGRAD_CASES, accumulate): 3 -> 2 channels in 8 -> 8, groups 2 and 8
 
 
 # ---- planner queries (no device needed) -----------------------------------------------------------------------------------------
