@@ -286,6 +286,38 @@ def clip_preprocess_batch(imgs_u8, size=(352, 352), mean=(0.485, 0.456, 0.406), 
     return out.view(B, 3, Sh, Sw)
 
 
+def renorm_affine(src_mean, src_std, dst_mean, dst_std):
+    """x normalised with (src_mean, src_std) -> the same pixel normalised with (dst_mean, dst_std) is x * a_c + b_c:
+    a_c = src_std / dst_std, b_c = (src_mean - dst_mean) / dst_std, computed in float64 and rounded once to fp32 -> (a, b) numpy fp32 [3]."""
+    sm, ss, dm, ds = (np.asarray(v, dtype=np.float64).reshape(3) for v in (src_mean, src_std, dst_mean, dst_std))
+    if not (ds != 0).all():
+        raise ValueError("egm_unet_amd.data.renorm_affine: zero std")
+    return (ss / ds).astype(np.float32), ((sm - dm) / ds).astype(np.float32)
+
+
+def renorm_resize(x, size=(352, 352), src_mean=(0.709, 0.381, 0.224), src_std=(0.127, 0.079, 0.043), dst_mean=(0.485, 0.456, 0.406),
+                  dst_std=(0.229, 0.224, 0.225), antialias=True, out=None):
+    """A batch normalised for one model as the input of another: fp32 [N, 3, H, W] on the device, normalised with (src_mean, src_std)
+    (the UNet's training crop) -> fp32 [N, 3, Sh, Sw] = F.interpolate(x * a_c + b_c, size, mode="bilinear", align_corners=False,
+    antialias=antialias) with (a, b) of renorm_affine, i.e. what clip_preprocess makes of the same pixels.  The filter tables are
+    float_filter_tables'; two launches whatever N (csrc/distill.hip; DESIGN.md 6.35 fixes the arithmetic order).  More than 64 taps on
+    an axis raise clip_preprocess_batch's error.  out: an optional contiguous fp32 buffer of N * 3 * Sh * Sw elements."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.shape[0] > 0):
+        raise RuntimeError("egm_unet_amd.data.renorm_resize: a non-empty CUDA float32 batch [N, 3, H, W] expected")
+    x = x.contiguous()
+    N, _, H, W = x.shape
+    Sh, Sw = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    xb, xw, xk = float_filter_tables(W, Sw, antialias, x.device)
+    yb, yw, yk = float_filter_tables(H, Sh, antialias, x.device)
+    out = _check_batch_out(out, (N, 3, Sh, Sw), x.device, "renorm_resize")
+    tmp = torch.empty((N, 3, H, Sw), dtype=torch.float32, device=x.device)
+    a, b = renorm_affine(src_mean, src_std, dst_mean, dst_std)
+    a3, b3 = (ctypes.c_float * 3)(*a.tolist()), (ctypes.c_float * 3)(*b.tolist())
+    lib().call("egm_renorm_resize_f32", ptr(x), N, H, W, ptr(out), Sh, Sw, ptr(xb), ptr(xw), xk, ptr(yb), ptr(yw), yk,
+               ctypes.cast(a3, ctypes.c_void_p), ctypes.cast(b3, ctypes.c_void_p), ptr(tmp), stream())
+    return out.view(N, 3, Sh, Sw)
+
+
 # ---- a whole training batch of ragged photos per call (csrc/train_batch.hip) -------------------------------------------------------
 # The host plans, the device does the pixel work in two launches: per image the draws fix which resized rows and columns the crop can
 # see, the plan cuts the filter and index tables to those windows and packs them behind the descriptor rows (egm_train_desc,

@@ -58,11 +58,16 @@ def _collector_rests():
 
 class GraphedTrainStep:
     def __init__(self, model, optimizer, example_image, example_target, loss_weight=None, num_classes=2, ignore_index=255,
-                 reducer=None, warmup=3, restore_after_warmup=False, split=None, boundary=None, lovasz=None):
+                 reducer=None, warmup=3, restore_after_warmup=False, split=None, boundary=None, lovasz=None, distill=None):
         self.model, self.opt, self.reducer = model, optimizer, reducer
         self.lw, self.nc, self.ign = loss_weight, num_classes, ignore_index
         self.boundary = boundary                      # a BoundaryLoss added to the criterion; its weight is read from device memory
         self.lovasz = lovasz                          # a LovaszSoftmax or LovaszHinge added to the criterion, likewise
+        # a Distill added to the criterion: the teacher's forward on self.x runs inside the graph ahead of the student's (prepare), its
+        # refold outside, before every warm-up step, the capture and every replay (refresh)
+        self.distill = distill
+        if distill is not None:
+            distill.bind(model)
         self.x = example_image.clone()
         self.t = example_target.clone()
         self.trace = []                               # host-order log of the last call (tests assert the overlap structure on it)
@@ -123,13 +128,16 @@ class GraphedTrainStep:
         self._cap_mode = "thread_local" if (_dist.is_available() and _dist.is_initialized()) else "global"
         want_split = self.reducer is not None and (self.reducer.world > 1 if split is None else split)
         self.split = bool(want_split and hasattr(model, "ddp_boundary") and len(self.reducer.buckets) == 2)
+        self._refresh_teacher()
         if self.split:
             self._capture_split()
         else:
             self.graph = torch.cuda.CUDAGraph()
             with _collector_rests(), self._ns, torch.cuda.graph(self.graph, capture_error_mode=self._cap_mode):
+                if self.distill is not None:
+                    self.distill.prepare(self.x)
                 loss = criterion(self.model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
-                                 boundary=self.boundary, lovasz=self.lovasz)
+                                 boundary=self.boundary, lovasz=self.lovasz, distill=self.distill)
                 loss.backward(self._one)                  # the seed gradient is a resident tensor, not a fill launch per replay
                 if self.reducer is None:
                     self.opt.step()
@@ -143,9 +151,11 @@ class GraphedTrainStep:
         self.gA, self.gB, self.gC = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         b0, b1 = red.buckets
         with _collector_rests(), self._ns, torch.cuda.graph(self.gA, capture_error_mode=self._cap_mode):
+            if self.distill is not None:
+                self.distill.prepare(self.x)
             model.ddp_boundary = []                   # forward() fills it with the encoder -> decoder tensors
             loss = criterion(model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
-                             boundary=self.boundary, lovasz=self.lovasz)
+                             boundary=self.boundary, lovasz=self.lovasz, distill=self.distill)
             bnd = list(model.ddp_boundary)
             # the decoder half of backward: stops at the boundary tensors (their gradients land in .grad) and at bucket 0's parameters
             torch.autograd.backward(loss, self._one, inputs=list(b0) + bnd, retain_graph=True)
@@ -181,9 +191,25 @@ class GraphedTrainStep:
             self._lr_event = torch.cuda.Event()
         self._lr_event.record()
 
+    def _refresh_teacher(self):
+        """The distillation teacher's refold, outside any graph.  A teacher that reports moved buffers (EnsembleTeacher.stale: the
+        CLIPSeg model changed) cannot be followed by a captured step."""
+        if self.distill is None:
+            return
+        self.distill.refresh()
+        if getattr(self.distill.teacher, "stale", False):
+            if not (hasattr(self, "graph") or hasattr(self, "gA")):
+                self.distill.teacher.stale = False     # before the capture: the graph is going to hold the buffers of now
+                return
+            raise RuntimeError("GraphedTrainStep: the distillation teacher's CLIPSeg model changed after the capture (parameters, compute "
+                               "dtype or cast-weight buffers); a captured step cannot follow it: build a new step")
+
     def _eager(self):
+        if self.distill is not None:
+            self._refresh_teacher()
+            self.distill.prepare(self.x)
         loss = criterion(self.model(self.x), self.t, self.lw, num_classes=self.nc, ignore_index=self.ign,
-                         boundary=self.boundary, lovasz=self.lovasz)
+                         boundary=self.boundary, lovasz=self.lovasz, distill=self.distill)
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         if self.reducer is not None:
@@ -197,6 +223,7 @@ class GraphedTrainStep:
             self.t.copy_(target, non_blocking=True)
         if self._own_lr:
             self._push_lr()
+        self._refresh_teacher()
         tr = self.trace = []
         if self.split:
             red, cur = self.reducer, torch.cuda.current_stream()

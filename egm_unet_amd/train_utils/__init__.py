@@ -3,3 +3,4 @@ from .distributed_utils import init_distributed_mode, ConfusionMatrix, DiceCoeff
 from .boundary_loss import BoundaryLoss, signed_distance2, distance_maps  # noqa: F401
 from .lovasz_loss import LovaszSoftmax, sort_pairs, lovasz_errors, lovasz_coefs  # noqa: F401
 from .lovasz_loss import LovaszHinge, hinge_errors, hinge_coefs  # noqa: F401
+from .distill_loss import Distill, ModelTeacher, EnsembleTeacher  # noqa: F401

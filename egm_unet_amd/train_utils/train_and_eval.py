@@ -6,11 +6,13 @@ from .dice_coefficient_loss import fused_criterion
 
 
 def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool = True, ignore_index: int = -100, boundary=None,
-              lovasz=None):
+              lovasz=None, distill=None):
     """Five-term loss of the reference (CE + Dice + Laplace + Lap + Sobel); `out` (+0.5*`aux`) convention kept.
     boundary: a boundary_loss.BoundaryLoss; every head's loss then gets w * L_B added (the distance maps of the target are made once).
     lovasz: a lovasz_loss.LovaszSoftmax, or a lovasz_loss.LovaszHinge with channels=(c_pos, c_neg); every head's loss then gets w * L
-    added, after the boundary term."""
+    added, after the boundary term.
+    distill: a distill_loss.Distill whose teacher logits are prepared (distill.prepare(image) or set_teacher_logits); every head's loss
+    then gets w * L_KD added, after the Lovasz term."""
     losses = {}
     sdf = boundary.sdf(target) if boundary is not None and target.is_cuda else None
     for name, x in inputs.items():
@@ -21,6 +23,8 @@ def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool
             losses[name] = losses[name] + boundary.loss(x, target, sdf=sdf)
         if lovasz is not None:
             losses[name] = losses[name] + lovasz.loss(x, target)
+        if distill is not None:
+            losses[name] = losses[name] + distill.loss(x, target)
     if len(losses) == 1:
         return losses["out"]
     return losses["out"] + 0.5 * losses["aux"]
@@ -52,7 +56,7 @@ def _graphable(model, optimizer, device):
 
 
 def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler, print_freq=10, scaler=None,
-                    boundary=None, lovasz=None):
+                    boundary=None, lovasz=None, distill=None):
     """scaler != None selects the reduced-precision path like the reference's autocast+GradScaler branch; on MI355X that
     is bf16 activation storage with fp32 accumulation and fp32 master weights, which needs no loss scaling.
 
@@ -66,7 +70,11 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
     boundary: a boundary_loss.BoundaryLoss added to the criterion of every step; its weight is a device scalar, so
     boundary.set_weight(...) between epochs is followed by the replayed step.
     lovasz: a lovasz_loss.LovaszSoftmax or LovaszHinge(channels=...), added the same way (under data parallel each rank takes the loss
-    of its own batch)."""
+    of its own batch).
+    distill: a distill_loss.Distill with a teacher, added the same way: the teacher's forward on the batch runs inside the replayed
+    graph, its refold (distill.refresh()) before every step outside it; distill.set_weight(...) is followed by the replayed step."""
+    if distill is not None:
+        distill.bind(model)
     model.train()
     metric_logger = utils.MetricLogger(delimiter="  ")
     metric_logger.add_meter("lr", utils.SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -84,12 +92,14 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
         # up to a step behind the host: a single buffer let the copy of step i pick up the learning rate of step i+1)
         lr_pinned = [torch.zeros(1, dtype=torch.float32).pin_memory() for _ in range(2)]
         lr_events = [None, None]
-        # a step captured in an earlier epoch is reused while model, optimizer, precision, class count, boundary and Lovasz term are the
-        # same objects / values (the key holds the term objects themselves, compared by identity: a step without a term is never one
-        # with it)
+        # a step captured in an earlier epoch is reused while model, optimizer, precision, class count, boundary, Lovasz and distillation
+        # term are the same objects / values (the key holds the term objects themselves, compared by identity: a step without a term is
+        # never one with it)
         # (its graph holds the pointer of ITS lr scalar, so that tensor comes back with it)
         import weakref
         key = (getattr(core, "compute_dtype", None), num_classes, boundary, lovasz)
+        if distill is not None:
+            key += (distill,)               # a fifth field only with the term: keys of different lengths are never equal
         cached = getattr(model, "_egm_train_graph", None)
         if cached is not None and cached[0] == key and cached[4]() is optimizer:      # the very same optimizer object, still alive
             _, step, step_shape, optimizer.lr_dev, _ = cached
@@ -125,14 +135,17 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
             from ..graph import GraphedTrainStep
             # warmup=1: the eager warm-up IS this batch's training step; capture records the next ones without executing anything
             step = GraphedTrainStep(model, optimizer, image, target, loss_weight, num_classes=num_classes, ignore_index=255, warmup=1,
-                                    boundary=boundary, lovasz=lovasz)
+                                    boundary=boundary, lovasz=lovasz, distill=distill)
             step_shape = shape
             model._egm_train_graph = (key, step, step_shape, optimizer.lr_dev, weakref.ref(optimizer))
             loss = step.warmup_loss
         else:
+            if distill is not None:
+                distill.refresh()
+                distill.prepare(image)
             output = model(image)
             loss = criterion(output, target, loss_weight, num_classes=num_classes, ignore_index=255, boundary=boundary,
-                             lovasz=lovasz)
+                             lovasz=lovasz, distill=distill)
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()

@@ -1127,6 +1127,43 @@ int egm_bloss_fwd(const float* logits, const int* sdf, const long long* target, 
 int egm_bloss_bwd(const float* logits, const int* sdf, const int* classes, int K, int N, int C, int H, int W, const void* workspace,
                   const float* grad_out, const float* w_dev, float* dlogits, egm_stream_t s);
 
+/* ---- Distillation against a frozen teacher (csrc/distill.hip, train_utils/distill_loss.py)
+ * Hinton, Vinyals, Dean, "Distilling the knowledge in a neural network" (2015).
+ * Student logits x fp32 [N][C][H][W], teacher logits z of teacher_dtype (EGM_F32 or EGM_BF16) in the same shape, C <= 16; target int64
+ * [N][H][W] or NULL.  A pixel is valid when (target == NULL or has_ignore == 0 or target != ignore_index) and
+ * (tau == 0 or max_c softmax(z)_c >= tau, at temperature 1), tau = tau_dev[0] read on the DEVICE.  With q = softmax(x / T),
+ * p = softmax(z / T), V = the valid pixels of the batch (an integer count):
+ *   L_KD = T^2 / max(1, V) * sum over the valid pixels of sum_c p_c (log p_c - log q_c),  log-softmax in the max-subtracted form
+ * egm_distill_fwd: out2 = {w L_KD, L_KD} with w = w_dev[0] read on the device, valid_out[0] = V (NULL: not written); no valid pixel
+ *   gives 0.  workspace: egm_distill_workspace(N, C, H, W) bytes, 4-byte aligned, kept for the backward (per workgroup partial sums
+ *   written with plain stores and summed in a fixed order in double, the counts, 1 / max(1, V)).  Two launches, no atomics.
+ * egm_distill_bwd: dlogits[n][c][p] = grad_out[0] (1 when NULL) * w * T / max(1, V) * (q_c - p_c) at a valid pixel, exactly 0
+ *   elsewhere; both softmaxes are recomputed, every element is written.  One launch.
+ *   Four pixels per lane where C <= 4, H*W is a multiple of 4 and every plane starts at a boundary of its four-pixel load (16 bytes of
+ *   fp32, 8 of bf16), one otherwise: the same dlogits either way.  egm_distill_blocks() = the workgroups per image of both passes.
+ * egm_pseudo_target_i64: out int64 [N][H][W] = argmax_c z (ties to the lowest class, as egm_argmax_u8) where the confidence
+ *   max_c softmax(z)_c >= tau and existing (int64 [N][H][W] or NULL) is not ignore_index there; ignore_index elsewhere.  One launch.
+ * A null pointer, C > 16, T <= 0, N > 65535 or another teacher_dtype: EGM_ERR_ARG with a message before any launch. */
+int egm_distill_blocks(void);
+long long egm_distill_workspace(int N, int C, int H, int W);
+int egm_distill_fwd(const float* logits, const void* teacher, int teacher_dtype, const long long* target, int N, int C, int H, int W,
+                    int has_ignore, long long ignore_index, float temperature, const float* w_dev, const float* tau_dev, void* workspace,
+                    float* out2, long long* valid_out, egm_stream_t s);
+int egm_distill_bwd(const float* logits, const void* teacher, int teacher_dtype, const long long* target, int N, int C, int H, int W,
+                    int has_ignore, long long ignore_index, float temperature, const float* w_dev, const float* tau_dev,
+                    const void* workspace, const float* grad_out, float* dlogits, egm_stream_t s);
+int egm_pseudo_target_i64(const void* teacher, int teacher_dtype, const long long* existing, int N, int C, int H, int W,
+                          long long ignore_index, const float* tau_dev, long long* out, egm_stream_t s);
+/* egm_renorm_resize_f32: x fp32 [N][3][H][W] normalised with one (mean, std) -> out fp32 [N][3][Sh][Sw] =
+ *   F.interpolate(x * a_c + b_c, (Sh, Sw), mode="bilinear", align_corners=False, antialias=...) with the tables of
+ *   data.float_filter_tables (egm_clip_preprocess_u8's contract); a3_host, b3_host: HOST arrays of the per-channel affine map.
+ *   tmp[n][c][y][xo] = sum_j wx[xo][j] * fmaf(x[n][c][y][x0 + j], a_c, b_c), then out[n][c][yo][xo] = sum_j wy[yo][j] * tmp[n][c][y0 + j][xo];
+ *   both sums start at 0 and take their taps in table order, each step one fmaf(weight, value, sum).  tmp: N * 3 * H * Sw floats.
+ *   Two launches whatever N.  More than 64 taps on an axis: EGM_ERR_ARG with egm_clip_preprocess_batch_u8's message. */
+int egm_renorm_resize_f32(const float* x_nchw, int N, int H, int W, float* out_nchw, int Sh, int Sw, const int* xbounds,
+                          const float* xweights, int xksize, const int* ybounds, const float* yweights, int yksize, const float* a3_host,
+                          const float* b3_host, float* tmp_nchw, egm_stream_t s);
+
 /* ---- Stable radix sort of (key, value) pairs (csrc/sort.hip)
  * egm_sort_pairs_u32: keys, vals uint32 [S][L] -> keys_out, vals_out [S][L]: each of the S segments sorted ascending on the key bits
  *   [begin_bit, end_bit), 0 <= begin_bit < end_bit <= 32 (the other bits travel with the key and are not looked at); elements with equal
